@@ -19,7 +19,9 @@ same on the headline's bodies, config 2 (65 536 direct), mass classes, free per-
 (direct), config 4 (4 194 304 bodies, quad tree, theta 0.5, f64; the reference's arithmetic and the opt-in FAST one).  The
 explanatory notes every record used to repeat live once in profiles/README.md ("Reading a bench line").  `--full-out PATH`
 also writes the unabridged records (headline + legs) to PATH; `--leg NAME` runs one leg alone and prints its unabridged
-record (what the rocprofv3 passes under profiles/ are taken on).
+record (what the rocprofv3 passes under profiles/ are taken on).  `--dump-outputs DIR` writes the headline path's positions and
+velocities after its last timed step to DIR/*.npy (the inputs are seeded: two builds run with the same arguments compare array
+for array).
 """
 import argparse
 import json
@@ -428,6 +430,45 @@ def emit_headline(full, legs_full, full_out=None):
     print(dumps_line(compact_headline(full, legs_full), HEADLINE_MAX_BYTES), flush=True)
 
 
+# ---------------------------------------------------------------------------------------------------- --dump-outputs
+DUMP_MAX_BYTES = 64 << 20   # all .npy files of one dump together
+DUMP_SEED = 0x5EED00D0      # the row sample when the whole state would not fit
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs DIR: what the timed path handed its caller after its last step, one DIR/<name>.npy per array
+    (float32 / float64, rows = bodies in input order).  When the arrays together exceed DUMP_MAX_BYTES, every array keeps the
+    same fixed, seeded sample of rows (sorted), so two builds run with the same arguments dump comparable files."""
+    n = next(iter(arrays.values())).shape[0]
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64) or a.shape[0] != n:
+            raise ValueError(f"bench.py: dump array {name!r} is {a.dtype} with {a.shape[0]} rows (float32/float64, {n} rows expected)")
+    row_bytes = sum(a.nbytes // max(1, n) for a in arrays.values())
+    budget = DUMP_MAX_BYTES - 4096 * len(arrays)                  # room for the .npy headers
+    rows = None
+    if row_bytes * n > budget:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, budget // row_bytes, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a if rows is None else a[rows]))
+
+
+def _stepper_state(stepper, world):
+    """-> (positions[n,2], velocities[n,2]) after the stepper's last step.  Positions are replicated on every rank; velocities
+    live with the rank that owns the row, so with several ranks they are collected (a collective: every rank calls this)."""
+    pos = stepper.all_positions()
+    rows, (_, vel_local) = stepper.local_rows(), stepper.local_state()
+    parts = [(rows, vel_local)]
+    if world > 1:
+        import torch.distributed as dist
+        parts = [None] * world
+        dist.all_gather_object(parts, (rows, vel_local))
+    vel = np.zeros((stepper.n, 2), np.float32)
+    for r, v in parts:
+        vel[r] = v
+    return pos, vel
+
+
 def _headline_roofline(n, n_tgt, kern_ms, kern_launches, steps, single_gpu_full):
     n_launch = max(1, kern_launches // max(1, steps))      # launches of the dominant kernel per step (= chunks)
     flops_per_launch = FLOPS_PER_PAIR * float(n) * float(n_tgt) / n_launch
@@ -484,6 +525,11 @@ def run_in_library(args):
         elapsed = time.perf_counter() - t0
         kern_ms, kern_launches = timer.read(reset=True)
         ctx.set_timer(None)
+        if args.dump_outputs:
+            p, v, _, ids = ctx.download()
+            pos_out, vel_out = np.empty_like(p), np.empty_like(v)
+            pos_out[ids], vel_out[ids] = p, v                  # rows back in input order
+            dump_outputs(args.dump_outputs, {"positions": pos_out, "velocities": vel_out})
         g, xch, chunks, block = ctx.multi_info()
         n_ranks = ctx.comm_count()
     # device 0's targets (its kernels are the ones timed): blocks {c*G + 0}
@@ -515,7 +561,12 @@ def main():
     ap.add_argument("--in-library", action="store_true", help="run the step through nbody_create_multi (one process) even for --gpus 1")
     ap.add_argument("--devices", default=None, help="in-library path: comma-separated device ids (default 0..gpus-1; one id may "
                                                     "repeat under NBODY_MULTI_EXCHANGE=peer to rehearse on one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (positions.npy, "
+                         "velocities.npy: float32 [n,2] in input order; a fixed, seeded row sample beyond 64 MB) to DIR")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # The launch convention is decided before anything touches a GPU, and nothing is ever re-executed: under an external
     # launcher (torch.distributed.run sets WORLD_SIZE) this is one rank of N processes; without one, `--gpus N > 1` runs
@@ -583,6 +634,10 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs:
+        pos_out, vel_out = _stepper_state(stepper, world)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"positions": pos_out, "velocities": vel_out})
 
     if rank == 0:
         n_tgt = stepper.n_local

@@ -121,3 +121,44 @@ def test_free_weights_leg_has_no_mass_classes(bench):
     assert np.array_equal(w, scenes.free_weights(1 << 20, seed=bench.SEED))
     assert np.array_equal(w[1000:2000], scenes.free_weights(1000, seed=bench.SEED, start=1000))
     assert "free_masses" in bench.LEGS and "mass_classes" in bench.LEGS
+
+
+def test_dump_outputs_writes_whole_arrays_under_the_budget(bench, tmp_path):
+    import numpy as np
+    pos = np.arange(2000, dtype=np.float32).reshape(-1, 2)
+    vel = -pos
+    bench.dump_outputs(str(tmp_path / "d"), {"positions": pos, "velocities": vel})
+    assert sorted(p.name for p in (tmp_path / "d").iterdir()) == ["positions.npy", "velocities.npy"]
+    assert np.array_equal(np.load(tmp_path / "d" / "positions.npy"), pos)
+    assert np.array_equal(np.load(tmp_path / "d" / "velocities.npy"), vel)
+
+
+def test_dump_outputs_samples_the_same_rows_of_every_array_beyond_the_budget(bench, tmp_path, monkeypatch):
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 64 << 10)
+    n = 10000
+    pos = np.stack([np.arange(n), np.arange(n) + 0.5], axis=1).astype(np.float64)
+    vel = pos.astype(np.float32) * 2
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"positions": pos, "velocities": vel})
+    total = sum(p.stat().st_size for p in (tmp_path / "a").iterdir())
+    assert total <= bench.DUMP_MAX_BYTES
+    p, v = np.load(tmp_path / "a" / "positions.npy"), np.load(tmp_path / "a" / "velocities.npy")
+    assert p.dtype == np.float64 and v.dtype == np.float32 and 0 < len(p) < n
+    rows = p[:, 0].astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(v, vel[rows])          # one sorted sample, shared by both arrays
+    assert np.array_equal(p, np.load(tmp_path / "b" / "positions.npy"))       # fixed seed: the same sample every run
+
+
+def test_dump_outputs_refuses_non_float_arrays(bench, tmp_path):
+    import numpy as np
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path), {"ids": np.arange(8, dtype=np.uint32)})
+
+
+def test_steps_below_one_is_refused(bench, monkeypatch):
+    import sys
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2
