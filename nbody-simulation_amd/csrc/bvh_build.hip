@@ -629,7 +629,7 @@ __device__ __forceinline__ int alloc_nodes(const BvhPtrs& a, int count) {
 __global__ __launch_bounds__(256) void bvh_init(BvhPtrs a, const float2* __restrict__ pos, int n, unsigned long long* __restrict__ stamp_begin,
                                                 unsigned long long* __restrict__ stamp_prev_end) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i == 0 && (stamp_begin || stamp_prev_end)) {  // phase clock (capi.hip, PhaseStamps): this step begins where the one before ends
+  if (i == 0 && (stamp_begin || stamp_prev_end)) {  // phase clock (tree_driver.hip, stamp_*): this step begins where the one before ends
     const unsigned long long now = (unsigned long long)wall_clock64();
     if (stamp_begin) *stamp_begin = now;
     if (stamp_prev_end) *stamp_prev_end = now;

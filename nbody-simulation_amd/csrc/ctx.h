@@ -1,4 +1,4 @@
-// Internal: the context of libnbody_hip and the functions its translation units share (capi.hip: one device;
+// Internal: the context of libnbody_hip and the functions its translation units share (the driver: one device;
 // multi.hip: several devices behind the same handle).  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -89,12 +89,9 @@ template <class T> struct State {
 // The `uniform_mass` argument of the direct step for this state: > 0 all equal, < 0 all equal to its magnitude but a few, 0 neither.
 template <class T> inline float direct_mass_hint(const State<T>& s) { return s.uniform_mass > 0.f ? s.uniform_mass : -s.sparse_base; }
 
-}  // namespace nbody
-
 // Two consecutive direct steps (A -> B -> A position buffers) captured once as a hipGraph and replayed: a small-N step
 // is ~15 launches (hazard scan, near/far split, gated kernels), i.e. launch-bound (N = 1024: 78 us per eager step
 // against 13 us of kernels).  The graph is rebuilt when anything it baked in changes.
-namespace nbody {
 struct DirectGraph {
   hipGraphExec_t exec = nullptr;
   int64_t n = -1;
@@ -126,9 +123,6 @@ inline std::string direct_env_signature() {
   return sig;
 }
 
-}  // namespace nbody
-
-namespace nbody {
 // The three phases of a tree step (Counting, main.rs:74-79) timed by four events on the step's stream: the stream idles
 // while the host works inside a phase (a host-side build), so device-timeline intervals cover host time too, and no
 // phase boundary needs a host synchronisation.
@@ -186,7 +180,7 @@ struct nbody_ctx {
   uint32_t frame_px = 0;
   unsigned long long last_stats[3] = {0, 0, 0};
   bool want_stats = false;
-  // Phase clock of the steps enqueued ahead (capi.hip, bvh_step_ahead): instead of three event records per step (each ~6 us of idle
+  // Phase clock of the steps enqueued ahead (tree_driver.hip, bvh_step_ahead): instead of three event records per step (each ~6 us of idle
   // stream) the step's own kernels write the 100 MHz wall clock at the phase boundaries: slot = {build begins, walk begins,
   // integration begins, step ends}; read back when the phases are drained.
   unsigned long long* stamp_dev = nullptr;               // [kStampSlots][4]
@@ -196,16 +190,15 @@ struct nbody_ctx {
   std::vector<nbody::PhaseEvents> ph_pending;           // recorded phase events
   std::vector<hipEvent_t> ph_free;                       // reusable events
   nbody_counting* ph_counter = nullptr;                // the caller's counter of the call in progress
-  // a BVH step enqueued whole, ahead of the host's knowledge of its build (capi.hip, bvh_step_ahead)
+  // a BVH step enqueued whole, ahead of the host's knowledge of its build (tree_driver.hip, bvh_step_ahead)
   int* spec_dev = nullptr;    // [2] verdict of the build: node count or 0, ok
   int* spec_host_dev = nullptr;  // spec_host as the device addresses it (kernels write the record there themselves)
   int* spec_host = nullptr;   // pinned: verdict [2] | build flags + level counters [128] | walk info before [8] and after [8] the walk
   hipEvent_t spec_event = nullptr;
 };
 
-
 namespace nbody {
-// ---- capi.hip
+// ---- the single-device driver: capi.hip (context, upload), tree_driver.hip (tree steps), direct_driver.hip (direct steps)
 int ctx_fail(nbody_ctx* c, int code, const std::string& msg);  // c == NULL: the thread's create error
 int ctx_create_single(nbody_ctx** out, int device_id);
 void ctx_destroy_single(nbody_ctx* c);

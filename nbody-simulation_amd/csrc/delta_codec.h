@@ -1,5 +1,5 @@
 // Delta-snapshot stream "NBD1" (SURVEY §8f-4): the format, shared by the device encoder (delta_snapshot.hip) and the
-// host decoder (capi.hip).  Upstream has only a commented-out experiment that prints the zstd size of raw position
+// host decoder (snapshot.hip).  Upstream has only a commented-out experiment that prints the zstd size of raw position
 // differences (main.rs:119-134): there is no format to match, this one is ours.  Lossless on the bit patterns.
 //
 //   element   a coordinate's bits (u32 for f32 contexts, u64 for f64), mapped to an ordered integer key:

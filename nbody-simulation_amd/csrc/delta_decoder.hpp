@@ -1,5 +1,5 @@
 // Host decoder of the delta-snapshot stream (format: delta_codec.h).  Plain C++ (no HIP), so that the sanitizer
-// harness of tests/native/ can compile it with g++; capi.hip wraps it as nbody_delta_decoder_*.  The stream comes from
+// harness of tests/native/ can compile it with g++; snapshot.hip wraps it as nbody_delta_decoder_*.  The stream comes from
 // outside (a channel, a file): everything is validated before the state is touched.
 #pragma once
 #include <cstdint>

@@ -30,7 +30,7 @@ struct DirectArgs {
   const uint32_t* near_list;  // near sources (ascending body index), count in flags[kFlagNearCount]
   int src_couples;            // src_pos is in couples {xA, xB, yA, yB} (nearfar.hip, far_store<true>), n_src a multiple of kFarPad
   const float* src_minv;      // free per-body masses, streamed main pass: 1 / mass in the far copy's slot order (nearfar.hip); null otherwise
-  const float* tile_mass;     // mass classes (capi.hip): src_pos is ordered by mass class, every 1024-source tile holds ONE class
+  const float* tile_mass;     // mass classes (direct_driver.hip): src_pos is ordered by mass class, every 1024-source tile holds ONE class
                               // (classes padded with far-away points) and tile_mass[tile] is its mass; null otherwise
 };
 

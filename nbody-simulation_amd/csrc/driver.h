@@ -1,0 +1,131 @@
+// Internal: the host plumbing the single-device driver's translation units share (capi.hip, direct_driver.hip,
+// tree_build_driver.hip, tree_driver.hip, caller_tree.hip, snapshot.hip) — error reporting, device buffers, and the
+// bookkeeping every tree build and walk repeats.  Not part of the C ABI; multi.hip needs only ctx.h.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <string>
+
+#include "bvh_build.h"
+#include "ctx.h"
+#include "tree_kernels.h"
+
+#define NB_API extern "C" __attribute__((visibility("default")))
+
+namespace nbody {
+
+int fail(nbody_ctx* c, int code, const std::string& msg);  // c == NULL: the thread's create error (capi.hip)
+inline int fail_hip(nbody_ctx* c, hipError_t e, const char* what) {
+  return fail(c, NBODY_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+#define HIPCHK(c, call)                                   \
+  do {                                                    \
+    hipError_t e__ = (call);                              \
+    if (e__ != hipSuccess) return fail_hip(c, e__, #call); \
+  } while (0)
+
+inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+template <class P> void free_dev(P*& p) { if (p) (void)hipFree((void*)p); p = nullptr; }
+template <class P> void free_host(P*& p) { if (p) (void)hipHostFree((void*)p); p = nullptr; }  // (pinned)
+// A device buffer of at least `need` bytes; a smaller one is freed and replaced (its contents are not kept).
+template <class P> int ensure_dev_bytes(nbody_ctx* c, P*& p, size_t& bytes, size_t need) {
+  if (bytes >= need) return NBODY_OK;
+  free_dev(p);
+  bytes = 0;
+  HIPCHK(c, hipMalloc((void**)&p, need));
+  bytes = need;
+  return NBODY_OK;
+}
+
+template <class T> State<T>& state_of(nbody_ctx* c);
+template <> inline State<float>& state_of<float>(nbody_ctx* c) { return c->sf; }
+template <> inline State<double>& state_of<double>(nbody_ctx* c) { return c->sd; }
+template <class T> bool has_state(const nbody_ctx* c);
+template <> inline bool has_state<float>(const nbody_ctx* c) { return c->has_f32; }
+template <> inline bool has_state<double>(const nbody_ctx* c) { return c->has_f64; }
+
+// ---- tree bookkeeping
+// The rows set[cur] gathered into set[1 - cur] in the order `perm`, every column: as the in-place partition leaves
+// `self.particles` (bvh_tree.rs:73-77).  The quad tree's leaf copies clear the outputs they do not need.
+template <class T> GatherArgs<T> row_gather_args(const State<T>& s, const uint32_t* perm) {
+  const auto& in = s.set[s.cur];
+  const auto& out = s.set[1 - s.cur];
+  GatherArgs<T> g{};
+  g.perm = perm;
+  g.n = s.n;
+  g.pos_in = in.pos; g.pos_out = out.pos;
+  g.vel_in = in.vel; g.vel_out = out.vel;
+  g.weight_in = in.weight; g.weight_out = out.weight;
+  g.ids_in = in.ids; g.ids_out = out.ids;
+  g.mass_out = out.mass;
+  return g;
+}
+
+// A finished build becomes the context's tree.  `rows_permuted`: the build gathered the rows into tree order in set[1 - cur],
+// which becomes the current set (a BVH; the quad tree leaves the rows where they are).  `on_device`: the host has neither
+// the tree nor, for permuted rows, the weights in their new order.
+template <class T>
+void commit_tree(nbody_ctx* c, State<T>& s, int kind, int n_nodes, int max_depth, int stops, bool rows_permuted, bool on_device) {
+  if (rows_permuted) {
+    s.cur = 1 - s.cur;
+    ++s.row_epoch;
+    if (on_device) s.h_weight_stale = true;
+  }
+  s.n_nodes = n_nodes;
+  s.tree_kind = kind;
+  s.tree_max_depth = max_depth;
+  s.tree_host_stale = on_device;
+  s.tree_valid = true;
+  c->bvh_stops = stops;
+}
+
+// How many long-node levels a device-built BVH had (`bigcount`: the build's level counters): what a step enqueued ahead
+// of the host enqueues blind next time.  A step-ahead build (`ahead`) counts the builds for which that number has
+// stood (bvh_step_ahead drops its spare level after eight); any other build starts that count again.
+template <class T> void record_bvh_levels(State<T>& s, const int* bigcount, bool ahead) {
+  int used = 0;
+  while (used < kBvhLevels - 1 && bigcount[used] != 0) ++used;
+  s.bvh_levels_stable = (ahead && used == s.bvh_levels_hint) ? s.bvh_levels_stable + 1 : 0;
+  s.bvh_levels_hint = used;
+}
+
+// The walk's parameters and tree arrays; the caller sets the leaves, the targets, `acc` and the node count.
+template <class T> WalkArgs<T> walk_args(const nbody_ctx* c, const State<T>& s, int kind) {
+  WalkArgs<T> w{};
+  w.geom0 = s.geom0; w.geom1 = s.geom1; w.link = s.link;
+  w.big_leaves = kind == NBODY_TREE_BVH && c->params.leaf_size >= 16;
+  w.fast = c->params.arith == NBODY_ARITH_FAST;  // AUTO and EXACT walk with the reference's operations
+  w.theta = (T)c->params.theta;
+  w.clamp = (T)c->params.clamp;
+  return w;
+}
+
+// ---- shared between the translation units
+void free_snapshot(nbody_ctx* c);  // snapshot.hip
+void free_delta(nbody_ctx* c);
+template <class T> int refresh_host_weights(nbody_ctx* c, State<T>& s);  // tree_build_driver.hip
+template <class T> int install_host_tree(nbody_ctx* c, State<T>& s, int kind);
+template <class T> int tree_build_phase(nbody_ctx* c, State<T>& s, int kind);
+template <class T> int download_tree(nbody_ctx* c, State<T>& s);
+template <class T>  // tree_driver.hip
+int accel_built_tree(nbody_ctx* c, State<T>& s, int kind, int64_t n_targets, const T* target_xy, T* acc_xy);
+
+}  // namespace nbody
+
+// A handle made by nbody_create_multi fronts several devices.  Calls that only read or that act on "the current rows"
+// are served by the first device once the replicas agree (multi_primary brings them up to date); `mutates` marks the
+// calls after which the other replicas must be refreshed from it (multi_replicate).
+#define NB_VIA_PRIMARY(c, mutates, expr)                    \
+  do {                                                      \
+    if ((c) && (c)->multi) {                                \
+      nbody_ctx* front__ = (c);                             \
+      nbody_ctx* p = nullptr;                               \
+      int rc__ = nbody::multi_primary(front__, &p);         \
+      if (rc__) return rc__;                                \
+      rc__ = (expr);                                        \
+      if (rc__) { front__->err = p->err; return rc__; }     \
+      return (mutates) ? nbody::multi_replicate(front__) : NBODY_OK; \
+    }                                                       \
+  } while (0)

@@ -501,7 +501,7 @@ def test_mass_classes_follow_the_rows_through_a_tree_build(nb, orc, lab_ctx, mon
 
 
 def test_captured_direct_graph_is_rebuilt_when_a_tree_step_permutes_the_rows(nb, orc, ctx):
-    """ADVICE r03 (capi.hip DirectGraph): four direct steps at 65 536 <= n <= 131 072 capture the step as a hipGraph with the mass
+    """ADVICE r03 (direct_driver.hip, DirectGraph): four direct steps at 65 536 <= n <= 131 072 capture the step as a hipGraph with the mass
     classes' device arrays baked in.  TWO tree steps permute the rows and put every buffer of the graph's key back where it was
     while ensure_mass_classes frees and rebuilds rank / pad_slots / tile_mass: the next four direct steps must not replay the old
     capture.  Checked against the same call sequence on a fresh context that never captured before the build (eager first), and

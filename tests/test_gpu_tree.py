@@ -590,7 +590,7 @@ def test_one_pass_walk_notices_a_history_whose_scan_wraps(nb, lab, monkeypatch, 
 @pytest.mark.parametrize("order_name", ["as_written", "consistent"])
 def test_step_ahead_equals_the_plain_sequence(nb, orc, monkeypatch, capfd, order_name):
     """From the second step of a call on, a BVH step is enqueued whole — build, device-side verdict, gather, walk reading
-    the node count from device memory, gated integration — with one host wait at its end (capi.hip, bvh_step_ahead).
+    the node count from device memory, gated integration — with one host wait at its end (tree_driver.hip, bvh_step_ahead).
     Same kernels on the same data: bit-identical to the phase-by-phase sequence and to the oracle."""
     C = nb._capi
     order = C.ORDER_AS_WRITTEN if order_name == "as_written" else C.ORDER_CONSISTENT

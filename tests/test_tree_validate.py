@@ -1,4 +1,4 @@
-"""The shape check a caller's linearised tree passes before nbody_walk_tree_* lets it near the device (capi.hip,
+"""The shape check a caller's linearised tree passes before nbody_walk_tree_* lets it near the device (caller_tree.hip,
 tree_shape_ok): host only.  Valid: what the product's host builders and the oracle (bvh_tree.rs:56-158, quad_tree.rs:153-270)
 produce.  Invalid: every way a foreign tree could send a stackless skip-link walk backwards, out of its arrays or into a
 range that is not its children's."""
