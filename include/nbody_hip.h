@@ -50,8 +50,9 @@ extern "C" {
 
 /* 2: nbody_create_multi*, nbody_multi_info, nbody_direct_prep/run_dev, nbody_update_tree_async_f32, nbody_wait,
  *    nbody_get_stream, nbody_delta_decoder_set_max_bodies, nbody_selftest_*_f64 (round 2), nbody_multi_comm_count (round 3);
+ * 3: nbody_update_direct_f64, nbody_accel_direct_f64 (the direct O(N^2) step on an f64 context);
  *    a binding compares nbody_abi_version() with the value it was written against before it binds anything else. */
-#define NBODY_ABI_VERSION 2
+#define NBODY_ABI_VERSION 3
 
 typedef struct nbody_ctx nbody_ctx;
 typedef struct nbody_timer nbody_timer;
@@ -157,6 +158,17 @@ int64_t nbody_num_particles(const nbody_ctx* ctx);
 /* Direct O(N^2): a_i = sum_j calculate_gravity(p_i, p_j, w_j) for j ascending, then main.rs:419-423.
  * (No reference function: this is what bvh_sum_gravity degenerates to at theta = 0) */
 int nbody_update_direct_f32(nbody_ctx* ctx, float delta, int n_steps, nbody_counting* counter);
+/* The same step on an f64 context (nbody_upload_f64), with T = double throughout; mass is `weight as f64`, the clamp is
+ * params.clamp widened to double.  AUTO and EXACT: one ascending-j chain of IEEE additions in double per target, every pair
+ * as main.rs:236-252 writes it (two correctly rounded divisions, no contraction, the is_normal skip), integration as
+ * main.rs:419-423 without contraction: bit-identical to the CPU restatement.  FAST (opt-in): one v_rcp_f64 + one Newton
+ * step per pair, fused multiply-adds, a 2^-700-biased denominator, sources split over waves; |a - a_ref|_1 <= 1e-12 *
+ * sum_j |term_ij|_1 per body.  A step whose positions are not all finite, below 2^100 in magnitude and zero or at least
+ * 2^-300, or whose clamp is not > 0, runs EXACT instead (decided on the device, per step).  n_steps = 0 or no bodies: a no-op.
+ * Not provided for f64: multi-device contexts (NBODY_ERR_INVALID: multi-device direct steps are f32 only), the sharded
+ * *_dev entry points, mass classes, the near/far split, and hipGraph replay of small steps.  nbody_update_direct_f32 on
+ * an f64 context still fails. */
+int nbody_update_direct_f64(nbody_ctx* ctx, double delta, int n_steps, nbody_counting* counter);
 /* Barnes-Hut: the linearised tree is the reference's tree, node for node (built on the device; by the host builder
  * for what the device builders decline — NaN positions, trees deeper than they follow — see nbody_last_build_on_device), and the device walks it. */
 int nbody_update_tree_f32(nbody_ctx* ctx, int tree_kind, float delta, int n_steps, nbody_counting* counter);
@@ -186,6 +198,7 @@ int nbody_import_rows_dev(nbody_ctx* ctx, int64_t n_rows, const void* rows_u32, 
 /* ---- parity hooks: force only, state untouched ----------------------------------------------------- */
 /* acc_xy[2*n]: accelerations in current row order. */
 int nbody_accel_direct_f32(nbody_ctx* ctx, float* acc_xy);
+int nbody_accel_direct_f64(nbody_ctx* ctx, double* acc_xy);  /* arithmetic as nbody_update_direct_f64 */
 /* Builds the tree over the current positions (rows are permuted for the BVH, as a step would) and walks
  * it for `n_targets` arbitrary target positions (NULL: the particles themselves, post-build order). */
 int nbody_accel_tree_f32(nbody_ctx* ctx, int tree_kind, int64_t n_targets, const float* target_xy, float* acc_xy);

@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libnbody_hip.so")
 LAB_LIB_PATH = os.path.join(_HERE, "lib", "libnbody_hip_lab.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "nbody_hip.h")
 
-ABI_VERSION = 2   # NBODY_ABI_VERSION of include/nbody_hip.h (tests/test_capi_host.py checks the two agree)
+ABI_VERSION = 3   # NBODY_ABI_VERSION of include/nbody_hip.h (tests/test_capi_host.py checks the two agree)
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_DEGENERATE, ERR_NOMEM = 0, -1, -2, -3, -4, -5
 ARITH_AUTO, ARITH_FAST, ARITH_EXACT = 0, 1, 2
 ORDER_AS_WRITTEN, ORDER_CONSISTENT = 0, 1
@@ -70,6 +70,7 @@ _SIGS = {
     "nbody_download_f64": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "nbody_num_particles": (_i64, [_vp]),
     "nbody_update_direct_f32": (C.c_int, [_vp, _f32, _i32, C.POINTER(Counting)]),
+    "nbody_update_direct_f64": (C.c_int, [_vp, _f64, _i32, C.POINTER(Counting)]),
     "nbody_update_tree_f32": (C.c_int, [_vp, _i32, _f32, _i32, C.POINTER(Counting)]),
     "nbody_update_tree_f64": (C.c_int, [_vp, _i32, _f64, _i32, C.POINTER(Counting)]),
     "nbody_update_tree_async_f32": (C.c_int, [_vp, _i32, _f32, _i32]),
@@ -79,6 +80,7 @@ _SIGS = {
     "nbody_export_slice_dev": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
     "nbody_import_rows_dev": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
     "nbody_accel_direct_f32": (C.c_int, [_vp, _vp]),
+    "nbody_accel_direct_f64": (C.c_int, [_vp, _vp]),
     "nbody_accel_tree_f32": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_accel_tree_f64": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_tree_info": (C.c_int, [_vp, C.POINTER(TreeView)]),
@@ -493,8 +495,8 @@ class Context:
 
     # ---- steps
     def update_direct(self, delta, n_steps=1, counter: Counting | None = None):
-        check(self.h, self.lib.nbody_update_direct_f32(self.h, float(delta), int(n_steps),
-                                                       C.byref(counter) if counter is not None else None))
+        f = self.lib.nbody_update_direct_f64 if self.dtype == np.float64 else self.lib.nbody_update_direct_f32
+        check(self.h, f(self.h, float(delta), int(n_steps), C.byref(counter) if counter is not None else None))
 
     def update_tree(self, kind, delta, n_steps=1, counter: Counting | None = None):
         f = self.lib.nbody_update_tree_f64 if self.dtype == np.float64 else self.lib.nbody_update_tree_f32
@@ -520,8 +522,12 @@ class Context:
         check(self.h, self.lib.nbody_import_rows_dev(self.h, int(n_rows), _vp(rows_ptr), _vp(pos_ptr), _vp(vel_ptr)))
 
     def accel_direct(self):
-        acc = np.zeros((self.n, 2), np.float32)
-        check(self.h, self.lib.nbody_accel_direct_f32(self.h, _ptr(acc)))
+        if self.dtype == np.float64:
+            acc = np.zeros((self.n, 2), np.float64)
+            check(self.h, self.lib.nbody_accel_direct_f64(self.h, _ptr(acc)))
+        else:
+            acc = np.zeros((self.n, 2), np.float32)
+            check(self.h, self.lib.nbody_accel_direct_f32(self.h, _ptr(acc)))
         return acc
 
     def accel_tree(self, kind, targets=None):
@@ -649,6 +655,11 @@ class MultiContext(Context):
             raise _err(None, rc)
         self.dtype = None
         self.n = 0
+
+    def update_direct(self, delta, n_steps=1, counter: Counting | None = None):
+        """Multi-device direct steps are f32 only: after an f64 upload this fails, as it always has."""
+        check(self.h, self.lib.nbody_update_direct_f32(self.h, float(delta), int(n_steps),
+                                                       C.byref(counter) if counter is not None else None))
 
 
 def mass_hint(weight) -> float:

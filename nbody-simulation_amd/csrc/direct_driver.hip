@@ -1,9 +1,11 @@
 // libnbody_hip — the direct-sum driver: the kernel configuration and workspace layout of a step, the mass classes, the
 // preparation / run split multi.hip shards over devices, the hipGraph replay of step pairs, and the direct entry points
-// of the C ABI (nbody_update_direct_f32, nbody_accel_direct_f32, nbody_direct_*_dev).  Kernels: direct_kernels.hip, nearfar.hip.
+// of the C ABI (nbody_update_direct_f32, nbody_accel_direct_f32, nbody_direct_*_dev), and the f64 direct entry points
+// (nbody_update_direct_f64, nbody_accel_direct_f64).  Kernels: direct_kernels.hip, nearfar.hip, direct64.hip.
 #include <algorithm>
 #include <cstdio>
 
+#include "direct64.h"
 #include "direct_kernels.h"
 #include "driver.h"
 
@@ -481,3 +483,69 @@ NB_API int nbody_direct_run_dev(void* stream, int64_t n_sources, const void* pos
                     acc_out, delta, clamp, arith, n_targets_total, n_targets_max, workspace, workspace_bytes, timer);
 }
 
+
+// ---- f64: one device, EXACT unless FAST is asked for (AUTO is EXACT, as for the f64 tree walks); direct64.h
+namespace {
+int direct64_step(nbody_ctx* c, double delta, bool integrate) {
+  State<double>& s = c->sd;
+  auto& st = s.set[s.cur];
+  Direct64Args a;
+  a.pos = st.pos;
+  a.mass = st.mass;
+  a.n = s.n;
+  if (integrate) {
+    a.vel = st.vel;
+    a.pos_out = s.pos_next;
+  } else {
+    a.acc_out = s.acc;
+  }
+  a.delta = delta;
+  a.clamp = (double)c->params.clamp;  // the f32 parameter widened, as the oracle's np.float32(clamp) -> T
+  const bool fast = c->params.arith == NBODY_ARITH_FAST && a.clamp > 0.0;  // (a NaN clamp fails the test too)
+  TimerScope ts(c->timer, c->stream);
+  HIPCHK(c, launch_direct64(c->stream, a, fast, c->workspace, c->workspace_bytes));
+  return NBODY_OK;
+}
+}  // namespace
+
+NB_API int nbody_update_direct_f64(nbody_ctx* c, double delta, int n_steps, nbody_counting* counter) {
+  if (!c) return NBODY_ERR_INVALID;
+  if (c->multi) return fail(c, NBODY_ERR_INVALID, "update_direct_f64: multi-device direct steps are f32 only");
+  if (!c->has_f64) return fail(c, NBODY_ERR_INVALID, "update_direct_f64: no f64 particles uploaded");
+  if (n_steps < 0) return fail(c, NBODY_ERR_INVALID, "update_direct_f64: n_steps < 0");
+  HIPCHK(c, hipSetDevice(c->device));
+  State<double>& s = c->sd;
+  int rc = ctx_ensure_workspace(c, direct64_ws_bytes(s.n));
+  if (rc) return rc;
+  const double t_begin = now_s();
+  for (int step = 0; step < n_steps && s.n > 0; ++step) {
+    rc = direct64_step(c, delta, true);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::swap(s.set[s.cur].pos, s.pos_next);
+  }
+  // force and integrate are one fused kernel: the whole call is booked under sum_gravity
+  const double dt = now_s() - t_begin;
+  c->counting.sum_gravity += dt;
+  if (counter) counter->sum_gravity += dt;
+  s.tree_valid = false;
+  c->steps_done += (uint64_t)n_steps;
+  return NBODY_OK;
+}
+
+NB_API int nbody_accel_direct_f64(nbody_ctx* c, double* acc_xy) {
+  if (!c) return NBODY_ERR_INVALID;
+  if (c->multi) return fail(c, NBODY_ERR_INVALID, "accel_direct_f64: multi-device direct steps are f32 only");
+  if (!c->has_f64) return fail(c, NBODY_ERR_INVALID, "accel_direct_f64: no f64 particles uploaded");
+  if (!acc_xy) return fail(c, NBODY_ERR_INVALID, "accel_direct_f64: acc_xy is NULL");
+  HIPCHK(c, hipSetDevice(c->device));
+  State<double>& s = c->sd;
+  int rc = ctx_ensure_workspace(c, direct64_ws_bytes(s.n));
+  if (rc) return rc;
+  if (s.n == 0) return NBODY_OK;
+  rc = direct64_step(c, 0.0, false);
+  if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(acc_xy, s.acc, (size_t)s.n * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return NBODY_OK;
+}

@@ -39,8 +39,8 @@ class World:
                             quad_root_x=float(quad_root[0]), quad_root_y=float(quad_root[1]),
                             quad_root_h=float(quad_root[2]))
         self.ctx.upload(position, velocity, weight)
-        if method == "direct" and self.ctx.dtype != np.float32:
-            raise ValueError("the direct path is f32 (the reference's precision)")
+        if method == "direct" and devices is not None and self.ctx.dtype != np.float32:
+            raise ValueError("multi-device direct steps are f32 only")
 
     def update(self, delta: float, counter: Counting | None = None, n_steps: int = 1):
         """World::update (main.rs:388-425): build, force, integrate; accumulates phase seconds into `counter`."""
