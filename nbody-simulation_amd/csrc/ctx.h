@@ -115,7 +115,8 @@ inline std::string direct_env_signature() {
   sig += nf ? nf : "-";
   sig += ';';
   for (const char* k : {"NBODY_DIRECT_ASM", "NBODY_DIRECT_TPT", "NBODY_DIRECT_GSPLIT", "NBODY_DIRECT_NO_UNIFORM", "NBODY_DIRECT_NO_CLASSES",
-                        "NBODY_DIRECT_NO_SPARSE"}) {  // (laboratory build only)
+                        "NBODY_DIRECT_NO_SPARSE",
+                        "NBODY_DIRECT_MUTUAL_MIN_N"}) {  // (laboratory build only)
     const char* v = lab_str(k);
     sig += v ? v : "-";
     sig += ';';

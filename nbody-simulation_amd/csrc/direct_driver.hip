@@ -17,7 +17,7 @@ namespace {
 // How the direct kernel covers (n_tgt x n_src): enough waves to fill 256 CUs x 4 SIMDs x 8 waves.
 DirectConfig choose_direct_config(int64_t n_src, int64_t n_tgt, bool uniform = true) {
   DirectConfig c;
-  c.use_asm = lab_int("NBODY_DIRECT_ASM", 3);
+  c.use_asm = lab_int("NBODY_DIRECT_ASM", 4);
   // near/far split: 0.05 ms (65 536 bodies) to 0.16 ms (1 M) of preparation per step against 10 % of the pair work: it pays
   // from 65 536 x 65 536 pairs on (profiles/r03_nearfar_hash_grid.txt; the sort-based split of rounds 1-2 broke even at
   // twice that).  NBODY_DIRECT_NEARFAR: 0 never, 1 by size (default), 2 always.
@@ -68,8 +68,20 @@ size_t direct_partial_bytes(int64_t n_src, int64_t n_tgt) {
   if (g_l2 <= 16 && (size_t)(g_l2 * n_tgt) * sizeof(float2) > partial) partial = (size_t)(g_l2 * n_tgt) * sizeof(float2);
   return (partial + 255) & ~(size_t)255;
 }
+// The mutual main pass (direct_mutual.hip) can engage when one block of targets covers every source, from its crossover on
+// (measured: profiles/r06_mutual_crossover.txt) up to 2^22 bodies (beyond, the per-strip reduction's full passes over the running sums
+// would pass 0.4 % of the step; untested).  Its strip buffers then follow the near/far scratch in the workspace.
+constexpr int64_t kMutualMinN = 393216;
+constexpr int64_t kMutualMaxN = 4194304;
+bool mutual_sizes(int64_t n_src, int64_t n_tgt) {
+  return n_tgt == n_src && n_src >= lab_int("NBODY_DIRECT_MUTUAL_MIN_N", (int)kMutualMinN) && n_src <= kMutualMaxN;
+}
+size_t mutual_offset(int64_t n_src, int64_t n_tgt) {
+  return (kFlagBytes + direct_partial_bytes(n_src, n_tgt) + nearfar_layout(n_src).total + 255) & ~(size_t)255;
+}
 size_t direct_ws_bytes(int64_t n_src, int64_t n_tgt) {
-  return kFlagBytes + direct_partial_bytes(n_src, n_tgt) + nearfar_layout(n_src).total;
+  const size_t base = kFlagBytes + direct_partial_bytes(n_src, n_tgt) + nearfar_layout(n_src).total;
+  return mutual_sizes(n_src, n_tgt) ? mutual_offset(n_src, n_tgt) + mutual_area_bytes(n_src) : base;
 }
 
 // Mass classes of the context's f32 rows in their current order (ctx.h, State::MassClasses): built on the host from the
@@ -171,6 +183,7 @@ struct DirectPlan {
   bool nearfar = false;
   bool couples = false;  // the far copy in couples {xA, xB, yA, yB}, padded to whole 16-source iterations (the packed kernels)
   bool stream_m = false; // free per-body masses through the streamed main pass: the far copy carries 1 / mass in slot order
+  bool mutual = false;   // the mutual main pass (direct_mutual.hip): each far pair once, equal-mass rate, one block of all targets
   int use_hazard = 0;
   size_t partial_bytes = 0;
 };
@@ -195,7 +208,10 @@ int direct_plan(nbody_ctx* c, int64_t n_src, const void* mass_all, float uniform
   if (uniform_mass < 0.f && p.nearfar && lab_int("NBODY_DIRECT_NO_UNIFORM", 0) == 0 && lab_int("NBODY_DIRECT_NO_SPARSE", 0) == 0)
     p.sparse_base = -uniform_mass;
   if (!p.uni && p.sparse_base == 0.f && p.nearfar) p.classes = classes_for(c, n_src, mass_all);
-  p.stream_m = !p.uni && p.sparse_base == 0.f && !p.classes && p.couples && lab_int("NBODY_DIRECT_ASM", 3) >= 3;
+  p.stream_m = !p.uni && p.sparse_base == 0.f && !p.classes && p.couples && lab_int("NBODY_DIRECT_ASM", 4) >= 3;
+  // lab NBODY_DIRECT_ASM: 4 (default) = mutual where it applies, else as 3
+  p.mutual = arith != NBODY_ARITH_EXACT && p.couples && (p.uni || p.sparse_base > 0.f) && !p.classes && n_tgt_max == n_tgt_total &&
+             mutual_sizes(n_src, n_tgt_total) && lab_int("NBODY_DIRECT_ASM", 4) >= 4;
   p.use_hazard = arith == NBODY_ARITH_AUTO;
   p.partial_bytes = direct_partial_bytes(n_src, n_tgt_max);
   *out = p;
@@ -302,7 +318,15 @@ int ctx_direct_run(nbody_ctx* c, hipStream_t stream, int64_t n_src, const void* 
         a0.uniform_mass = 1.0f;
         a0.tile_mass = p.classes->tile_mass;
       }
-      HIPCHK(c, launch_direct_fast(stream, a0, cfg, true));
+      if (p.mutual) {  // the mutual pass and its partial reduction, both inside the timer: one far sum per target in a.partial
+        char* nf_scratch = (char*)ws + kFlagBytes + p.partial_bytes;
+        NearFarLayout L = nearfar_layout(n_src);
+        char* area = (char*)ws + mutual_offset(n_src, n_tgt_max);
+        HIPCHK(c, launch_direct_mutual(stream, a0, mutual_area(area, n_src, (const uint32_t*)(nf_scratch + L.is_near),
+                                                                (const uint32_t*)(nf_scratch + L.scan))));
+      } else {
+        HIPCHK(c, launch_direct_fast(stream, a0, cfg, true));
+      }
     }
     DirectArgs a1 = a;  // state 1: one clamped pass over every source
     a1.to_partial = cfg.gsplit > 1;
@@ -313,7 +337,7 @@ int ctx_direct_run(nbody_ctx* c, hipStream_t stream, int64_t n_src, const void* 
     DirectArgs a0 = a;
     a0.near_list = near_list;
     a0.run_state = 0;
-    HIPCHK(c, launch_direct_finish(stream, a0, cfg.gsplit, true));
+    HIPCHK(c, launch_direct_finish(stream, a0, p.mutual ? 1 : cfg.gsplit, true));
   }
   if (cfg.gsplit > 1) {
     DirectArgs a1 = a;

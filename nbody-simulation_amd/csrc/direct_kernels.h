@@ -37,7 +37,7 @@ struct DirectArgs {
 struct DirectConfig {
   int tpt = 1;     // targets per thread: 1 or 2
   int gsplit = 1;  // source split over blockIdx.y
-  int use_asm = 3;      // tpt 1: 0 the compiler's schedule, 1 the hand-ordered 8-pair block, 2 packed couples (two pairs per packed op) through
+  int use_asm = 4;      // tpt 1 (4: the mutual pass where direct_plan allows it, else 3): 0 the compiler's schedule, 1 the hand-ordered 8-pair block, 2 packed couples (two pairs per packed op) through
                         // LDS, 3 packed couples with the far sources streamed through SGPRs (equal masses, no clamp; otherwise as 2)
   bool nearfar = true;  // per-step near/far split of the sources
 };
@@ -63,6 +63,26 @@ hipError_t launch_nearfar(hipStream_t s, const float2* pos, const float* mass, f
 // per-body-mass main pass reads it (direct_stream_m)
 hipError_t launch_decide_simple(hipStream_t s, int use_hazard, int* flags);
 
+// The mutual main pass (direct_mutual.hip): equal masses, one block of targets covering every source, couples.  The items (slice
+// pairs) run in strips of kMutualStripItems; a strip's partial sums — one per target per item (tpart) and one per source per
+// off-diagonal item (spart) — are added to every body's running sum (a.partial) before the next strip reuses them.  near_acc: the
+// far sources of each near body.  is_near / near_scan: nearfar.hip's per-body flags and their exclusive scan.
+constexpr int kMutualSlice = 8192;          // targets (and sources) per slice: 8 waves x 64 lanes x 16
+constexpr int kMutualStripItems = 256;      // items per strip: one round of work-groups on the 256 CUs of an MI355X
+struct MutualArea {
+  int n_slices;
+  float2* tpart;
+  float2* spart;
+  float2* near_acc;
+  const uint32_t* is_near;
+  const uint32_t* near_scan;
+};
+int mutual_slices(int64_t n_slots);
+size_t mutual_area_bytes(int64_t n_src);  // the strip buffers + near_acc: part of the direct workspace when the pass can engage
+MutualArea mutual_area(void* base, int64_t n_src, const uint32_t* is_near, const uint32_t* near_scan);
+// a.src_pos: the far copy in couples (a.n_src slots), a.pos_all / a.near_list: the near bodies; a.partial receives every
+// target's far acceleration (one split) for launch_direct_finish
+hipError_t launch_direct_mutual(hipStream_t s, const DirectArgs& a, const MutualArea& m);
 hipError_t launch_direct_fast(hipStream_t s, const DirectArgs& a, const DirectConfig& c, bool noclamp);
 hipError_t launch_direct_finish(hipStream_t s, const DirectArgs& a, int n_gsplit, bool add_near);
 hipError_t launch_direct_exact(hipStream_t s, const DirectArgs& a);

@@ -754,7 +754,7 @@ hipError_t launch_direct_fast(hipStream_t s, const DirectArgs& a, const DirectCo
   const int tpt = c.tpt == 2 ? 2 : 1;
   const int use_asm = tpt == 1 ? c.use_asm : 0;
   if (a.src_couples && (use_asm < 2 || (a.n_src % kFarPad) != 0)) return hipErrorInvalidValue;  // only the packed kernels read couples
-  if (use_asm == 3 && noclamp && a.src_couples && (uni || a.src_minv)) {
+  if (use_asm >= 3 && noclamp && a.src_couples && (uni || a.src_minv)) {
     const dim3 grid((unsigned)((a.n_tgt + 63) / 64), (unsigned)c.gsplit);
     if (uni) hipLaunchKernelGGL(direct_stream, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(direct_stream_m, grid, dim3(256), 0, s, a);
