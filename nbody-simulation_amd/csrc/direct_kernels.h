@@ -63,17 +63,20 @@ hipError_t launch_nearfar(hipStream_t s, const float2* pos, const float* mass, f
 // per-body-mass main pass reads it (direct_stream_m)
 hipError_t launch_decide_simple(hipStream_t s, int use_hazard, int* flags);
 
-// The mutual main pass (direct_mutual.hip): equal masses, one block of targets covering every source, couples.  The items (slice
-// pairs) run in strips of kMutualStripItems; a strip's partial sums — one per target per item (tpart) and one per source per
-// off-diagonal item (spart) — are added to every body's running sum (a.partial) before the next strip reuses them.  near_acc: the
-// far sources of each near body.  is_near / near_scan: nearfar.hip's per-body flags and their exclusive scan.
+// The mutual main pass (direct_mutual.hip): equal masses, one block of targets covering every source, couples.  The units (slice
+// pairs, and the diagonal items two by two: mutual_schedule.h) run in strips of whole rounds, at most kMutualStripItems units; a
+// strip's partial sums — one per target per unit (tpart) and one per source per off-diagonal item (spart; a diagonal unit's second
+// slice) — are added to every body's running sum (a.partial) before the next strip reuses them.  near_part: the far sources of
+// each near body, in kMutualNearSplit source ranges.  is_near / near_scan: nearfar.hip's per-body flags and their exclusive scan.
 constexpr int kMutualSlice = 8192;          // targets (and sources) per slice: 8 waves x 64 lanes x 16
-constexpr int kMutualStripItems = 256;      // items per strip: one round of work-groups on the 256 CUs of an MI355X
+constexpr int kMutualStripItems = 256;      // units per strip at most (the strip area): one round of work-groups on 256 CUs
+constexpr int kMutualNearSplit = 32;        // source ranges per near body (direct_mutual_near's blockIdx.x)
+constexpr int kMutualNearRows = 64;         // near bodies in flight (blockIdx.y)
 struct MutualArea {
   int n_slices;
   float2* tpart;
   float2* spart;
-  float2* near_acc;
+  float2* near_part;
   const uint32_t* is_near;
   const uint32_t* near_scan;
 };
