@@ -13,15 +13,17 @@ body + semi-implicit Euler (reference: World::update, src/main.rs:388-425, with 
 force phase).
 
 Output (rank 0, stdout): the HEADLINE is the LAST line, one compact JSON object (< 2 KB: metric, value, unit, n_gpus, steps,
-warmup, ms_per_step, dtype, config, `roofline`, `cpu_baseline`, and a one-number-per-leg `legs` digest).  At N = 1 it is
-preceded by one compact JSON line (< 1 KB) per leg — the other single-GPU configurations: the reference's live BVH step, the
-same on the headline's bodies, config 2 (65 536 direct), mass classes, free per-body masses, the reference's own scene
-(direct), config 4 (4 194 304 bodies, quad tree, theta 0.5, f64; the reference's arithmetic and the opt-in FAST one).  The
-explanatory notes every record used to repeat live once in profiles/README.md ("Reading a bench line").  `--full-out PATH`
-also writes the unabridged records (headline + legs) to PATH; `--leg NAME` runs one leg alone and prints its unabridged
-record (what the rocprofv3 passes under profiles/ are taken on).  `--dump-outputs DIR` writes the headline path's positions and
-velocities after its last timed step to DIR/*.npy (the inputs are seeded: two builds run with the same arguments compare array
-for array).
+warmup, ms_per_step, dtype, config and `roofline`, the latter from HIP events on the timed steps' own kernels).  A plain run
+does only that: set up, warm up, time the steps, dump if asked, print the line.  `--full` adds what takes runs of its own:
+a `cpu_baseline` (the CPU oracle on a sample of the same workload; single GPU) and, at one GPU and N = 1 048 576, one compact
+JSON line (< 1 KB) per leg before the headline plus a one-number-per-leg `legs` digest in it — the other single-GPU
+configurations: the reference's live BVH step, the same on the headline's bodies, config 2 (65 536 direct), mass classes,
+free per-body masses, the reference's own scene (direct), config 4 (4 194 304 bodies, quad tree, theta 0.5, f64; the
+reference's arithmetic and the opt-in FAST one).  The explanatory notes every record used to repeat live once in
+profiles/README.md ("Reading a bench line").  `--full-out PATH` also writes the unabridged records (headline + legs) to PATH;
+`--leg NAME` runs one leg alone and prints its unabridged record (what the rocprofv3 passes under profiles/ are taken on).
+`--dump-outputs DIR` writes the headline path's positions and velocities after its last timed step to DIR/*.npy (the inputs
+are seeded: two builds run with the same arguments compare array for array).
 """
 import argparse
 import json
@@ -540,7 +542,7 @@ def run_in_library(args):
                           "one worker thread per device)", "n_ranks": n_ranks,
                           "exchange": ("RCCL in-place ncclAllGather of float2 positions per chunk (xGMI)" if xch == C.EXCHANGE_RCCL
                                        else "hipMemcpyPeerAsync of every block to every peer")})
-    if g == 1 and not args.no_cpu_baseline:
+    if g == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(pos, w, args.cpu_sample_targets)
     emit_headline(out, [], args.full_out)
 
@@ -551,8 +553,10 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--bodies", dest="n", type=int, default=N_BODIES, help="total bodies (default: the BASELINE config)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-legs", action="store_true", help="skip the non-headline single-GPU configurations")
+    ap.add_argument("--full", action="store_true", help="after the headline's steps also time the CPU baseline and, at one GPU "
+                                                        "and the default N, the other single-GPU configurations (legs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full or --leg: skip the CPU baseline")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the legs")
     ap.add_argument("--leg", default=None, help=f"run ONE leg alone and print its unabridged record (for profiling): {', '.join(LEGS)}")
     ap.add_argument("--full-out", default=None, help="also write the unabridged records (headline + legs) to this file")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse "
@@ -648,10 +652,10 @@ def main():
                               "n_ranks": dist.get_world_size() if world > 1 else 1,
                               "exchange": "none" if world == 1 else f"{args.backend} in-place all-gather of float2 positions per chunk"
                                           + (" (RCCL over xGMI)" if args.backend == "nccl" else " (rehearsal)")})
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(pos, w, args.cpu_sample_targets)
         legs = []
-        if world == 1 and not args.no_legs and n == N_BODIES:
+        if world == 1 and args.full and not args.no_legs and n == N_BODIES:
             del stepper
             torch.cuda.empty_cache()
             for name in LEGS:

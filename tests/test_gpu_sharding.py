@@ -164,6 +164,18 @@ def test_bench_without_a_launcher_runs_the_library_multi_gpu_path():
     assert "hipMemcpyPeerAsync" in lib2["config"]["exchange"]
 
 
+def test_plain_bench_is_the_headline_alone_and_full_adds_the_cpu_baseline():
+    """A plain `bench.py` run does what its headline needs and nothing more: no CPU baseline, no legs.  `--full` adds the CPU
+    baseline (and, at the default N only, the legs), on the torch route and on the in-library one."""
+    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--bodies", "65536"]
+    for route in ([], ["--in-library"]):
+        plain = _bench(common + route)
+        assert "cpu_baseline" not in plain and "legs" not in plain
+        assert plain["steps"] == 2 and plain["warmup"] == 1 and plain["value"] > 0 and plain["roofline"]["frac"] > 0
+        full = _bench(common + route + ["--full", "--cpu-sample-targets", "256"])
+        assert full["cpu_baseline"]["value"] > 0 and full["cpu_baseline"]["kind"] == "port" and "legs" not in full
+
+
 def _tree_worker(rank, world, port, kind, dtype_name, order, steps, ret):
     sys.path.insert(0, ROOT)
     os.environ["MASTER_ADDR"] = "127.0.0.1"
