@@ -51,6 +51,8 @@ extern "C" {
 /* 2: nbody_create_multi*, nbody_multi_info, nbody_direct_prep/run_dev, nbody_update_tree_async_f32, nbody_wait,
  *    nbody_get_stream, nbody_delta_decoder_set_max_bodies, nbody_selftest_*_f64 (round 2), nbody_multi_comm_count (round 3);
  * 3: nbody_update_direct_f64, nbody_accel_direct_f64 (the direct O(N^2) step on an f64 context);
+ *    nbody_accel_direct_at_f32 / _f64 (the direct sum at arbitrary points) were added under 3: new symbols only, nothing
+ *    that existed changed;
  *    a binding compares nbody_abi_version() with the value it was written against before it binds anything else. */
 #define NBODY_ABI_VERSION 3
 
@@ -203,6 +205,20 @@ int nbody_accel_direct_f64(nbody_ctx* ctx, double* acc_xy);  /* arithmetic as nb
  * it for `n_targets` arbitrary target positions (NULL: the particles themselves, post-build order). */
 int nbody_accel_tree_f32(nbody_ctx* ctx, int tree_kind, int64_t n_targets, const float* target_xy, float* acc_xy);
 int nbody_accel_tree_f64(nbody_ctx* ctx, int tree_kind, int64_t n_targets, const double* target_xy, double* acc_xy);
+/* Direct-sum accelerations of the current bodies at n_targets arbitrary points (x0,y0,x1,y1,...); state untouched.
+ * The sources are the bodies in their current row order, each pair calculate_gravity (main.rs:234-253) with the params'
+ * clamp; a target is a point without mass or self term (one that sits on a body skips that pair by the reference's rule).
+ * Arithmetic as the direct step of the context's precision: EXACT is bit-identical to one ascending-row chain per target;
+ * f32 FAST is within the step's tolerance, and AUTO is EXACT for every target when the step would be (a body outside FAST's
+ * domain, a clamp below 2^-19), else FAST but for a target outside that domain, which gets its EXACT value; f64 is EXACT
+ * unless FAST is asked for, FAST then gated like the f64 step, with the same per-target exception.  Whatever the route, a
+ * target's bits depend only on its own position (the bodies, params and build fixed): not on the other targets, their
+ * number or order, nor on the number of devices of a multi-device context, which splits the targets into one contiguous
+ * block per device.  Targets go through in bounded batches.  Zero bodies: every acceleration is +0.
+ * NBODY_ERR_INVALID: ctx NULL, n_targets < 0, a NULL array with n_targets > 0, no particles, the other precision.
+ * n_targets == 0 does nothing. */
+int nbody_accel_direct_at_f32(nbody_ctx* ctx, int64_t n_targets, const float* target_xy, float* acc_xy);
+int nbody_accel_direct_at_f64(nbody_ctx* ctx, int64_t n_targets, const double* target_xy, double* acc_xy);
 
 /* Linearised tree of the last build (pre-order; node i's first child is i+1; `skip` is the pre-order index
  * following the subtree).  Any pointer may be NULL; call with all NULL to get the node count. */

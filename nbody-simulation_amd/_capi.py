@@ -81,6 +81,8 @@ _SIGS = {
     "nbody_import_rows_dev": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
     "nbody_accel_direct_f32": (C.c_int, [_vp, _vp]),
     "nbody_accel_direct_f64": (C.c_int, [_vp, _vp]),
+    "nbody_accel_direct_at_f32": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "nbody_accel_direct_at_f64": (C.c_int, [_vp, _i64, _vp, _vp]),
     "nbody_accel_tree_f32": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_accel_tree_f64": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_tree_info": (C.c_int, [_vp, C.POINTER(TreeView)]),
@@ -521,7 +523,16 @@ class Context:
     def import_rows_dev(self, n_rows, rows_ptr, pos_ptr, vel_ptr):
         check(self.h, self.lib.nbody_import_rows_dev(self.h, int(n_rows), _vp(rows_ptr), _vp(pos_ptr), _vp(vel_ptr)))
 
-    def accel_direct(self):
+    def accel_direct(self, targets=None):
+        """The direct sum at the bodies, in row order — or, with an (m, 2) array `targets` (cast to the context's dtype), at
+        those points (nbody_accel_direct_at_*: no mass, no self term; a target's result depends on its position alone)."""
+        if targets is not None:
+            dt = np.float64 if self.dtype == np.float64 else np.float32
+            f = self.lib.nbody_accel_direct_at_f64 if dt == np.float64 else self.lib.nbody_accel_direct_at_f32
+            tg = np.ascontiguousarray(targets, dtype=dt).reshape(-1, 2)
+            acc = np.zeros_like(tg)
+            check(self.h, f(self.h, tg.shape[0], _ptr(tg), _ptr(acc)))
+            return acc
         if self.dtype == np.float64:
             acc = np.zeros((self.n, 2), np.float64)
             check(self.h, self.lib.nbody_accel_direct_f64(self.h, _ptr(acc)))

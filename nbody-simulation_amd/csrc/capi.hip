@@ -235,6 +235,7 @@ void nbody::ctx_destroy_single(nbody_ctx* c) {
   free_state(c->sf);
   free_state(c->sd);
   free_dev(c->workspace);
+  free_dev(c->probe_ws);
   free_dev(c->stats_dev);
   free_dev(c->frame_work);
   free_dev(c->frame_rgba);

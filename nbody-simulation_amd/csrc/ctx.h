@@ -196,6 +196,9 @@ struct nbody_ctx {
   int* spec_host_dev = nullptr;  // spec_host as the device addresses it (kernels write the record there themselves)
   int* spec_host = nullptr;   // pinned: verdict [2] | build flags + level counters [128] | walk info before [8] and after [8] the walk
   hipEvent_t spec_event = nullptr;
+  // the direct sum at arbitrary points (direct_driver.hip): flag word, a batch of targets and results, the FAST partial sums
+  void* probe_ws = nullptr;
+  size_t probe_ws_bytes = 0;
 };
 
 namespace nbody {
@@ -216,6 +219,8 @@ int ctx_direct_prep(nbody_ctx* c, hipStream_t stream, int64_t n_src, const void*
 int ctx_direct_run(nbody_ctx* c, hipStream_t stream, int64_t n_src, const void* pos_all, const void* mass_all, float uniform_mass,
                    int64_t tgt_begin, int64_t n_tgt, void* vel, void* pos_out, void* acc_out, float delta, float clamp, int arith,
                    int64_t n_tgt_total, int64_t n_tgt_max, void* ws, size_t ws_bytes, nbody_timer* timer);
+// nbody_accel_direct_at_* on one device, arguments checked, n_targets > 0 (direct_driver.hip)
+int ctx_accel_direct_at(nbody_ctx* c, bool f64, int64_t n_targets, const void* target_xy, void* acc_xy);
 // ---- multi.hip (`front` is the handle nbody_create_multi returned)
 void multi_destroy(nbody_ctx* front);
 int multi_set_params(nbody_ctx* front);
@@ -224,5 +229,6 @@ nbody_ctx* multi_peek(const nbody_ctx* front);            // the first device's 
 int multi_primary(nbody_ctx* front, nbody_ctx** out);     // ... after bringing every replica up to date
 int multi_replicate(nbody_ctx* front);                    // the first device's rows to every other replica
 int multi_update_direct(nbody_ctx* front, float delta, int n_steps, nbody_counting* counter);
+int multi_accel_direct_at(nbody_ctx* front, bool f64, int64_t n_targets, const void* target_xy, void* acc_xy);  // a block of targets per device
 int multi_update_tree(nbody_ctx* front, bool f64, int kind, double delta, int n_steps, nbody_counting* counter);
 }  // namespace nbody

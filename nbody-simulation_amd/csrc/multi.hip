@@ -544,6 +544,23 @@ int multi_update_direct(nbody_ctx* front, float delta, int n_steps, nbody_counti
   return NBODY_OK;
 }
 
+// Every device holds all current rows (after an upload, direct steps and tree steps alike), so the targets split into G contiguous
+// blocks, one per device, each computed straight into its place in the caller's array: a target's bits are those of one device.
+int multi_accel_direct_at(nbody_ctx* front, bool f64, int64_t n_targets, const void* target_xy, void* acc_xy) {
+  Multi& M = *front->multi;
+  const size_t e2 = f64 ? sizeof(double2) : sizeof(float2);
+  const int64_t per = (n_targets + M.G - 1) / M.G;
+  int who = 0;
+  clear_errors(M);
+  DeviceGuard guard;
+  int rc = M.pool.run([&](int d) {
+    const int64_t b = std::min<int64_t>((int64_t)d * per, n_targets), cnt = std::min<int64_t>(per, n_targets - b);
+    if (cnt <= 0) return (int)NBODY_OK;
+    return ctx_accel_direct_at(M.sub[(size_t)d], f64, cnt, (const char*)target_xy + (size_t)b * e2, (char*)acc_xy + (size_t)b * e2);
+  }, &who);
+  return rc ? front_fail(front, who, rc) : NBODY_OK;
+}
+
 int multi_update_tree(nbody_ctx* front, bool f64, int kind, double delta, int n_steps, nbody_counting* counter) {
   Multi& M = *front->multi;
   if (f64 ? !front->has_f64 : !front->has_f32) return ctx_fail(front, NBODY_ERR_INVALID, "update_tree: no particles of this precision uploaded");
