@@ -52,7 +52,8 @@ extern "C" {
  *    nbody_get_stream, nbody_delta_decoder_set_max_bodies, nbody_selftest_*_f64 (round 2), nbody_multi_comm_count (round 3);
  * 3: nbody_update_direct_f64, nbody_accel_direct_f64 (the direct O(N^2) step on an f64 context);
  *    nbody_accel_direct_at_f32 / _f64 (the direct sum at arbitrary points) were added under 3: new symbols only, nothing
- *    that existed changed;
+ *    that existed changed; nbody_tracers_upload_f32 / _f64, nbody_tracers_download_f32 / _f64 and nbody_num_tracers (massless
+ *    tracers that step with the bodies) likewise: new symbols only;
  *    a binding compares nbody_abi_version() with the value it was written against before it binds anything else. */
 #define NBODY_ABI_VERSION 3
 
@@ -219,6 +220,37 @@ int nbody_accel_tree_f64(nbody_ctx* ctx, int tree_kind, int64_t n_targets, const
  * n_targets == 0 does nothing. */
 int nbody_accel_direct_at_f32(nbody_ctx* ctx, int64_t n_targets, const float* target_xy, float* acc_xy);
 int nbody_accel_direct_at_f64(nbody_ctx* ctx, int64_t n_targets, const double* target_xy, double* acc_xy);
+
+/* ---- tracers: points without mass that step with the bodies, on the device ------------------------------------
+ * m tracers (x0,y0,...; velocities likewise) of the context's precision, kept in device arrays of their own; an upload
+ * replaces any earlier set and m == 0 removes them.  While a context holds tracers, every nbody_update_direct_f32 / _f64 and
+ * nbody_update_tree_f32 / _f64 step also advances them: a tracer's acceleration is the field of the bodies at their pre-step
+ * positions — the snapshot the bodies' own force phase reads; for the tree methods the step's tree, walked at the tracer's
+ * position — and it integrates as main.rs:419-423 (v += a*dt; x += v*dt, multiply then add, no contraction).  A tracer has no
+ * mass and no self term and exerts nothing.  Rows keep their upload order for ever (a BVH's permutations concern bodies only).
+ * Arithmetic: direct steps as nbody_accel_direct_at_* documents it (EXACT one ascending-row chain per tracer; f32 FAST within
+ * the step's tolerance; AUTO the step's route, a tracer outside FAST's domain taking its EXACT value; f64 EXACT unless FAST is
+ * asked for, then gated like the f64 step with the same per-tracer exception); tree steps as nbody_accel_tree_* with targets.
+ * A tracer's route in a step is decided once, from its position before the step.
+ * All of it is decided on the device, per step: nothing is read back and no host synchronisation is added between the steps of
+ * a call.  A tracer's bits depend on its own state and the bodies alone — not on the other tracers, their number or order.
+ * The bodies' rows are bit-identical to the same steps without tracers: the same kernels run in the same order (with tracers
+ * present, small direct steps are not replayed from a captured graph and BVH steps are not enqueued ahead of the host; both
+ * routes give the same bits as the plain ones).  The FAST partial sums go through a bounded workspace in batches, whatever m
+ * is.  The timer of nbody_set_timer keeps bracketing the bodies' dominant kernel only; a direct step's tracer time is booked
+ * under sum_gravity with the rest of the call (force and integration are fused), a tree step's tracer walk under sum_gravity
+ * and their integration under post_calculations.
+ * nbody_upload_* of bodies removes the tracers (a new world).  Snapshots, delta streams, nbody_render_rgba and the parity
+ * hooks (nbody_accel_*, nbody_walk_tree_*) see bodies only and leave the tracers alone.
+ * NBODY_ERR_INVALID (the message names "tracers"): ctx NULL, m < 0, a NULL array with m > 0, the other precision, no particles
+ * uploaded, a context made by nbody_create_multi*; and nbody_update_tree_async_f32, nbody_update_tree_shard_*,
+ * nbody_export_slice_dev, nbody_import_rows_dev while tracers are present.
+ * Download: either pointer may be NULL; upload order, always.  nbody_num_tracers: 0 for NULL or none. */
+int nbody_tracers_upload_f32(nbody_ctx* ctx, int64_t m, const float* pos_xy, const float* vel_xy);
+int nbody_tracers_upload_f64(nbody_ctx* ctx, int64_t m, const double* pos_xy, const double* vel_xy);
+int nbody_tracers_download_f32(nbody_ctx* ctx, float* pos_xy, float* vel_xy);
+int nbody_tracers_download_f64(nbody_ctx* ctx, double* pos_xy, double* vel_xy);
+int64_t nbody_num_tracers(const nbody_ctx* ctx);
 
 /* Linearised tree of the last build (pre-order; node i's first child is i+1; `skip` is the pre-order index
  * following the subtree).  Any pointer may be NULL; call with all NULL to get the node count. */

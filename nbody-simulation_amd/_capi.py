@@ -83,6 +83,11 @@ _SIGS = {
     "nbody_accel_direct_f64": (C.c_int, [_vp, _vp]),
     "nbody_accel_direct_at_f32": (C.c_int, [_vp, _i64, _vp, _vp]),
     "nbody_accel_direct_at_f64": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "nbody_tracers_upload_f32": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "nbody_tracers_upload_f64": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "nbody_tracers_download_f32": (C.c_int, [_vp, _vp, _vp]),
+    "nbody_tracers_download_f64": (C.c_int, [_vp, _vp, _vp]),
+    "nbody_num_tracers": (_i64, [_vp]),
     "nbody_accel_tree_f32": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_accel_tree_f64": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_tree_info": (C.c_int, [_vp, C.POINTER(TreeView)]),
@@ -495,6 +500,30 @@ class Context:
         check(self.h, f(self.h, _ptr(pos), _ptr(vel), _ptr(w), _ptr(ids)))
         return pos, vel, w, ids
 
+    def upload_tracers(self, pos, vel):
+        """Massless tracers (m, 2) that every update_direct / update_tree step advances with the bodies, on the device
+        (nbody_tracers_upload_*): cast to the context's dtype; replaces any earlier set, m == 0 removes them."""
+        if self.dtype is None:
+            raise NBodyError(ERR_INVALID, "upload_tracers: tracers need particles uploaded first")
+        pos = np.ascontiguousarray(pos, dtype=self.dtype).reshape(-1, 2)
+        vel = np.ascontiguousarray(vel, dtype=self.dtype).reshape(-1, 2)
+        if vel.shape[0] != pos.shape[0]:
+            raise ValueError("pos/vel length mismatch")
+        f = self.lib.nbody_tracers_upload_f64 if self.dtype == np.float64 else self.lib.nbody_tracers_upload_f32
+        check(self.h, f(self.h, pos.shape[0], _ptr(pos), _ptr(vel)))
+
+    def download_tracers(self):
+        """-> (pos[m,2], vel[m,2]) of the tracers, in upload order."""
+        m, dt = self.n_tracers, self.dtype
+        pos, vel = np.zeros((m, 2), dt), np.zeros((m, 2), dt)
+        f = self.lib.nbody_tracers_download_f64 if dt == np.float64 else self.lib.nbody_tracers_download_f32
+        check(self.h, f(self.h, _ptr(pos), _ptr(vel)))
+        return pos, vel
+
+    @property
+    def n_tracers(self) -> int:
+        return int(self.lib.nbody_num_tracers(self.h))
+
     # ---- steps
     def update_direct(self, delta, n_steps=1, counter: Counting | None = None):
         f = self.lib.nbody_update_direct_f64 if self.dtype == np.float64 else self.lib.nbody_update_direct_f32
@@ -671,6 +700,12 @@ class MultiContext(Context):
         """Multi-device direct steps are f32 only: after an f64 upload this fails, as it always has."""
         check(self.h, self.lib.nbody_update_direct_f32(self.h, float(delta), int(n_steps),
                                                        C.byref(counter) if counter is not None else None))
+
+    def upload_tracers(self, pos, vel):
+        raise NBodyError(ERR_INVALID, "upload_tracers: tracers are not available on a multi-device context")
+
+    def download_tracers(self):
+        raise NBodyError(ERR_INVALID, "download_tracers: tracers are not available on a multi-device context")
 
 
 def mass_hint(weight) -> float:

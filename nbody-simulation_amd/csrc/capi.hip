@@ -80,6 +80,11 @@ template <class T> void free_state(State<T>& s) {
   s.classes = typename State<T>::MassClasses{};
 }
 
+void free_tracers(nbody_ctx* c) {
+  free_dev(c->tracers.pos); free_dev(c->tracers.vel); free_dev(c->tracers.acc); free_dev(c->tracers.mark);
+  c->tracers.m = 0;
+}
+
 // -------------------------------------------------------------------------------------------- upload / download
 template <class T> int upload(nbody_ctx* c, int64_t n, const T* pos, const T* vel, const uint32_t* w) {
   if (!c) return NBODY_ERR_INVALID;
@@ -88,6 +93,7 @@ template <class T> int upload(nbody_ctx* c, int64_t n, const T* pos, const T* ve
   c->direct_graph.reset();
   free_state(c->sf);
   free_state(c->sd);
+  free_tracers(c);  // a new world
   c->has_f32 = c->has_f64 = false;
   c->dl_key_next = true;  // new bodies: the next delta snapshot starts a sequence
   State<T>& s = state_of<T>(c);
@@ -163,6 +169,57 @@ template <class T> int download(nbody_ctx* c, T* pos, T* vel, uint32_t* w, uint3
   return NBODY_OK;
 }
 
+// ---- tracers (ctx.h, Tracers): the arguments common to nbody_tracers_upload_* and nbody_tracers_download_*
+template <class T> int tracers_check(nbody_ctx* c, const char* what) {
+  if (!c) return fail(nullptr, NBODY_ERR_INVALID, std::string(what) + ": the context is NULL (tracers)");
+  if (c->multi) return fail(c, NBODY_ERR_INVALID, std::string(what) + ": tracers are not available on a context made by nbody_create_multi");
+  if (!has_state<T>(c))
+    return fail(c, NBODY_ERR_INVALID, std::string(what) + ((c->has_f32 || c->has_f64) ? ": tracers take the precision of the uploaded particles"
+                                                                                    : ": tracers need particles uploaded first"));
+  return NBODY_OK;
+}
+
+template <class T> int tracers_upload(nbody_ctx* c, int64_t m, const T* pos, const T* vel) {
+  using T2 = typename State<T>::T2;
+  int rc = tracers_check<T>(c, "tracers_upload");
+  if (rc) return rc;
+  if (m < 0) return fail(c, NBODY_ERR_INVALID, "tracers_upload: m < 0 (tracers)");
+  if (m > 0 && (!pos || !vel)) return fail(c, NBODY_ERR_INVALID, "tracers_upload: pos_xy or vel_xy is NULL (tracers)");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  free_tracers(c);
+  if (m == 0) return NBODY_OK;
+  Tracers& tr = c->tracers;
+  const size_t bytes = (size_t)m * sizeof(T2);
+  hipError_t e = hipMalloc(&tr.pos, bytes);
+  if (e == hipSuccess) e = hipMalloc(&tr.vel, bytes);
+  if (e == hipSuccess) e = hipMalloc(&tr.acc, bytes);
+  if (e == hipSuccess) e = hipMalloc((void**)&tr.mark, (size_t)m);
+  if (e == hipSuccess) e = hipMemcpyAsync(tr.pos, pos, bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(tr.vel, vel, bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    free_tracers(c);
+    return fail_hip(c, e, "tracers_upload");
+  }
+  tr.m = m;
+  return NBODY_OK;
+}
+
+template <class T> int tracers_download(nbody_ctx* c, T* pos, T* vel) {
+  using T2 = typename State<T>::T2;
+  int rc = tracers_check<T>(c, "tracers_download");
+  if (rc) return rc;
+  const Tracers& tr = c->tracers;
+  if (tr.m == 0) return NBODY_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t bytes = (size_t)tr.m * sizeof(T2);
+  if (pos) HIPCHK(c, hipMemcpyAsync(pos, tr.pos, bytes, hipMemcpyDeviceToHost, c->stream));
+  if (vel) HIPCHK(c, hipMemcpyAsync(vel, tr.vel, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return NBODY_OK;
+}
+
 }  // namespace
 
 int nbody::fail(nbody_ctx* c, int code, const std::string& msg) {
@@ -234,6 +291,7 @@ void nbody::ctx_destroy_single(nbody_ctx* c) {
   c->direct_graph.reset();
   free_state(c->sf);
   free_state(c->sd);
+  free_tracers(c);
   free_dev(c->workspace);
   free_dev(c->probe_ws);
   free_dev(c->stats_dev);
@@ -295,6 +353,12 @@ NB_API int64_t nbody_num_particles(const nbody_ctx* c) {
   if (c->multi) return nbody_num_particles(nbody::multi_peek(c));
   return c->has_f32 ? c->sf.n : (c->has_f64 ? c->sd.n : 0);
 }
+
+NB_API int nbody_tracers_upload_f32(nbody_ctx* c, int64_t m, const float* pos, const float* vel) { return tracers_upload<float>(c, m, pos, vel); }
+NB_API int nbody_tracers_upload_f64(nbody_ctx* c, int64_t m, const double* pos, const double* vel) { return tracers_upload<double>(c, m, pos, vel); }
+NB_API int nbody_tracers_download_f32(nbody_ctx* c, float* pos, float* vel) { return tracers_download<float>(c, pos, vel); }
+NB_API int nbody_tracers_download_f64(nbody_ctx* c, double* pos, double* vel) { return tracers_download<double>(c, pos, vel); }
+NB_API int64_t nbody_num_tracers(const nbody_ctx* c) { return c ? c->tracers.m : 0; }
 
 NB_API int nbody_get_counting(const nbody_ctx* c, nbody_counting* out) {
   if (!c || !out) return NBODY_ERR_INVALID;

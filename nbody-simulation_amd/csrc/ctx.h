@@ -86,6 +86,17 @@ template <class T> struct State {
 };
 
 
+// Massless tracers that step with the bodies (tracers.h; nbody_tracers_*): rows of the context's precision in upload order,
+// for ever — the BVH's permutations concern bodies only.  `acc` receives a tree step's walk at the tracers; `mark` a direct step's
+// decision per tracer (1: EXACT), taken from the pre-step positions before anything is integrated.
+struct Tracers {
+  int64_t m = 0;
+  void* pos = nullptr;
+  void* vel = nullptr;
+  void* acc = nullptr;
+  uint8_t* mark = nullptr;
+};
+
 // The `uniform_mass` argument of the direct step for this state: > 0 all equal, < 0 all equal to its magnitude but a few, 0 neither.
 template <class T> inline float direct_mass_hint(const State<T>& s) { return s.uniform_mass > 0.f ? s.uniform_mass : -s.sparse_base; }
 
@@ -199,6 +210,7 @@ struct nbody_ctx {
   // the direct sum at arbitrary points (direct_driver.hip): flag word, a batch of targets and results, the FAST partial sums
   void* probe_ws = nullptr;
   size_t probe_ws_bytes = 0;
+  nbody::Tracers tracers;  // of the precision of the bodies; a body upload removes them
 };
 
 namespace nbody {

@@ -1,8 +1,9 @@
 // libnbody_hip — the direct-sum driver: the kernel configuration and workspace layout of a step, the mass classes, the
 // preparation / run split multi.hip shards over devices, the hipGraph replay of step pairs, and the direct entry points
 // of the C ABI (nbody_update_direct_f32, nbody_accel_direct_f32, nbody_direct_*_dev), and the f64 direct entry points
-// (nbody_update_direct_f64, nbody_accel_direct_f64), and the direct sum at arbitrary points (nbody_accel_direct_at_f32 / _f64).
-// Kernels: direct_kernels.hip, nearfar.hip, direct64.hip, direct_probe.hip.
+// (nbody_update_direct_f64, nbody_accel_direct_f64), and the direct sum at arbitrary points (nbody_accel_direct_at_f32 / _f64),
+// and the tracers' share of a direct step.
+// Kernels: direct_kernels.hip, nearfar.hip, direct64.hip, direct_probe.hip, tracers.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -12,6 +13,7 @@
 #include "direct_kernels.h"
 #include "direct_probe.h"
 #include "driver.h"
+#include "tracers.h"
 
 using namespace nbody;
 
@@ -381,6 +383,106 @@ int ctx_ensure_mass_classes(nbody_ctx* c) { return c && c->has_f32 ? ensure_mass
 
 }  // namespace nbody
 
+// ---- tracers (ctx.h, Tracers; kernels: tracers.hip and the probe call's FAST passes)
+// The tracers' share of one direct step, enqueued behind the bodies' kernels of that step and before its buffers swap: `pos` /
+// `mass` are the bodies at their pre-step positions, which the step's kernels only read.  Routing as nbody_accel_direct_at_*
+// (below), but nothing comes back to the host: tracer_mark reads the decision word the bodies' step has just written to the
+// workspace and every tracer's pre-step position, and leaves one mark per tracer (which of the two finishing kernels integrates
+// it) and a decision word of the tracers' own at the head of ctx->probe_ws, which gates the f32 FAST main pass (the f64 pass has
+// no gate: it runs for nothing in a step whose bodies left the f64 FAST domain).  The FAST partial sums go through ctx->probe_ws
+// in batches of the probe call's size, so the workspace is bounded whatever the number of tracers.
+namespace {
+constexpr size_t kTracerFlagBytes = 256;
+
+int tracer_batch(nbody_ctx* c, int64_t m, size_t elem, int64_t max_partial, int gsplit, int64_t* batch) {
+  const int64_t b = std::min<int64_t>(1 << 20, max_partial / gsplit) / 256 * 256;
+  *batch = std::min<int64_t>(m, std::max<int64_t>(b, 256));
+  return ensure_dev_bytes(c, c->probe_ws, c->probe_ws_bytes, kTracerFlagBytes + (size_t)*batch * elem * (size_t)gsplit);
+}
+
+int tracers_direct_f32(nbody_ctx* c, const float2* pos, const float* mass, float delta) {
+  const Tracers& tr = c->tracers;
+  if (tr.m == 0) return NBODY_OK;
+  const State<float>& s = c->sf;
+  const int64_t n = s.n, m = tr.m;
+  const float clamp = c->params.clamp;
+  int arith = c->params.arith;
+  if (arith != NBODY_ARITH_EXACT && !(clamp >= 1.9073486328125e-06f)) arith = NBODY_ARITH_EXACT;  // as direct_plan
+  float2 *tpos = (float2*)tr.pos, *tvel = (float2*)tr.vel;
+  if (arith == NBODY_ARITH_EXACT || n == 0) {
+    HIPCHK(c, launch_tracer_exact<float>(c->stream, pos, mass, n, tpos, tvel, m, clamp, delta, nullptr));
+    return NBODY_OK;
+  }
+  TracerRoute r;
+  if (arith == NBODY_ARITH_AUTO) {  // the step's own decision (kFlagState == 2: a body outside FAST's domain), and the per-tracer exception
+    r.word = (const int*)c->workspace;
+    r.word_kind = kTracerWordState;
+    r.per_target = 1;
+  }
+  const int g = probe_gsplit_f32(n);
+  int64_t batch = 0;
+  int rc = tracer_batch(c, m, sizeof(float2), (int64_t)1 << 23, g, &batch);
+  if (rc) return rc;
+  int* state = (int*)c->probe_ws;
+  float2* part = (float2*)((char*)c->probe_ws + kTracerFlagBytes);
+  HIPCHK(c, launch_tracer_mark<float>(c->stream, tpos, m, r, tr.mark, state));
+  for (int64_t b0 = 0; b0 < m; b0 += batch) {
+    const int64_t nb = std::min<int64_t>(batch, m - b0);
+    DirectArgs a{};
+    a.pos_all = tpos + b0;  // the tracers ...
+    a.src_pos = pos;        // ... and the bodies
+    a.mass_all = mass;
+    a.n_src = (int)n;
+    a.tgt_begin = 0;
+    a.n_tgt = (int)nb;
+    a.partial = part;
+    a.to_partial = 1;
+    a.clamp = clamp;
+    a.uniform_mass = s.uniform_mass > 0.f ? s.uniform_mass : 0.f;
+    a.flags = state;
+    a.run_state = 1;  // (tracer_mark wrote 2 when the step-level route is EXACT: the pass returns at once)
+    DirectConfig cfg;
+    cfg.tpt = 1;
+    cfg.gsplit = g;
+    cfg.use_asm = 2;  // the packed pass through LDS, with the clamp: the probe call's main pass
+    cfg.nearfar = false;
+    HIPCHK(c, launch_direct_fast(c->stream, a, cfg, false));
+    HIPCHK(c, launch_tracer_finish<float>(c->stream, part, g, nb, tpos + b0, tvel + b0, delta, tr.mark + b0));
+  }
+  if (r.per_target) HIPCHK(c, launch_tracer_exact<float>(c->stream, pos, mass, n, tpos, tvel, m, clamp, delta, tr.mark));  // the fix-up pass
+  return NBODY_OK;
+}
+
+int tracers_direct_f64(nbody_ctx* c, const double2* pos, const double* mass, double delta) {
+  const Tracers& tr = c->tracers;
+  if (tr.m == 0) return NBODY_OK;
+  const int64_t n = c->sd.n, m = tr.m;
+  const double clamp = (double)c->params.clamp;  // as direct64_step
+  double2 *tpos = (double2*)tr.pos, *tvel = (double2*)tr.vel;
+  if (!(c->params.arith == NBODY_ARITH_FAST && clamp > 0.0) || n == 0) {
+    HIPCHK(c, launch_tracer_exact<double>(c->stream, pos, mass, n, tpos, tvel, m, clamp, delta, nullptr));
+    return NBODY_OK;
+  }
+  TracerRoute r;
+  r.word = (const int*)c->workspace;  // the domain flag the f64 step has just scanned the bodies into
+  r.word_kind = kTracerWordDomain64;
+  r.per_target = 1;
+  const int g = probe_gsplit_f64(n);
+  int64_t batch = 0;
+  int rc = tracer_batch(c, m, sizeof(double2), (int64_t)1 << 22, g, &batch);
+  if (rc) return rc;
+  double2* part = (double2*)((char*)c->probe_ws + kTracerFlagBytes);
+  HIPCHK(c, launch_tracer_mark<double>(c->stream, tpos, m, r, tr.mark, (int*)c->probe_ws));
+  for (int64_t b0 = 0; b0 < m; b0 += batch) {
+    const int64_t nb = std::min<int64_t>(batch, m - b0);
+    HIPCHK(c, launch_probe_fast_pass_f64(c->stream, pos, mass, n, tpos + b0, nb, clamp, part));
+    HIPCHK(c, launch_tracer_finish<double>(c->stream, part, g, nb, tpos + b0, tvel + b0, delta, tr.mark + b0));
+  }
+  HIPCHK(c, launch_tracer_exact<double>(c->stream, pos, mass, n, tpos, tvel, m, clamp, delta, tr.mark));  // the fix-up pass
+  return NBODY_OK;
+}
+}  // namespace
+
 NB_API int nbody_update_direct_f32(nbody_ctx* c, float delta, int n_steps, nbody_counting* counter) {
   if (!c) return NBODY_ERR_INVALID;
   if (c->multi) return nbody::multi_update_direct(c, delta, n_steps, counter);
@@ -393,7 +495,8 @@ NB_API int nbody_update_direct_f32(nbody_ctx* c, float delta, int n_steps, nbody
   const double t_begin = now_s();
   int step = 0;
   // ---- graph replay of step pairs (no timer attached: event records do not belong in a captured graph)
-  const bool want_graph = n_steps >= 4 && s.n > 0 && s.n <= (1 << 17) && !c->timer && env_int("NBODY_DIRECT_GRAPH", 1) != 0;
+  // (nor with tracers present: their launches are not part of the captured pair; the eager steps give the same bits)
+  const bool want_graph = n_steps >= 4 && s.n > 0 && s.n <= (1 << 17) && !c->timer && c->tracers.m == 0 && env_int("NBODY_DIRECT_GRAPH", 1) != 0;
   rc = ensure_mass_classes(c);  // (host work and copies: before any capture)
   if (rc) return rc;
   if (want_graph) {
@@ -438,6 +541,8 @@ NB_API int nbody_update_direct_f32(nbody_ctx* c, float delta, int n_steps, nbody
     auto& st = s.set[s.cur];
     rc = direct_step_dev(c, c->stream, s.n, st.pos, st.mass, direct_mass_hint(s), 0, s.n, st.vel, s.pos_next, nullptr, delta,
                          c->params.clamp, c->params.arith, c->workspace, c->workspace_bytes, c->timer);
+    if (rc) return rc;
+    rc = tracers_direct_f32(c, st.pos, st.mass, delta);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::swap(st.pos, s.pos_next);
@@ -546,8 +651,10 @@ NB_API int nbody_update_direct_f64(nbody_ctx* c, double delta, int n_steps, nbod
   int rc = ctx_ensure_workspace(c, direct64_ws_bytes(s.n));
   if (rc) return rc;
   const double t_begin = now_s();
-  for (int step = 0; step < n_steps && s.n > 0; ++step) {
-    rc = direct64_step(c, delta, true);
+  for (int step = 0; step < n_steps && (s.n > 0 || c->tracers.m > 0); ++step) {
+    rc = s.n > 0 ? direct64_step(c, delta, true) : NBODY_OK;
+    if (rc) return rc;
+    rc = tracers_direct_f64(c, s.set[s.cur].pos, s.set[s.cur].mass, delta);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::swap(s.set[s.cur].pos, s.pos_next);

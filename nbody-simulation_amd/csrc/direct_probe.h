@@ -29,6 +29,10 @@ hipError_t launch_probe_finish_f32(hipStream_t s, const float2* partial, int gsp
 // probe_gsplit_f64(n_src) source splits, the partial sums [gsplit][n_tgt] added in split order.
 hipError_t launch_probe_f64(hipStream_t s, const double2* src, const double* mass, int64_t n_src, const double2* tgt, int64_t n_tgt,
                             double clamp, bool fast, double2* partial, double2* acc);
+// The FAST pass of launch_probe_f64 alone: partial[probe_gsplit_f64(n_src)][n_tgt], left for the caller to add in split order
+// (the tracer step's finish integrates in the same kernel, tracers.h).
+hipError_t launch_probe_fast_pass_f64(hipStream_t s, const double2* src, const double* mass, int64_t n_src, const double2* tgt, int64_t n_tgt,
+                                      double clamp, double2* partial);
 // flag |= 1 when a coordinate of xy lies outside the f64 FAST domain of direct64.h (the flag is not cleared here).
 hipError_t launch_probe_domain_f64(hipStream_t s, const double* xy, int64_t n_doubles, int* flag);
 

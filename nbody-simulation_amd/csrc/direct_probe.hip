@@ -178,10 +178,18 @@ hipError_t launch_probe_f64(hipStream_t s, const double2* src, const double* mas
     hipLaunchKernelGGL((probe_pass_f64<false, 8>), dim3(blocks_of(n_tgt)), dim3(256), 0, s, src, mass, n_src, tgt, n_tgt, clamp, 1, acc);
     return hipGetLastError();
   }
+  hipError_t e = launch_probe_fast_pass_f64(s, src, mass, n_src, tgt, n_tgt, clamp, partial);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(probe_finish_f64, dim3(blocks_of(n_tgt)), dim3(256), 0, s, partial, probe_gsplit_f64(n_src), n_tgt, acc);
+  return hipGetLastError();
+}
+
+hipError_t launch_probe_fast_pass_f64(hipStream_t s, const double2* src, const double* mass, int64_t n_src, const double2* tgt, int64_t n_tgt,
+                                      double clamp, double2* partial) {
+  if (n_tgt <= 0) return hipSuccess;
   const int g = probe_gsplit_f64(n_src);
   hipLaunchKernelGGL((probe_pass_f64<true, 8>), dim3(blocks_of(n_tgt), (unsigned)g), dim3(256), 0, s, src, mass, n_src, tgt, n_tgt, clamp, g,
                      partial);
-  hipLaunchKernelGGL(probe_finish_f64, dim3(blocks_of(n_tgt)), dim3(256), 0, s, partial, g, n_tgt, acc);
   return hipGetLastError();
 }
 

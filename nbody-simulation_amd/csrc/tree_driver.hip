@@ -431,6 +431,30 @@ template <class T> int bvh_step_ahead(nbody_ctx* c, State<T>& s, T delta, PhaseE
   }
 }
 
+// The tracers' share of a tree step (ctx.h, Tracers): the step's tree walked at the tracers' positions, after the bodies' walk
+// and before anything is integrated (a BVH's leaves ARE the bodies' rows), in batches that bound the walk's scratch; then their
+// integration behind the bodies'.  The timer and the walk statistics stay the bodies' alone, and so does ws_backoff: how many
+// terms the tracers take says nothing about which walk suits the bodies.  (What the tracers' walk does displace is the bodies'
+// history for the next walk's estimate — wt_hist_n — so that walk counts its terms instead; and each batch of a tile walk reads
+// its `info` back, one host wait of the kind the bodies' walk has.)
+constexpr int64_t kTracerWalkBatch = 1 << 20;
+template <class T> int tracers_walk(nbody_ctx* c, State<T>& s, int kind) {
+  using T2 = typename State<T>::T2;
+  const Tracers& tr = c->tracers;
+  nbody_timer* timer = c->timer;
+  const bool want_stats = c->want_stats;
+  const int backoff = s.ws_backoff;
+  c->timer = nullptr;
+  c->want_stats = false;
+  int rc = NBODY_OK;
+  for (int64_t b0 = 0; b0 < tr.m && !rc; b0 += kTracerWalkBatch)
+    rc = tree_walk_phase<T>(c, s, kind, (const T2*)tr.pos + b0, std::min<int64_t>(kTracerWalkBatch, tr.m - b0), (T2*)tr.acc + b0);
+  c->timer = timer;
+  c->want_stats = want_stats;
+  s.ws_backoff = backoff;
+  return rc;
+}
+
 // One step in the plain sequence — no host wait between the phases but those a phase needs for itself — over every row, or
 // (count >= 0) a rank's slice [begin, begin + count) of the tree-ordered targets (update_tree_shard).
 template <class T> int plain_tree_step(nbody_ctx* c, State<T>& s, int kind, T delta, int64_t begin = 0, int64_t count = -1) {
@@ -439,11 +463,14 @@ template <class T> int plain_tree_step(nbody_ctx* c, State<T>& s, int kind, T de
   if (!rc) rc = tree_build_phase<T>(c, s, kind);
   if (!rc) rc = phase_mark(c, ph, 1);
   if (!rc) rc = tree_walk_phase<T>(c, s, kind, nullptr, 0, s.acc, begin, count);
+  const bool tracers = count < 0 && c->tracers.m > 0;  // (a sharded step refuses them)
+  if (!rc && tracers) rc = tracers_walk<T>(c, s, kind);
   if (!rc) rc = phase_mark(c, ph, 2);
   if (rc) return rc;
   auto& st = s.set[s.cur];
   if (count < 0) {
     hipError_t e = launch_integrate<T>(c->stream, st.pos, st.vel, s.acc, s.n, delta);
+    if (e == hipSuccess && tracers) e = launch_integrate<T>(c->stream, c->tracers.pos, c->tracers.vel, c->tracers.acc, c->tracers.m, delta);
     if (e != hipSuccess) return fail_hip(c, e, "launch_integrate");
   } else {
     const uint32_t* rows = kind == NBODY_TREE_QUAD ? s.order_dev + begin : nullptr;
@@ -478,7 +505,7 @@ template <class T> int update_tree(nbody_ctx* c, int kind, T delta, int n_steps,
       if (rc) return done(rc);
       chain = PhaseEvents{};
     }
-    if (kind == NBODY_TREE_BVH) {
+    if (kind == NBODY_TREE_BVH && c->tracers.m == 0) {  // (the step enqueued ahead does not carry the tracers' walk: the plain sequence, same bits)
       int rc = bvh_step_ahead<T>(c, s, delta, &chain);
       if (rc < 0) return done(rc);
       if (rc == NBODY_OK) {
@@ -602,6 +629,10 @@ template <class T> int accel_tree(nbody_ctx* c, int kind, int64_t n_targets, con
 
 using namespace nbody;
 
+static int not_with_tracers(nbody_ctx* c, const char* what) {
+  return fail(c, NBODY_ERR_INVALID, std::string(what) + ": not available while the context holds tracers (nbody_tracers_upload_*)");
+}
+
 NB_API int nbody_update_tree_f32(nbody_ctx* c, int kind, float delta, int n_steps, nbody_counting* counter) {
   if (c && c->multi) return nbody::multi_update_tree(c, false, kind, (double)delta, n_steps, counter);
   return update_tree<float>(c, kind, delta, n_steps, counter);
@@ -613,6 +644,7 @@ NB_API int nbody_update_tree_f64(nbody_ctx* c, int kind, double delta, int n_ste
 // Asynchronous form of nbody_update_tree_f32 and its completion.
 NB_API int nbody_update_tree_async_f32(nbody_ctx* c, int kind, float delta, int n_steps) {
   if (c && c->multi) return nbody::multi_update_tree(c, false, kind, (double)delta, n_steps, nullptr);  // (synchronous there)
+  if (c && c->tracers.m > 0) return not_with_tracers(c, "update_tree_async");
   return update_tree<float>(c, kind, delta, n_steps, nullptr, true);
 }
 NB_API int nbody_wait(nbody_ctx* c) {
@@ -629,21 +661,25 @@ static int not_on_multi(nbody_ctx* c, const char* what) {
 }
 NB_API int nbody_update_tree_shard_f32(nbody_ctx* c, int kind, float delta, int64_t begin, int64_t count, nbody_counting* counter) {
   if (c && c->multi) return not_on_multi(c, "update_tree_shard");
+  if (c && c->tracers.m > 0) return not_with_tracers(c, "update_tree_shard");
   return update_tree_shard<float>(c, kind, delta, begin, count, counter);
 }
 NB_API int nbody_update_tree_shard_f64(nbody_ctx* c, int kind, double delta, int64_t begin, int64_t count, nbody_counting* counter) {
   if (c && c->multi) return not_on_multi(c, "update_tree_shard");
+  if (c && c->tracers.m > 0) return not_with_tracers(c, "update_tree_shard");
   return update_tree_shard<double>(c, kind, delta, begin, count, counter);
 }
 NB_API int nbody_export_slice_dev(nbody_ctx* c, int64_t begin, int64_t count, void* rows_u32, void* pos_xy, void* vel_xy) {
   if (!c) return NBODY_ERR_INVALID;
   if (c->multi) return not_on_multi(c, "export_slice");
+  if (c && c->tracers.m > 0) return not_with_tracers(c, "export_slice");
   return c->has_f64 ? export_slice<double>(c, begin, count, rows_u32, pos_xy, vel_xy)
                     : export_slice<float>(c, begin, count, rows_u32, pos_xy, vel_xy);
 }
 NB_API int nbody_import_rows_dev(nbody_ctx* c, int64_t n_rows, const void* rows_u32, const void* pos_xy, const void* vel_xy) {
   if (!c) return NBODY_ERR_INVALID;
   if (c->multi) return not_on_multi(c, "import_rows");
+  if (c && c->tracers.m > 0) return not_with_tracers(c, "import_rows");
   return c->has_f64 ? import_rows_api<double>(c, n_rows, rows_u32, pos_xy, vel_xy)
                     : import_rows_api<float>(c, n_rows, rows_u32, pos_xy, vel_xy);
 }

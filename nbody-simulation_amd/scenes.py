@@ -5,6 +5,7 @@ plummer():   2-D projection of a Plummer sphere — the synthetic input of every
              be generated independently (each rank of a sharded run generates the same full set).
 galaxy():    the scene of World::new (main.rs:276-346) with a seeded generator: two heavy bodies, a thinned
              lattice disc around the second, 100 000 bodies in a uniform-angle/uniform-radius disc.
+restricted(): a scene split into the bodies that carry the field and massless tracers (the restricted problem).
 """
 from __future__ import annotations
 
@@ -116,3 +117,13 @@ def galaxy(seed: int = 0xC0FFEE, dtype=np.float32):
     vel = np.concatenate([np.stack(vel), v.astype(np.float32), bv]).astype(dtype)
     weight = np.concatenate([np.array(w, np.uint32), np.ones(p.shape[0] + n_disc, np.uint32)])
     return pos, vel, weight
+
+
+def restricted(pos, vel, weight, min_weight):
+    """The restricted problem of a scene: -> ((pos, vel, weight) of the bodies with weight >= min_weight, (pos, vel) of the
+    rest), each part in the scene's row order.  The first part is what `World(...)` takes as bodies, the second its
+    `tracers=`: points that feel the bodies and exert nothing.  For galaxy() with min_weight = 2 that is the two heavy bodies
+    and ~151 000 tracers — a step of 2 x 151 000 pairs where the full direct sum has 151 000^2."""
+    pos, vel, weight = np.asarray(pos), np.asarray(vel), np.asarray(weight)
+    heavy = weight >= min_weight
+    return (pos[heavy], vel[heavy], weight[heavy]), (pos[~heavy], vel[~heavy])

@@ -26,9 +26,11 @@ _METHODS = {"bvh": _capi.TREE_BVH, "quad": _capi.TREE_QUAD, "direct": None}
 
 class World:
     def __init__(self, position, velocity, weight=None, *, method="bvh", device=0, devices=None, theta=THETA, clamp=0.001,
-                 leaf_size=64, order="as_written", arith="auto", quad_root=(0.0, 0.0, float(HEIGHT))):
+                 leaf_size=64, order="as_written", arith="auto", quad_root=(0.0, 0.0, float(HEIGHT)), tracers=None):
         """`devices=[0, 1, ...]`: the same world on several GPUs of one node behind one handle (nbody_create_multi);
-        `update` is still the one call of main.rs:120, the library shards the step and exchanges the results."""
+        `update` is still the one call of main.rs:120, the library shards the step and exchanges the results.
+        `tracers=(position, velocity)`: points without mass that every `update` advances with the bodies, on the device
+        (nbody_tracers_upload_*; one GPU only); read them back with `tracers()`."""
         if method not in _METHODS:
             raise ValueError(f"method must be one of {sorted(_METHODS)}")
         self.method = method
@@ -41,6 +43,8 @@ class World:
         self.ctx.upload(position, velocity, weight)
         if method == "direct" and devices is not None and self.ctx.dtype != np.float32:
             raise ValueError("multi-device direct steps are f32 only")
+        if tracers is not None:
+            self.ctx.upload_tracers(*tracers)
 
     def update(self, delta: float, counter: Counting | None = None, n_steps: int = 1):
         """World::update (main.rs:388-425): build, force, integrate; accumulates phase seconds into `counter`."""
@@ -66,6 +70,10 @@ class World:
         """-> (position[n,2], velocity[n,2], weight[n], ids[n]); rows are in the order the reference's
         `self.particles` would be in (permuted by every BVH build); ids give each row's original index."""
         return self.ctx.download()
+
+    def tracers(self):
+        """-> (position[m,2], velocity[m,2]) of the tracers, in the order they were given, always."""
+        return self.ctx.download_tracers()
 
     def snapshot_begin(self):
         """Hand the current particles to a consumer without stopping the simulation (the `try_send` of
