@@ -1,5 +1,6 @@
 // libnbody_hip — context and extern "C" surface (include/nbody_hip.h): create/destroy, parameters, upload/download,
-// the kernel timer, counters and self-tests.  The steps live beside it: direct_driver.hip (direct sum),
+// the kernel timer, counters and self-tests.  The steps live beside it: direct_driver.hip (direct sum), target_driver.hip (the
+// sum at points that are not bodies: probes, tracers),
 // tree_build_driver.hip and tree_driver.hip (Barnes-Hut builds, walks, the step driver), caller_tree.hip (trees that cross
 // the C ABI), snapshot.hip (snapshots, delta snapshots, render); multi.hip fronts several devices with one handle.
 //

@@ -86,7 +86,7 @@ template <class T> struct State {
 };
 
 
-// Massless tracers that step with the bodies (tracers.h; nbody_tracers_*): rows of the context's precision in upload order,
+// Massless tracers that step with the bodies (target_kernels.h; nbody_tracers_*): rows of the context's precision in upload order,
 // for ever — the BVH's permutations concern bodies only.  `acc` receives a tree step's walk at the tracers; `mark` a direct step's
 // decision per tracer (1: EXACT), taken from the pre-step positions before anything is integrated.
 struct Tracers {
@@ -207,14 +207,14 @@ struct nbody_ctx {
   int* spec_host_dev = nullptr;  // spec_host as the device addresses it (kernels write the record there themselves)
   int* spec_host = nullptr;   // pinned: verdict [2] | build flags + level counters [128] | walk info before [8] and after [8] the walk
   hipEvent_t spec_event = nullptr;
-  // the direct sum at arbitrary points (direct_driver.hip): flag word, a batch of targets and results, the FAST partial sums
+  // the direct sum at arbitrary points and the tracers' share of a direct step (target_driver.hip): flag word, a batch of targets and results, the FAST partial sums
   void* probe_ws = nullptr;
   size_t probe_ws_bytes = 0;
   nbody::Tracers tracers;  // of the precision of the bodies; a body upload removes them
 };
 
 namespace nbody {
-// ---- the single-device driver: capi.hip (context, upload), tree_driver.hip (tree steps), direct_driver.hip (direct steps)
+// ---- the single-device driver: capi.hip (context, upload), tree_driver.hip (tree steps), direct_driver.hip (direct steps), target_driver.hip (probes, tracers)
 int ctx_fail(nbody_ctx* c, int code, const std::string& msg);  // c == NULL: the thread's create error
 int ctx_create_single(nbody_ctx** out, int device_id);
 void ctx_destroy_single(nbody_ctx* c);
@@ -231,7 +231,7 @@ int ctx_direct_prep(nbody_ctx* c, hipStream_t stream, int64_t n_src, const void*
 int ctx_direct_run(nbody_ctx* c, hipStream_t stream, int64_t n_src, const void* pos_all, const void* mass_all, float uniform_mass,
                    int64_t tgt_begin, int64_t n_tgt, void* vel, void* pos_out, void* acc_out, float delta, float clamp, int arith,
                    int64_t n_tgt_total, int64_t n_tgt_max, void* ws, size_t ws_bytes, nbody_timer* timer);
-// nbody_accel_direct_at_* on one device, arguments checked, n_targets > 0 (direct_driver.hip)
+// nbody_accel_direct_at_* on one device, arguments checked, n_targets > 0 (target_driver.hip)
 int ctx_accel_direct_at(nbody_ctx* c, bool f64, int64_t n_targets, const void* target_xy, void* acc_xy);
 // ---- multi.hip (`front` is the handle nbody_create_multi returned)
 void multi_destroy(nbody_ctx* front);

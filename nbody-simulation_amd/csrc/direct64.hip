@@ -10,6 +10,7 @@
 
 #include "direct64.h"
 #include "env.h"
+#include "fast_domain.h"
 #include "pair.h"
 
 namespace nbody {
@@ -112,12 +113,12 @@ __global__ __launch_bounds__(256) void direct64_finish(const Direct64Args a) {
   direct64_out(a, t, s.x, s.y);
 }
 
-// The FAST domain of direct64.h, every coordinate: finite, below 2^100 in magnitude, zero or at least 2^-300.
+// The FAST domain of direct64.h (fast_domain.h), every coordinate: finite, below 2^100 in magnitude, zero or at least 2^-300.
 __global__ __launch_bounds__(256) void direct64_domain_scan(const double* xy, int64_t n_doubles, int* flag) {
   bool out = false;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_doubles; i += (int64_t)gridDim.x * 256) {
     const double v = __builtin_fabs(xy[i]);
-    out |= !(v < 0x1p100) || (v != 0.0 && v < 0x1p-300);  // (a NaN fails the first test)
+    out |= !(v < kFastBig64) || (v != 0.0 && v < kFastTiny64);  // outside_fast (fast_domain.h), spelled out: (a NaN fails the first test)
   }
   if (__builtin_amdgcn_ballot_w64(out) != 0 && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
 }

@@ -1,19 +1,15 @@
 // libnbody_hip — the direct-sum driver: the kernel configuration and workspace layout of a step, the mass classes, the
 // preparation / run split multi.hip shards over devices, the hipGraph replay of step pairs, and the direct entry points
-// of the C ABI (nbody_update_direct_f32, nbody_accel_direct_f32, nbody_direct_*_dev), and the f64 direct entry points
-// (nbody_update_direct_f64, nbody_accel_direct_f64), and the direct sum at arbitrary points (nbody_accel_direct_at_f32 / _f64),
-// and the tracers' share of a direct step.
-// Kernels: direct_kernels.hip, nearfar.hip, direct64.hip, direct_probe.hip, tracers.hip.
+// of the C ABI (nbody_update_direct_f32 / _f64, nbody_accel_direct_f32 / _f64, nbody_direct_*_dev).  The sum at points that are
+// not bodies (the probe call, the tracers' share of a step) is target_driver.hip.
+// Kernels: direct_kernels.hip, direct_mutual.hip, nearfar.hip, direct64.hip.
 #include <algorithm>
-#include <cmath>
 #include <cstdio>
 #include <vector>
 
 #include "direct64.h"
 #include "direct_kernels.h"
-#include "direct_probe.h"
 #include "driver.h"
-#include "tracers.h"
 
 using namespace nbody;
 
@@ -199,8 +195,7 @@ int direct_plan(nbody_ctx* c, int64_t n_src, const void* mass_all, float uniform
     return fail(c, NBODY_ERR_INVALID, "direct_step: bad target/source counts");
   if (arith < NBODY_ARITH_AUTO || arith > NBODY_ARITH_EXACT) return fail(c, NBODY_ERR_INVALID, "direct_step: bad arith");
   if (!ws || ws_bytes < direct_ws_bytes(n_src, n_tgt_max)) return fail(c, NBODY_ERR_INVALID, "direct_step: workspace too small");
-  // FAST's zero-distance bias needs clamp >= 2^-19 (HISTORY.md §4.1); smaller clamps always take EXACT.
-  if (arith != NBODY_ARITH_EXACT && !(clamp >= 1.9073486328125e-06f)) arith = NBODY_ARITH_EXACT;
+  arith = direct_arith_f32(arith, clamp);
   DirectPlan p;
   p.arith = arith;
   p.uni = uniform_mass > 0.f && lab_int("NBODY_DIRECT_NO_UNIFORM", 0) == 0;
@@ -383,106 +378,6 @@ int ctx_ensure_mass_classes(nbody_ctx* c) { return c && c->has_f32 ? ensure_mass
 
 }  // namespace nbody
 
-// ---- tracers (ctx.h, Tracers; kernels: tracers.hip and the probe call's FAST passes)
-// The tracers' share of one direct step, enqueued behind the bodies' kernels of that step and before its buffers swap: `pos` /
-// `mass` are the bodies at their pre-step positions, which the step's kernels only read.  Routing as nbody_accel_direct_at_*
-// (below), but nothing comes back to the host: tracer_mark reads the decision word the bodies' step has just written to the
-// workspace and every tracer's pre-step position, and leaves one mark per tracer (which of the two finishing kernels integrates
-// it) and a decision word of the tracers' own at the head of ctx->probe_ws, which gates the f32 FAST main pass (the f64 pass has
-// no gate: it runs for nothing in a step whose bodies left the f64 FAST domain).  The FAST partial sums go through ctx->probe_ws
-// in batches of the probe call's size, so the workspace is bounded whatever the number of tracers.
-namespace {
-constexpr size_t kTracerFlagBytes = 256;
-
-int tracer_batch(nbody_ctx* c, int64_t m, size_t elem, int64_t max_partial, int gsplit, int64_t* batch) {
-  const int64_t b = std::min<int64_t>(1 << 20, max_partial / gsplit) / 256 * 256;
-  *batch = std::min<int64_t>(m, std::max<int64_t>(b, 256));
-  return ensure_dev_bytes(c, c->probe_ws, c->probe_ws_bytes, kTracerFlagBytes + (size_t)*batch * elem * (size_t)gsplit);
-}
-
-int tracers_direct_f32(nbody_ctx* c, const float2* pos, const float* mass, float delta) {
-  const Tracers& tr = c->tracers;
-  if (tr.m == 0) return NBODY_OK;
-  const State<float>& s = c->sf;
-  const int64_t n = s.n, m = tr.m;
-  const float clamp = c->params.clamp;
-  int arith = c->params.arith;
-  if (arith != NBODY_ARITH_EXACT && !(clamp >= 1.9073486328125e-06f)) arith = NBODY_ARITH_EXACT;  // as direct_plan
-  float2 *tpos = (float2*)tr.pos, *tvel = (float2*)tr.vel;
-  if (arith == NBODY_ARITH_EXACT || n == 0) {
-    HIPCHK(c, launch_tracer_exact<float>(c->stream, pos, mass, n, tpos, tvel, m, clamp, delta, nullptr));
-    return NBODY_OK;
-  }
-  TracerRoute r;
-  if (arith == NBODY_ARITH_AUTO) {  // the step's own decision (kFlagState == 2: a body outside FAST's domain), and the per-tracer exception
-    r.word = (const int*)c->workspace;
-    r.word_kind = kTracerWordState;
-    r.per_target = 1;
-  }
-  const int g = probe_gsplit_f32(n);
-  int64_t batch = 0;
-  int rc = tracer_batch(c, m, sizeof(float2), (int64_t)1 << 23, g, &batch);
-  if (rc) return rc;
-  int* state = (int*)c->probe_ws;
-  float2* part = (float2*)((char*)c->probe_ws + kTracerFlagBytes);
-  HIPCHK(c, launch_tracer_mark<float>(c->stream, tpos, m, r, tr.mark, state));
-  for (int64_t b0 = 0; b0 < m; b0 += batch) {
-    const int64_t nb = std::min<int64_t>(batch, m - b0);
-    DirectArgs a{};
-    a.pos_all = tpos + b0;  // the tracers ...
-    a.src_pos = pos;        // ... and the bodies
-    a.mass_all = mass;
-    a.n_src = (int)n;
-    a.tgt_begin = 0;
-    a.n_tgt = (int)nb;
-    a.partial = part;
-    a.to_partial = 1;
-    a.clamp = clamp;
-    a.uniform_mass = s.uniform_mass > 0.f ? s.uniform_mass : 0.f;
-    a.flags = state;
-    a.run_state = 1;  // (tracer_mark wrote 2 when the step-level route is EXACT: the pass returns at once)
-    DirectConfig cfg;
-    cfg.tpt = 1;
-    cfg.gsplit = g;
-    cfg.use_asm = 2;  // the packed pass through LDS, with the clamp: the probe call's main pass
-    cfg.nearfar = false;
-    HIPCHK(c, launch_direct_fast(c->stream, a, cfg, false));
-    HIPCHK(c, launch_tracer_finish<float>(c->stream, part, g, nb, tpos + b0, tvel + b0, delta, tr.mark + b0));
-  }
-  if (r.per_target) HIPCHK(c, launch_tracer_exact<float>(c->stream, pos, mass, n, tpos, tvel, m, clamp, delta, tr.mark));  // the fix-up pass
-  return NBODY_OK;
-}
-
-int tracers_direct_f64(nbody_ctx* c, const double2* pos, const double* mass, double delta) {
-  const Tracers& tr = c->tracers;
-  if (tr.m == 0) return NBODY_OK;
-  const int64_t n = c->sd.n, m = tr.m;
-  const double clamp = (double)c->params.clamp;  // as direct64_step
-  double2 *tpos = (double2*)tr.pos, *tvel = (double2*)tr.vel;
-  if (!(c->params.arith == NBODY_ARITH_FAST && clamp > 0.0) || n == 0) {
-    HIPCHK(c, launch_tracer_exact<double>(c->stream, pos, mass, n, tpos, tvel, m, clamp, delta, nullptr));
-    return NBODY_OK;
-  }
-  TracerRoute r;
-  r.word = (const int*)c->workspace;  // the domain flag the f64 step has just scanned the bodies into
-  r.word_kind = kTracerWordDomain64;
-  r.per_target = 1;
-  const int g = probe_gsplit_f64(n);
-  int64_t batch = 0;
-  int rc = tracer_batch(c, m, sizeof(double2), (int64_t)1 << 22, g, &batch);
-  if (rc) return rc;
-  double2* part = (double2*)((char*)c->probe_ws + kTracerFlagBytes);
-  HIPCHK(c, launch_tracer_mark<double>(c->stream, tpos, m, r, tr.mark, (int*)c->probe_ws));
-  for (int64_t b0 = 0; b0 < m; b0 += batch) {
-    const int64_t nb = std::min<int64_t>(batch, m - b0);
-    HIPCHK(c, launch_probe_fast_pass_f64(c->stream, pos, mass, n, tpos + b0, nb, clamp, part));
-    HIPCHK(c, launch_tracer_finish<double>(c->stream, part, g, nb, tpos + b0, tvel + b0, delta, tr.mark + b0));
-  }
-  HIPCHK(c, launch_tracer_exact<double>(c->stream, pos, mass, n, tpos, tvel, m, clamp, delta, tr.mark));  // the fix-up pass
-  return NBODY_OK;
-}
-}  // namespace
-
 NB_API int nbody_update_direct_f32(nbody_ctx* c, float delta, int n_steps, nbody_counting* counter) {
   if (!c) return NBODY_ERR_INVALID;
   if (c->multi) return nbody::multi_update_direct(c, delta, n_steps, counter);
@@ -634,7 +529,7 @@ int direct64_step(nbody_ctx* c, double delta, bool integrate) {
   }
   a.delta = delta;
   a.clamp = (double)c->params.clamp;  // the f32 parameter widened, as the oracle's np.float32(clamp) -> T
-  const bool fast = c->params.arith == NBODY_ARITH_FAST && a.clamp > 0.0;  // (a NaN clamp fails the test too)
+  const bool fast = direct_fast_f64(c->params.arith, a.clamp);
   TimerScope ts(c->timer, c->stream);
   HIPCHK(c, launch_direct64(c->stream, a, fast, c->workspace, c->workspace_bytes));
   return NBODY_OK;
@@ -683,219 +578,4 @@ NB_API int nbody_accel_direct_f64(nbody_ctx* c, double* acc_xy) {
   HIPCHK(c, hipMemcpyAsync(acc_xy, s.acc, (size_t)s.n * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return NBODY_OK;
-}
-
-
-// ---- the direct sum at arbitrary points (nbody_accel_direct_at_*; kernels: direct_probe.hip, and the step's clamped FAST pass)
-// Routing, per call, from the bodies and the params alone; per target, from its own coordinates alone (include/nbody_hip.h):
-//   f32  EXACT, or a clamp below 2^-19, or AUTO with a body outside FAST's domain (what makes the step run direct_exact):
-//        every target EXACT.  Otherwise FAST — under AUTO a target outside FAST's domain takes its EXACT value.
-//   f64  EXACT unless FAST is asked for with a clamp > 0 and every body inside the f64 FAST domain; then FAST, a target
-//        outside that domain EXACT.
-// FAST f32 is the clamped packed pass of the step (direct_fast<1, *, false, 2>) over the bodies in row order, its source split
-// fixed by the number of bodies (probe_gsplit_f32); the clamp is in every pair, so no near/far decision depends on the targets.
-// Targets go through in batches: the workspace (ctx->probe_ws) is bounded whatever n_targets is.
-namespace {
-
-constexpr size_t kProbeFlagBytes = 256;
-
-bool fast_domain_f32(float x, float y) {
-  for (float v : {x, y}) {
-    const float a = std::fabs(v);
-    if (!(a < kFastBig) || (a != 0.f && a < kFastTiny)) return false;
-  }
-  return true;
-}
-bool fast_domain_f64(double x, double y) {
-  for (double v : {x, y}) {
-    const double a = std::fabs(v);
-    if (!(a < 0x1p100) || (a != 0.0 && a < 0x1p-300)) return false;
-  }
-  return true;
-}
-
-// The workspace of a call once its route is known: the flag word, a batch of targets and of results, and — FAST only (`gsplit`
-// > 0) — the batch's partial sums.  A batch holds at most 2^20 targets, and its partial sums at most `max_partial` entries (2^23
-// f32, 2^22 f64).  *batch receives the batch size.
-int probe_workspace(nbody_ctx* c, int64_t n_targets, size_t elem, int64_t max_partial, int gsplit, int64_t* batch) {
-  const int64_t b = std::min<int64_t>(1 << 20, max_partial / std::max(gsplit, 1)) / 256 * 256;
-  *batch = std::min<int64_t>(n_targets, std::max<int64_t>(b, 256));
-  const size_t need = kProbeFlagBytes + (size_t)*batch * elem * (2 + (size_t)std::max(gsplit, 0));
-  return ensure_dev_bytes(c, c->probe_ws, c->probe_ws_bytes, need);
-}
-
-// The device flag word of a body scan, read back: 0 all inside the domain.
-int read_flag(nbody_ctx* c, const int* flag_dev, int* out) {
-  HIPCHK(c, hipMemcpyAsync(out, flag_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return NBODY_OK;
-}
-
-// Runs `pass(d_tgt, n, d_out, d_partial)` over the targets `idx` (all of them when idx is null) batch by batch and scatters the
-// results into acc.
-template <class T2, class Pass>
-int probe_batches(nbody_ctx* c, int64_t m, const T2* tgt, const std::vector<int64_t>* idx, T2* acc, int64_t batch, Pass pass) {
-  char* ws = (char*)c->probe_ws;
-  T2* d_tgt = (T2*)(ws + kProbeFlagBytes);
-  T2* d_out = d_tgt + batch;
-  T2* d_part = d_out + batch;
-  std::vector<T2> gather, result;
-  const int64_t total = idx ? (int64_t)idx->size() : m;
-  for (int64_t b0 = 0; b0 < total; b0 += batch) {
-    const int64_t nb = std::min<int64_t>(batch, total - b0);
-    const T2* src = tgt + b0;
-    T2* dst = acc + b0;
-    if (idx) {
-      gather.resize((size_t)nb);
-      result.resize((size_t)nb);
-      for (int64_t k = 0; k < nb; ++k) gather[(size_t)k] = tgt[(*idx)[(size_t)(b0 + k)]];
-      src = gather.data();
-      dst = result.data();
-    }
-    HIPCHK(c, hipMemcpyAsync(d_tgt, src, (size_t)nb * sizeof(T2), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, pass(d_tgt, nb, d_out, d_part));
-    HIPCHK(c, hipMemcpyAsync(dst, d_out, (size_t)nb * sizeof(T2), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (idx)
-      for (int64_t k = 0; k < nb; ++k) acc[(*idx)[(size_t)(b0 + k)]] = result[(size_t)k];
-  }
-  return NBODY_OK;
-}
-
-int accel_at_f32(nbody_ctx* c, int64_t m, const float2* tgt, float2* acc) {
-  State<float>& s = c->sf;
-  const int64_t n = s.n;
-  if (n == 0) {
-    std::fill(acc, acc + m, make_float2(0.f, 0.f));
-    return NBODY_OK;
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  const float clamp = c->params.clamp;
-  int arith = c->params.arith;
-  if (arith != NBODY_ARITH_EXACT && !(clamp >= 1.9073486328125e-06f)) arith = NBODY_ARITH_EXACT;  // as direct_plan
-  const int g = probe_gsplit_f32(n);
-  auto& st = s.set[s.cur];
-  int rc = NBODY_OK;
-  if (arith == NBODY_ARITH_AUTO) {  // the step's hazard scan over the bodies
-    rc = ensure_dev_bytes(c, c->probe_ws, c->probe_ws_bytes, kProbeFlagBytes);
-    if (rc) return rc;
-    int* flag = (int*)c->probe_ws;
-    HIPCHK(c, hipMemsetAsync(flag, 0, sizeof(int), c->stream));
-    HIPCHK(c, launch_hazard_scan(c->stream, (const float*)st.pos, 2 * n, flag));
-    int bad = 0;
-    rc = read_flag(c, flag, &bad);
-    if (rc) return rc;
-    if (bad) arith = NBODY_ARITH_EXACT;
-  }
-  int64_t batch = 0;
-  rc = probe_workspace(c, m, sizeof(float2), (int64_t)1 << 23, arith == NBODY_ARITH_EXACT ? 0 : g, &batch);
-  if (rc) return rc;
-  int* flag = (int*)c->probe_ws;
-  auto exact = [&](const float2* d_tgt, int64_t nb, float2* d_out, float2*) {
-    return launch_probe_exact_f32(c->stream, st.pos, st.mass, n, d_tgt, nb, clamp, d_out);
-  };
-  if (arith == NBODY_ARITH_EXACT) return probe_batches(c, m, tgt, nullptr, acc, batch, exact);
-  auto fast = [&](const float2* d_tgt, int64_t nb, float2* d_out, float2* d_part) {
-    DirectArgs a{};
-    a.pos_all = d_tgt;  // the targets ...
-    a.src_pos = st.pos;  // ... and the bodies
-    a.mass_all = st.mass;
-    a.n_src = (int)n;
-    a.tgt_begin = 0;
-    a.n_tgt = (int)nb;
-    a.partial = d_part;
-    a.to_partial = 1;
-    a.clamp = clamp;
-    a.uniform_mass = s.uniform_mass > 0.f ? s.uniform_mass : 0.f;
-    a.flags = flag;
-    a.run_state = -1;
-    DirectConfig cfg;
-    cfg.tpt = 1;
-    cfg.gsplit = g;
-    cfg.use_asm = 2;  // the packed pass through LDS, with the clamp
-    cfg.nearfar = false;
-    hipError_t e = launch_direct_fast(c->stream, a, cfg, false);
-    return e == hipSuccess ? launch_probe_finish_f32(c->stream, d_part, g, nb, d_out) : e;
-  };
-  rc = probe_batches(c, m, tgt, nullptr, acc, batch, fast);
-  if (rc || arith != NBODY_ARITH_AUTO) return rc;
-  std::vector<int64_t> odd;  // AUTO: the targets outside FAST's domain take their EXACT values
-  for (int64_t i = 0; i < m; ++i)
-    if (!fast_domain_f32(tgt[i].x, tgt[i].y)) odd.push_back(i);
-  return odd.empty() ? NBODY_OK : probe_batches(c, m, tgt, &odd, acc, batch, exact);
-}
-
-int accel_at_f64(nbody_ctx* c, int64_t m, const double2* tgt, double2* acc) {
-  State<double>& s = c->sd;
-  const int64_t n = s.n;
-  if (n == 0) {
-    std::fill(acc, acc + m, double2{0.0, 0.0});
-    return NBODY_OK;
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  const double clamp = (double)c->params.clamp;  // the f32 parameter widened, as direct64_step
-  bool fast = c->params.arith == NBODY_ARITH_FAST && clamp > 0.0;
-  auto& st = s.set[s.cur];
-  int rc = NBODY_OK;
-  if (fast) {  // the f64 step's domain scan over the bodies
-    rc = ensure_dev_bytes(c, c->probe_ws, c->probe_ws_bytes, kProbeFlagBytes);
-    if (rc) return rc;
-    int* flag = (int*)c->probe_ws;
-    HIPCHK(c, hipMemsetAsync(flag, 0, sizeof(int), c->stream));
-    HIPCHK(c, launch_probe_domain_f64(c->stream, (const double*)st.pos, 2 * n, flag));
-    int bad = 0;
-    rc = read_flag(c, flag, &bad);
-    if (rc) return rc;
-    if (bad) fast = false;
-  }
-  int64_t batch = 0;
-  rc = probe_workspace(c, m, sizeof(double2), (int64_t)1 << 22, fast ? probe_gsplit_f64(n) : 0, &batch);
-  if (rc) return rc;
-  auto pass = [&](bool f) {
-    return [&, f](const double2* d_tgt, int64_t nb, double2* d_out, double2* d_part) {
-      return launch_probe_f64(c->stream, st.pos, st.mass, n, d_tgt, nb, clamp, f, d_part, d_out);
-    };
-  };
-  rc = probe_batches(c, m, tgt, nullptr, acc, batch, pass(fast));
-  if (rc || !fast) return rc;
-  std::vector<int64_t> odd;
-  for (int64_t i = 0; i < m; ++i)
-    if (!fast_domain_f64(tgt[i].x, tgt[i].y)) odd.push_back(i);
-  return odd.empty() ? NBODY_OK : probe_batches(c, m, tgt, &odd, acc, batch, pass(false));
-}
-
-int accel_at_check(nbody_ctx* c, bool f64, int64_t m, const void* tgt, const void* acc) {
-  const char* what = f64 ? "accel_direct_at_f64" : "accel_direct_at_f32";
-  if (m < 0) return fail(c, NBODY_ERR_INVALID, std::string(what) + ": n_targets < 0");
-  if (m > 0 && (!tgt || !acc)) return fail(c, NBODY_ERR_INVALID, std::string(what) + ": target_xy or acc_xy is NULL");
-  if (f64 ? !c->has_f64 : !c->has_f32)
-    return fail(c, NBODY_ERR_INVALID, std::string(what) + ((f64 ? c->has_f32 : c->has_f64)
-                                                               ? ": the context holds particles of the other precision"
-                                                               : ": no particles uploaded"));
-  return NBODY_OK;
-}
-
-}  // namespace
-
-namespace nbody {
-int ctx_accel_direct_at(nbody_ctx* c, bool f64, int64_t n_targets, const void* target_xy, void* acc_xy) {
-  if (n_targets == 0) return NBODY_OK;
-  return f64 ? accel_at_f64(c, n_targets, (const double2*)target_xy, (double2*)acc_xy)
-             : accel_at_f32(c, n_targets, (const float2*)target_xy, (float2*)acc_xy);
-}
-}  // namespace nbody
-
-NB_API int nbody_accel_direct_at_f32(nbody_ctx* c, int64_t n_targets, const float* target_xy, float* acc_xy) {
-  if (!c) return NBODY_ERR_INVALID;
-  int rc = accel_at_check(c, false, n_targets, target_xy, acc_xy);
-  if (rc || n_targets == 0) return rc;
-  if (c->multi) return multi_accel_direct_at(c, false, n_targets, target_xy, acc_xy);
-  return ctx_accel_direct_at(c, false, n_targets, target_xy, acc_xy);
-}
-NB_API int nbody_accel_direct_at_f64(nbody_ctx* c, int64_t n_targets, const double* target_xy, double* acc_xy) {
-  if (!c) return NBODY_ERR_INVALID;
-  int rc = accel_at_check(c, true, n_targets, target_xy, acc_xy);
-  if (rc || n_targets == 0) return rc;
-  if (c->multi) return multi_accel_direct_at(c, true, n_targets, target_xy, acc_xy);
-  return ctx_accel_direct_at(c, true, n_targets, target_xy, acc_xy);
 }

@@ -1,4 +1,4 @@
-// Internal: the host plumbing the single-device driver's translation units share (capi.hip, direct_driver.hip,
+// Internal: the host plumbing the single-device driver's translation units share (capi.hip, direct_driver.hip, target_driver.hip,
 // tree_build_driver.hip, tree_driver.hip, caller_tree.hip, snapshot.hip) — error reporting, device buffers, and the
 // bookkeeping every tree build and walk repeats.  Not part of the C ABI; multi.hip needs only ctx.h.
 #pragma once
@@ -9,6 +9,7 @@
 
 #include "bvh_build.h"
 #include "ctx.h"
+#include "fast_domain.h"
 #include "tree_kernels.h"
 
 #define NB_API extern "C" __attribute__((visibility("default")))
@@ -102,6 +103,13 @@ template <class T> WalkArgs<T> walk_args(const nbody_ctx* c, const State<T>& s, 
   return w;
 }
 
+// The arithmetic a direct sum runs in under the context's params.  f32: FAST and AUTO need the clamp floor of fast_domain.h (a
+// smaller clamp, or a NaN, takes EXACT).  f64: FAST only where it is asked for, with a clamp > 0 (a NaN fails the test too).
+inline int direct_arith_f32(int arith, float clamp) {
+  return arith != NBODY_ARITH_EXACT && !(clamp >= kFastClampFloor) ? (int)NBODY_ARITH_EXACT : arith;
+}
+inline bool direct_fast_f64(int arith, double clamp) { return arith == NBODY_ARITH_FAST && clamp > 0.0; }
+
 // ---- shared between the translation units
 void free_snapshot(nbody_ctx* c);  // snapshot.hip
 void free_delta(nbody_ctx* c);
@@ -111,6 +119,10 @@ template <class T> int tree_build_phase(nbody_ctx* c, State<T>& s, int kind);
 template <class T> int download_tree(nbody_ctx* c, State<T>& s);
 template <class T>  // tree_driver.hip
 int accel_built_tree(nbody_ctx* c, State<T>& s, int kind, int64_t n_targets, const T* target_xy, T* acc_xy);
+// target_driver.hip: the tracers' share of one direct step, enqueued behind the bodies' kernels of that step and before its buffers
+// swap (`pos` / `mass`: the bodies at their pre-step positions)
+int tracers_direct_f32(nbody_ctx* c, const float2* pos, const float* mass, float delta);
+int tracers_direct_f64(nbody_ctx* c, const double2* pos, const double* mass, double delta);
 
 }  // namespace nbody
 

@@ -66,6 +66,7 @@ def main():
             peak = PEAK_F64_TFLOPS if dt == np.float64 else PEAK_F32_TFLOPS
             print(json.dumps({"case": name, "bodies": n, "targets": m, "arith": arith, "masses": masses,
                               "ms_median": round(1e3 * s, 3), "ms_min": round(1e3 * min(times), 3),
+                              "ms_runs": [round(1e3 * t, 3) for t in times],
                               "pairs_per_s": float(f"{pairs / s:.4g}"), "tflops": round(tflops, 2),
                               "frac_of_peak": round(tflops / peak, 3), "peak_tflops": peak,
                               "timing": "host clock around the synchronous call (includes target upload, result download)"}),
