@@ -5,6 +5,7 @@
 
 #include <cstdlib>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "common.h"
@@ -100,11 +101,29 @@ struct Tracers {
 // The `uniform_mass` argument of the direct step for this state: > 0 all equal, < 0 all equal to its magnitude but a few, 0 neither.
 template <class T> inline float direct_mass_hint(const State<T>& s) { return s.uniform_mass > 0.f ? s.uniform_mass : -s.sparse_base; }
 
+// A direct step as ctx_direct_prep sees it, and what one ctx_direct_run over a block of its targets adds.  `n_tgt_total`: all targets this
+// device computes in the step (decides whether the near/far split pays); `n_tgt_max`: the largest block of one run (sizes the workspace).
+struct DirectStep {
+  hipStream_t stream = nullptr;
+  int64_t n_src = 0;
+  const void *pos_all = nullptr, *mass_all = nullptr;
+  float uniform_mass = 0.f, clamp = 0.f;  // (uniform_mass: direct_mass_hint())
+  int arith = 0;
+  int64_t n_tgt_total = 0, n_tgt_max = 0;
+  void* ws = nullptr;
+  size_t ws_bytes = 0;
+};
+struct DirectBlock {
+  int64_t tgt_begin = 0, n_tgt = 0;
+  void *vel = nullptr, *pos_out = nullptr, *acc_out = nullptr;  // rows of the block's first target
+  float delta = 0.f;
+  nbody_timer* timer = nullptr;
+};
+
 // Two consecutive direct steps (A -> B -> A position buffers) captured once as a hipGraph and replayed: a small-N step
 // is ~15 launches (hazard scan, near/far split, gated kernels), i.e. launch-bound (N = 1024: 78 us per eager step
-// against 13 us of kernels).  The graph is rebuilt when anything it baked in changes.
-struct DirectGraph {
-  hipGraphExec_t exec = nullptr;
+// against 13 us of kernels).  The graph is rebuilt when anything it baked in changes: its key.
+struct DirectGraphKey {
   int64_t n = -1;
   const void *pos_a = nullptr, *pos_b = nullptr, *vel = nullptr, *mass = nullptr, *ws = nullptr;
   float delta = 0.f, clamp = 0.f, uniform = 0.f;
@@ -114,10 +133,16 @@ struct DirectGraph {
   bool cls_usable = false;
   const void *cls_rank = nullptr, *cls_tile_mass = nullptr;
   std::string env;  // the NBODY_DIRECT_* switches read at capture time
+  auto tied() const { return std::tie(n, pos_a, pos_b, vel, mass, ws, delta, clamp, uniform, arith, row_epoch, cls_usable, cls_rank, cls_tile_mass, env); }
+  bool operator==(const DirectGraphKey& o) const { return tied() == o.tied(); }
+};
+struct DirectGraph {
+  hipGraphExec_t exec = nullptr;
+  DirectGraphKey key;
   void reset() {
     if (exec) (void)hipGraphExecDestroy(exec);
     exec = nullptr;
-    n = -1;
+    key = DirectGraphKey{};
   }
 };
 inline std::string direct_env_signature() {
@@ -226,11 +251,8 @@ int ctx_import_rows(nbody_ctx* c, int64_t n_rows, const void* rows, const void* 
 size_t ctx_direct_ws_bytes(int64_t n_src, int64_t n_tgt);
 int ctx_ensure_workspace(nbody_ctx* c, size_t bytes);
 int ctx_ensure_mass_classes(nbody_ctx* c);  // State::MassClasses of the f32 rows, for the direct steps that follow
-int ctx_direct_prep(nbody_ctx* c, hipStream_t stream, int64_t n_src, const void* pos_all, const void* mass_all, float uniform_mass,
-                    int64_t n_tgt_total, int64_t n_tgt_max, float clamp, int arith, void* ws, size_t ws_bytes);
-int ctx_direct_run(nbody_ctx* c, hipStream_t stream, int64_t n_src, const void* pos_all, const void* mass_all, float uniform_mass,
-                   int64_t tgt_begin, int64_t n_tgt, void* vel, void* pos_out, void* acc_out, float delta, float clamp, int arith,
-                   int64_t n_tgt_total, int64_t n_tgt_max, void* ws, size_t ws_bytes, nbody_timer* timer);
+int ctx_direct_prep(nbody_ctx* c, const DirectStep& step);  // decides, on the stream, which kernels of this step do the work
+int ctx_direct_run(nbody_ctx* c, const DirectStep& step, const DirectBlock& block);  // force + integration of one block under that decision
 // nbody_accel_direct_at_* on one device, arguments checked, n_targets > 0 (target_driver.hip)
 int ctx_accel_direct_at(nbody_ctx* c, bool f64, int64_t n_targets, const void* target_xy, void* acc_xy);
 // ---- multi.hip (`front` is the handle nbody_create_multi returned)

@@ -8,7 +8,7 @@
 #include <vector>
 
 #include "direct64.h"
-#include "direct_kernels.h"
+#include "direct_layout.h"
 #include "driver.h"
 
 using namespace nbody;
@@ -17,7 +17,7 @@ namespace nbody {
 namespace {
 
 // How the direct kernel covers (n_tgt x n_src): enough waves to fill 256 CUs x 4 SIMDs x 8 waves.
-DirectConfig choose_direct_config(int64_t n_src, int64_t n_tgt, bool uniform = true) {
+DirectConfig choose_direct_config(int64_t n_src, int64_t n_tgt) {
   DirectConfig c;
   c.use_asm = lab_int("NBODY_DIRECT_ASM", 4);
   // near/far split: 0.05 ms (65 536 bodies) to 0.16 ms (1 M) of preparation per step against 10 % of the pair work: it pays
@@ -27,7 +27,6 @@ DirectConfig choose_direct_config(int64_t n_src, int64_t n_tgt, bool uniform = t
   c.nearfar = nf == 2 || (nf == 1 && (double)n_src * (double)n_tgt >= 4294967296.0);
   // measured at N = 1M (profiles/r01_direct_mass_variants.txt): 1 target/thread with the hand-ordered block wins for
   // equal masses (44.0 %) and for per-body masses (39.8 % vs 36.1 % for 2 targets/thread)
-  (void)uniform;
   c.tpt = lab_int("NBODY_DIRECT_TPT", 1);
   if (c.tpt != 1 && c.tpt != 2) c.tpt = 1;
   // 256 CUs x 32 wave slots hold 8192 waves; several rounds of waves balance the tail, so the sources are split
@@ -58,12 +57,7 @@ constexpr size_t kFlagBytes = 256;
 // ceil(want_waves / (4 ceil(n/64))) <= 16, so gsplit(n) n < 2097152 + n and <= 16 n; ctx_direct_run clamps what an
 // environment override could still push past it.
 size_t direct_partial_bytes(int64_t n_src, int64_t n_tgt) {
-  size_t partial = 0;
-  for (bool uni : {false, true}) {
-    DirectConfig c = choose_direct_config(n_src, n_tgt, uni);
-    size_t p = (size_t)c.gsplit * (size_t)n_tgt * sizeof(float2);
-    if (p > partial) partial = p;
-  }
+  size_t partial = (size_t)choose_direct_config(n_src, n_tgt).gsplit * (size_t)n_tgt * sizeof(float2);
   size_t any_block = (size_t)std::min<int64_t>(16 * n_tgt, 2097152 + n_tgt) * sizeof(float2);
   if (any_block > partial) partial = any_block;
   const int64_t g_l2 = (n_src + 262143) / 262144;  // (the L2 rule of choose_direct_config holds for every block size)
@@ -75,17 +69,24 @@ size_t direct_partial_bytes(int64_t n_src, int64_t n_tgt) {
 // would pass 0.4 % of the step; untested).  Its strip buffers then follow the near/far scratch in the workspace.
 constexpr int64_t kMutualMinN = 393216;
 constexpr int64_t kMutualMaxN = 4194304;
-bool mutual_sizes(int64_t n_src, int64_t n_tgt) {
-  return n_tgt == n_src && n_src >= lab_int("NBODY_DIRECT_MUTUAL_MIN_N", (int)kMutualMinN) && n_src <= kMutualMaxN;
-}
-size_t mutual_offset(int64_t n_src, int64_t n_tgt) {
-  return (kFlagBytes + direct_partial_bytes(n_src, n_tgt) + nearfar_layout(n_src).total + 255) & ~(size_t)255;
-}
-size_t direct_ws_bytes(int64_t n_src, int64_t n_tgt) {
-  const size_t base = kFlagBytes + direct_partial_bytes(n_src, n_tgt) + nearfar_layout(n_src).total;
-  return mutual_sizes(n_src, n_tgt) ? mutual_offset(n_src, n_tgt) + mutual_area_bytes(n_src) : base;
+}  // namespace
+
+// Flag words, partial sums, near/far scratch, and the mutual area where the pass can engage: in this order.
+DirectLayout direct_layout(int64_t n_src, int64_t n_tgt_max) {
+  DirectLayout L;
+  L.partial = DirectLayout::flags + kFlagBytes;
+  L.partial_bytes = direct_partial_bytes(n_src, n_tgt_max);
+  L.nearfar = L.partial + L.partial_bytes;
+  L.nf = nearfar_layout(n_src);
+  L.total = L.nearfar + L.nf.total;
+  if (n_tgt_max == n_src && n_src >= lab_int("NBODY_DIRECT_MUTUAL_MIN_N", (int)kMutualMinN) && n_src <= kMutualMaxN) {
+    L.mutual = (L.total + 255) & ~(size_t)255;
+    L.total = L.mutual + mutual_area_bytes(n_src);
+  }
+  return L;
 }
 
+namespace {
 // Mass classes of the context's f32 rows in their current order (ctx.h, State::MassClasses): built on the host from the
 // weights (static between uploads; only the row order moves, with the tree builds), cached until the rows are permuted.
 // Classes are taken in ascending weight, bodies inside a class in ascending row: everything downstream stays a function
@@ -174,9 +175,8 @@ const State<float>::MassClasses* classes_for(const nbody_ctx* c, int64_t n_src, 
 }
 
 // A direct step = one preparation over ALL positions (hazard scan, near/far split, the decision word) followed by one
-// or more runs, each over a block of targets.  `n_tgt_total` (all targets this device computes in the step) decides
-// whether the near/far split pays; `n_tgt_max` (the largest block of one run) sizes the partial-sum area, so that
-// preparation and runs agree on the workspace layout.
+// or more runs, each over a block of targets (ctx.h: DirectStep, DirectBlock).  The plan is what both derive from the step:
+// it carries the workspace layout, so they cannot disagree on it.
 struct DirectPlan {
   int arith = 0;
   bool uni = false;
@@ -187,129 +187,122 @@ struct DirectPlan {
   bool stream_m = false; // free per-body masses through the streamed main pass: the far copy carries 1 / mass in slot order
   bool mutual = false;   // the mutual main pass (direct_mutual.hip): each far pair once, equal-mass rate, one block of all targets
   int use_hazard = 0;
-  size_t partial_bytes = 0;
+  DirectLayout L;
 };
-int direct_plan(nbody_ctx* c, int64_t n_src, const void* mass_all, float uniform_mass, int64_t n_tgt_total, int64_t n_tgt_max, float clamp,
-                int arith, const void* ws, size_t ws_bytes, DirectPlan* out) {
-  if (n_src < 0 || n_tgt_total < 0 || n_tgt_max < 0 || n_tgt_max > n_tgt_total || n_tgt_total > n_src || n_src > 0x7fffffffLL)
+int direct_plan(nbody_ctx* c, const DirectStep& s, DirectPlan* out) {  // (checks the step's own arguments)
+  if (s.n_src < 0 || s.n_tgt_total < 0 || s.n_tgt_max < 0 || s.n_tgt_max > s.n_tgt_total || s.n_tgt_total > s.n_src || s.n_src > 0x7fffffffLL)
     return fail(c, NBODY_ERR_INVALID, "direct_step: bad target/source counts");
-  if (arith < NBODY_ARITH_AUTO || arith > NBODY_ARITH_EXACT) return fail(c, NBODY_ERR_INVALID, "direct_step: bad arith");
-  if (!ws || ws_bytes < direct_ws_bytes(n_src, n_tgt_max)) return fail(c, NBODY_ERR_INVALID, "direct_step: workspace too small");
-  arith = direct_arith_f32(arith, clamp);
+  if (s.arith < NBODY_ARITH_AUTO || s.arith > NBODY_ARITH_EXACT) return fail(c, NBODY_ERR_INVALID, "direct_step: bad arith");
   DirectPlan p;
-  p.arith = arith;
-  p.uni = uniform_mass > 0.f && lab_int("NBODY_DIRECT_NO_UNIFORM", 0) == 0;
+  p.L = direct_layout(s.n_src, s.n_tgt_max);
+  if (!s.ws || s.ws_bytes < p.L.total) return fail(c, NBODY_ERR_INVALID, "direct_step: workspace too small");
+  p.arith = direct_arith_f32(s.arith, s.clamp);
+  p.uni = s.uniform_mass > 0.f && lab_int("NBODY_DIRECT_NO_UNIFORM", 0) == 0;
   {
-    const DirectConfig c0 = choose_direct_config(n_src, n_tgt_total, p.uni);
+    const DirectConfig c0 = choose_direct_config(s.n_src, s.n_tgt_total);
     p.nearfar = c0.nearfar;
     p.couples = c0.nearfar && c0.use_asm >= 2 && c0.tpt == 1;
   }
   // uniform_mass < 0: every mass is -uniform_mass except a sparse set; the split hands those to direct_finish, so the
   // main pass runs at the equal-mass rate.  Without the split (small problems) the per-body-mass kernel is used.
-  if (uniform_mass < 0.f && p.nearfar && lab_int("NBODY_DIRECT_NO_UNIFORM", 0) == 0 && lab_int("NBODY_DIRECT_NO_SPARSE", 0) == 0)
-    p.sparse_base = -uniform_mass;
-  if (!p.uni && p.sparse_base == 0.f && p.nearfar) p.classes = classes_for(c, n_src, mass_all);
+  if (s.uniform_mass < 0.f && p.nearfar && lab_int("NBODY_DIRECT_NO_UNIFORM", 0) == 0 && lab_int("NBODY_DIRECT_NO_SPARSE", 0) == 0)
+    p.sparse_base = -s.uniform_mass;
+  if (!p.uni && p.sparse_base == 0.f && p.nearfar) p.classes = classes_for(c, s.n_src, s.mass_all);
   p.stream_m = !p.uni && p.sparse_base == 0.f && !p.classes && p.couples && lab_int("NBODY_DIRECT_ASM", 4) >= 3;
   // lab NBODY_DIRECT_ASM: 4 (default) = mutual where it applies, else as 3
-  p.mutual = arith != NBODY_ARITH_EXACT && p.couples && (p.uni || p.sparse_base > 0.f) && !p.classes && n_tgt_max == n_tgt_total &&
-             mutual_sizes(n_src, n_tgt_total) && lab_int("NBODY_DIRECT_ASM", 4) >= 4;
-  p.use_hazard = arith == NBODY_ARITH_AUTO;
-  p.partial_bytes = direct_partial_bytes(n_src, n_tgt_max);
+  p.mutual = p.arith != NBODY_ARITH_EXACT && p.couples && (p.uni || p.sparse_base > 0.f) && !p.classes && s.n_tgt_max == s.n_tgt_total &&
+             p.L.mutual != DirectLayout::kNoMutual && lab_int("NBODY_DIRECT_ASM", 4) >= 4;
+  p.use_hazard = p.arith == NBODY_ARITH_AUTO;
   *out = p;
   return NBODY_OK;
+}
+
+// The argument checks of a block, each written once.  `whole`: the block is the whole step (nbody_direct_step_dev), where a source
+// count beyond int is a bad range too.
+int check_range(nbody_ctx* c, const DirectStep& s, const DirectBlock& b, bool whole) {
+  if (b.n_tgt < 0 || b.tgt_begin < 0 || b.tgt_begin + b.n_tgt > s.n_src || b.n_tgt > s.n_tgt_max || (whole && s.n_src > 0x7fffffffLL))
+    return fail(c, NBODY_ERR_INVALID, "direct_step: bad target/source range");
+  return NBODY_OK;
+}
+int check_arrays(nbody_ctx* c, const DirectStep& s, const DirectBlock* b) {  // b == null: the preparation, which has no outputs
+  if (!s.pos_all || !s.mass_all) return fail(c, NBODY_ERR_INVALID, "direct_step: null pos_all/mass_all");
+  if (b && (b->vel == nullptr) != (b->pos_out == nullptr))
+    return fail(c, NBODY_ERR_INVALID, "direct_step: vel and pos_out must both be given or both be NULL");
+  return !b || b->vel || b->acc_out ? NBODY_OK : fail(c, NBODY_ERR_INVALID, "direct_step: nothing to compute");
 }
 
 }  // namespace
 
 // Decides, on the stream, which kernels of this step do the work (flags[kFlagState]).
-int ctx_direct_prep(nbody_ctx* c, hipStream_t stream, int64_t n_src, const void* pos_all, const void* mass_all, float uniform_mass,
-                    int64_t n_tgt_total, int64_t n_tgt_max, float clamp, int arith, void* ws, size_t ws_bytes) {
+int ctx_direct_prep(nbody_ctx* c, const DirectStep& s) {
   DirectPlan p;
-  int rc = direct_plan(c, n_src, mass_all, uniform_mass, n_tgt_total, n_tgt_max, clamp, arith, ws, ws_bytes, &p);
+  int rc = direct_plan(c, s, &p);
+  if (rc || s.n_tgt_total == 0 || p.arith == NBODY_ARITH_EXACT) return rc;
+  rc = check_arrays(c, s, nullptr);
   if (rc) return rc;
-  if (n_tgt_total == 0 || p.arith == NBODY_ARITH_EXACT) return NBODY_OK;
-  if (!pos_all || !mass_all) return fail(c, NBODY_ERR_INVALID, "direct_step: null pos_all/mass_all");
-  int* flags = (int*)ws;
-  HIPCHK(c, hipMemsetAsync(flags, 0, kFlagBytes, stream));
-  if (p.use_hazard && !(p.nearfar && n_src > 0))  // (with the split on, nf_insert checks the positions as it reads them)
-    HIPCHK(c, launch_hazard_scan(stream, (const float*)pos_all, 2 * n_src, flags));
+  int* flags = direct_flags(s.ws);
+  HIPCHK(c, hipMemsetAsync(flags, 0, kFlagBytes, s.stream));
+  if (p.use_hazard && !(p.nearfar && s.n_src > 0))  // (with the split on, nf_insert checks the positions as it reads them)
+    HIPCHK(c, launch_hazard_scan(s.stream, (const float*)s.pos_all, 2 * s.n_src, flags));
   if (p.nearfar) {
-    char* nf_scratch = (char*)ws + kFlagBytes + p.partial_bytes;
-    NearFarLayout L = nearfar_layout(n_src);
-    const float2* pos_far = nullptr;
+    const float2* pos_far = nullptr;  // (where launch_nearfar says it put them: the places the layout's accessors name)
     const uint32_t* near_list = nullptr;
     const float* minv_far = nullptr;
-    HIPCHK(c, launch_nearfar(stream, (const float2*)pos_all, (const float*)mass_all, p.sparse_base, (int)n_src, clamp, p.use_hazard, flags,
-                             nf_scratch, L, &pos_far, &near_list, p.classes ? p.classes->rank : nullptr,
+    HIPCHK(c, launch_nearfar(s.stream, (const float2*)s.pos_all, (const float*)s.mass_all, p.sparse_base, (int)s.n_src, s.clamp, p.use_hazard,
+                             flags, direct_nearfar(s.ws, p.L), p.L.nf, &pos_far, &near_list, p.classes ? p.classes->rank : nullptr,
                              p.classes ? p.classes->pad_slots : nullptr, p.classes ? p.classes->n_pad_slots : 0, p.couples,
                              p.stream_m ? &minv_far : nullptr));
   } else {
-    HIPCHK(c, launch_decide_simple(stream, p.use_hazard, flags));
+    HIPCHK(c, launch_decide_simple(s.stream, p.use_hazard, flags));
   }
   return NBODY_OK;
 }
 
-// Force + integration for the targets [tgt_begin, tgt_begin + n_tgt) under the decision ctx_direct_prep left in `ws`.
-int ctx_direct_run(nbody_ctx* c, hipStream_t stream, int64_t n_src, const void* pos_all, const void* mass_all, float uniform_mass,
-                   int64_t tgt_begin, int64_t n_tgt, void* vel, void* pos_out, void* acc_out, float delta, float clamp, int arith,
-                   int64_t n_tgt_total, int64_t n_tgt_max, void* ws, size_t ws_bytes, nbody_timer* timer) {
-  if (n_tgt < 0 || tgt_begin < 0 || tgt_begin + n_tgt > n_src || n_tgt > n_tgt_max)
-    return fail(c, NBODY_ERR_INVALID, "direct_step: bad target/source range");
+// Force + integration for the block's targets under the decision ctx_direct_prep left in the workspace.
+int ctx_direct_run(nbody_ctx* c, const DirectStep& s, const DirectBlock& b) {
+  int rc = check_range(c, s, b, false);
   DirectPlan p;
-  int rc = direct_plan(c, n_src, mass_all, uniform_mass, n_tgt_total, n_tgt_max, clamp, arith, ws, ws_bytes, &p);
+  if (!rc) rc = direct_plan(c, s, &p);
+  if (rc || b.n_tgt == 0) return rc;
+  rc = check_arrays(c, s, &b);
   if (rc) return rc;
-  if (n_tgt == 0) return NBODY_OK;
-  if (!pos_all || !mass_all) return fail(c, NBODY_ERR_INVALID, "direct_step: null pos_all/mass_all");
-  if ((vel == nullptr) != (pos_out == nullptr))
-    return fail(c, NBODY_ERR_INVALID, "direct_step: vel and pos_out must both be given or both be NULL");
-  if (!vel && !acc_out) return fail(c, NBODY_ERR_INVALID, "direct_step: nothing to compute");
 
-  DirectConfig cfg = choose_direct_config(n_src, n_tgt, p.uni);
+  DirectConfig cfg = choose_direct_config(s.n_src, b.n_tgt);
   cfg.nearfar = p.nearfar;
-  while (cfg.gsplit > 1 && (size_t)cfg.gsplit * (size_t)n_tgt * sizeof(float2) > p.partial_bytes) --cfg.gsplit;
-  if ((size_t)cfg.gsplit * (size_t)n_tgt * sizeof(float2) > p.partial_bytes)
+  while (cfg.gsplit > 1 && (size_t)cfg.gsplit * (size_t)b.n_tgt * sizeof(float2) > p.L.partial_bytes) --cfg.gsplit;
+  if ((size_t)cfg.gsplit * (size_t)b.n_tgt * sizeof(float2) > p.L.partial_bytes)
     return fail(c, NBODY_ERR_INVALID, "direct_step: the partial sums of this block do not fit the workspace's layout");
-  int* flags = (int*)ws;
   DirectArgs a{};
-  a.pos_all = (const float2*)pos_all;
+  a.pos_all = (const float2*)s.pos_all;
   a.src_pos = a.pos_all;
-  a.mass_all = (const float*)mass_all;
-  a.n_src = (int)n_src;
-  a.tgt_begin = (int)tgt_begin;
-  a.n_tgt = (int)n_tgt;
-  a.vel = (float2*)vel;
-  a.pos_out = (float2*)pos_out;
-  a.acc_out = (float2*)acc_out;
-  a.partial = (float2*)((char*)ws + kFlagBytes);
-  a.delta = delta;
-  a.clamp = clamp;
-  a.uniform_mass = p.uni ? uniform_mass : 0.f;
-  a.flags = flags;
+  a.mass_all = (const float*)s.mass_all;
+  a.n_src = (int)s.n_src;
+  a.tgt_begin = (int)b.tgt_begin;
+  a.n_tgt = (int)b.n_tgt;
+  a.vel = (float2*)b.vel;
+  a.pos_out = (float2*)b.pos_out;
+  a.acc_out = (float2*)b.acc_out;
+  a.partial = direct_partial(s.ws, p.L);
+  a.delta = b.delta;
+  a.clamp = s.clamp;
+  a.uniform_mass = p.uni ? s.uniform_mass : 0.f;
+  a.flags = direct_flags(s.ws);
   a.run_state = -1;
 
   if (p.arith == NBODY_ARITH_EXACT) {
-    TimerScope ts(timer, stream);
-    HIPCHK(c, launch_direct_exact(stream, a));
+    TimerScope ts(b.timer, s.stream);
+    HIPCHK(c, launch_direct_exact(s.stream, a));
     return NBODY_OK;
   }
-  const float2* pos_far = nullptr;
-  const uint32_t* near_list = nullptr;
-  const float* minv_far = nullptr;
-  if (cfg.nearfar) {
-    char* nf_scratch = (char*)ws + kFlagBytes + p.partial_bytes;
-    NearFarLayout L = nearfar_layout(n_src);
-    pos_far = (const float2*)(nf_scratch + L.pos_far);
-    near_list = (const uint32_t*)(nf_scratch + L.near_list);
-    if (p.stream_m) minv_far = (const float*)(nf_scratch + L.minv_far);
-  }
+  const uint32_t* near_list = cfg.nearfar ? direct_near_list(s.ws, p.L) : nullptr;
   {
-    TimerScope ts(timer, stream);
+    TimerScope ts(b.timer, s.stream);
     if (cfg.nearfar) {  // state 0: main pass over the far sources without the clamp, near sources added by finish
       DirectArgs a0 = a;
-      a0.src_pos = pos_far;
+      a0.src_pos = direct_pos_far(s.ws, p.L);
       a0.src_couples = p.couples ? 1 : 0;
-      a0.src_minv = minv_far;
-      if (p.couples) a0.n_src = (int)far_padded(n_src);
+      a0.src_minv = p.stream_m ? direct_minv_far(s.ws, p.L) : nullptr;
+      if (p.couples) a0.n_src = (int)far_padded(s.n_src);
       a0.near_list = near_list;
       a0.to_partial = 1;
       a0.run_state = 0;
@@ -319,61 +312,67 @@ int ctx_direct_run(nbody_ctx* c, hipStream_t stream, int64_t n_src, const void* 
         a0.uniform_mass = 1.0f;
         a0.tile_mass = p.classes->tile_mass;
       }
-      if (p.mutual) {  // the mutual pass and its partial reduction, both inside the timer: one far sum per target in a.partial
-        char* nf_scratch = (char*)ws + kFlagBytes + p.partial_bytes;
-        NearFarLayout L = nearfar_layout(n_src);
-        char* area = (char*)ws + mutual_offset(n_src, n_tgt_max);
-        HIPCHK(c, launch_direct_mutual(stream, a0, mutual_area(area, n_src, (const uint32_t*)(nf_scratch + L.is_near),
-                                                                (const uint32_t*)(nf_scratch + L.scan))));
-      } else {
-        HIPCHK(c, launch_direct_fast(stream, a0, cfg, true));
-      }
+      if (p.mutual)  // the mutual pass and its partial reduction, both inside the timer: one far sum per target in a.partial
+        HIPCHK(c, launch_direct_mutual(s.stream, a0, direct_mutual_area(s.ws, p.L, s.n_src)));
+      else
+        HIPCHK(c, launch_direct_fast(s.stream, a0, cfg, true));
     }
     DirectArgs a1 = a;  // state 1: one clamped pass over every source
     a1.to_partial = cfg.gsplit > 1;
     a1.run_state = 1;
-    HIPCHK(c, launch_direct_fast(stream, a1, cfg, false));
+    HIPCHK(c, launch_direct_fast(s.stream, a1, cfg, false));
   }
   if (cfg.nearfar) {
     DirectArgs a0 = a;
     a0.near_list = near_list;
     a0.run_state = 0;
-    HIPCHK(c, launch_direct_finish(stream, a0, p.mutual ? 1 : cfg.gsplit, true));
+    HIPCHK(c, launch_direct_finish(s.stream, a0, p.mutual ? 1 : cfg.gsplit, true));
   }
   if (cfg.gsplit > 1) {
     DirectArgs a1 = a;
     a1.run_state = 1;
-    HIPCHK(c, launch_direct_finish(stream, a1, cfg.gsplit, false));
+    HIPCHK(c, launch_direct_finish(s.stream, a1, cfg.gsplit, false));
   }
   if (p.use_hazard) {  // state 2
     DirectArgs a2 = a;
     a2.run_state = 2;
-    HIPCHK(c, launch_direct_exact(stream, a2));
+    HIPCHK(c, launch_direct_exact(s.stream, a2));
   }
   return NBODY_OK;
 }
 
 namespace {
-int direct_step_dev(nbody_ctx* c, hipStream_t stream, int64_t n_src, const void* pos_all, const void* mass_all,
-                    float uniform_mass, int64_t tgt_begin, int64_t n_tgt, void* vel, void* pos_out, void* acc_out,
-                    float delta, float clamp, int arith, void* ws, size_t ws_bytes, nbody_timer* timer) {
-  if (n_src < 0 || n_tgt < 0 || tgt_begin < 0 || tgt_begin + n_tgt > n_src || n_src > 0x7fffffffLL)
-    return fail(c, NBODY_ERR_INVALID, "direct_step: bad target/source range");
-  if (n_tgt == 0) return NBODY_OK;
-  if (!pos_all || !mass_all) return fail(c, NBODY_ERR_INVALID, "direct_step: null pos_all/mass_all");
-  if ((vel == nullptr) != (pos_out == nullptr))
-    return fail(c, NBODY_ERR_INVALID, "direct_step: vel and pos_out must both be given or both be NULL");
-  if (!vel && !acc_out) return fail(c, NBODY_ERR_INVALID, "direct_step: nothing to compute");
-  int rc = ctx_direct_prep(c, stream, n_src, pos_all, mass_all, uniform_mass, n_tgt, n_tgt, clamp, arith, ws, ws_bytes);
-  if (rc) return rc;
-  return ctx_direct_run(c, stream, n_src, pos_all, mass_all, uniform_mass, tgt_begin, n_tgt, vel, pos_out, acc_out, delta, clamp, arith,
-                    n_tgt, n_tgt, ws, ws_bytes, timer);
+// One call for a whole step whose block is all its targets: the block's checks come first (an empty block needs no workspace).
+int direct_step_dev(nbody_ctx* c, DirectStep s, const DirectBlock& b) {
+  s.n_tgt_total = s.n_tgt_max = b.n_tgt;
+  int rc = check_range(c, s, b, true);
+  if (rc || b.n_tgt == 0) return rc;
+  rc = check_arrays(c, s, &b);
+  if (!rc) rc = ctx_direct_prep(c, s);
+  return rc ? rc : ctx_direct_run(c, s, b);
+}
+
+DirectStep ctx_whole_step(const nbody_ctx* c, const void* pos) {  // the step of a context over all its f32 bodies, from `pos`
+  const State<float>& s = c->sf;
+  return DirectStep{c->stream, s.n, pos, s.set[s.cur].mass, direct_mass_hint(s), c->params.clamp, c->params.arith, s.n, s.n,
+                    c->workspace, c->workspace_bytes};
+}
+// Everything a captured pair of steps bakes in (ctx.h: DirectGraph).
+DirectGraphKey direct_graph_key(const nbody_ctx* c, float delta) {
+  const State<float>& s = c->sf;
+  const auto& st = s.set[s.cur];
+  DirectGraphKey k;
+  k.n = s.n; k.pos_a = st.pos; k.pos_b = s.pos_next; k.vel = st.vel; k.mass = st.mass; k.ws = c->workspace;
+  k.delta = delta; k.clamp = c->params.clamp; k.uniform = direct_mass_hint(s); k.arith = c->params.arith;
+  k.row_epoch = s.row_epoch; k.cls_usable = s.classes.usable; k.cls_rank = s.classes.rank; k.cls_tile_mass = s.classes.tile_mass;
+  k.env = direct_env_signature();
+  return k;
 }
 
 }  // namespace
 
 int ctx_ensure_workspace(nbody_ctx* c, size_t bytes) { return ensure_dev_bytes(c, c->workspace, c->workspace_bytes, bytes); }
-size_t ctx_direct_ws_bytes(int64_t n_src, int64_t n_tgt) { return direct_ws_bytes(n_src, n_tgt); }
+size_t ctx_direct_ws_bytes(int64_t n_src, int64_t n_tgt) { return direct_layout(n_src, n_tgt).total; }
 int ctx_ensure_mass_classes(nbody_ctx* c) { return c && c->has_f32 ? ensure_mass_classes(c) : NBODY_OK; }
 
 }  // namespace nbody
@@ -385,7 +384,7 @@ NB_API int nbody_update_direct_f32(nbody_ctx* c, float delta, int n_steps, nbody
   if (n_steps < 0) return fail(c, NBODY_ERR_INVALID, "update_direct_f32: n_steps < 0");
   HIPCHK(c, hipSetDevice(c->device));
   State<float>& s = c->sf;
-  int rc = ctx_ensure_workspace(c, direct_ws_bytes(s.n, s.n));
+  int rc = ctx_ensure_workspace(c, ctx_direct_ws_bytes(s.n, s.n));
   if (rc) return rc;
   const double t_begin = now_s();
   int step = 0;
@@ -397,23 +396,15 @@ NB_API int nbody_update_direct_f32(nbody_ctx* c, float delta, int n_steps, nbody
   if (want_graph) {
     auto& st = s.set[s.cur];
     DirectGraph& g = c->direct_graph;
-    const std::string sig = direct_env_signature();
-    const auto& mc = s.classes;
-    const bool stale = !g.exec || g.n != s.n || g.pos_a != st.pos || g.pos_b != s.pos_next || g.vel != st.vel ||
-                       g.mass != st.mass || g.ws != c->workspace || g.delta != delta || g.clamp != c->params.clamp ||
-                       g.uniform != direct_mass_hint(s) || g.arith != c->params.arith || g.env != sig || g.row_epoch != s.row_epoch ||
-                       g.cls_usable != mc.usable || g.cls_rank != (const void*)mc.rank || g.cls_tile_mass != (const void*)mc.tile_mass;
-    if (stale) {
+    const DirectGraphKey key = direct_graph_key(c, delta);
+    if (!g.exec || !(g.key == key)) {
       g.reset();
       hipGraph_t graph = nullptr;
       hipError_t e = hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal);
       int rc1 = NBODY_OK, rc2 = NBODY_OK;
       if (e == hipSuccess) {
-        rc1 = direct_step_dev(c, c->stream, s.n, st.pos, st.mass, direct_mass_hint(s), 0, s.n, st.vel, s.pos_next, nullptr, delta,
-                              c->params.clamp, c->params.arith, c->workspace, c->workspace_bytes, nullptr);
-        if (!rc1)
-          rc2 = direct_step_dev(c, c->stream, s.n, s.pos_next, st.mass, direct_mass_hint(s), 0, s.n, st.vel, st.pos, nullptr, delta,
-                                c->params.clamp, c->params.arith, c->workspace, c->workspace_bytes, nullptr);
+        rc1 = direct_step_dev(c, ctx_whole_step(c, st.pos), DirectBlock{0, s.n, st.vel, s.pos_next, nullptr, delta, nullptr});
+        if (!rc1) rc2 = direct_step_dev(c, ctx_whole_step(c, s.pos_next), DirectBlock{0, s.n, st.vel, st.pos, nullptr, delta, nullptr});
         e = hipStreamEndCapture(c->stream, &graph);
       }
       if (e == hipSuccess && !rc1 && !rc2 && graph) e = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
@@ -422,9 +413,7 @@ NB_API int nbody_update_direct_f32(nbody_ctx* c, float delta, int n_steps, nbody
         g.reset();  // capture is an optimisation: fall through to eager steps
         (void)hipGetLastError();
       } else {
-        g.n = s.n; g.pos_a = st.pos; g.pos_b = s.pos_next; g.vel = st.vel; g.mass = st.mass; g.ws = c->workspace;
-        g.delta = delta; g.clamp = c->params.clamp; g.uniform = direct_mass_hint(s); g.arith = c->params.arith; g.env = sig;
-        g.row_epoch = s.row_epoch; g.cls_usable = mc.usable; g.cls_rank = mc.rank; g.cls_tile_mass = mc.tile_mass;
+        g.key = key;
       }
     }
     if (g.exec) {
@@ -434,8 +423,7 @@ NB_API int nbody_update_direct_f32(nbody_ctx* c, float delta, int n_steps, nbody
   }
   for (; step < n_steps; ++step) {
     auto& st = s.set[s.cur];
-    rc = direct_step_dev(c, c->stream, s.n, st.pos, st.mass, direct_mass_hint(s), 0, s.n, st.vel, s.pos_next, nullptr, delta,
-                         c->params.clamp, c->params.arith, c->workspace, c->workspace_bytes, c->timer);
+    rc = direct_step_dev(c, ctx_whole_step(c, st.pos), DirectBlock{0, s.n, st.vel, s.pos_next, nullptr, delta, c->timer});
     if (rc) return rc;
     rc = tracers_direct_f32(c, st.pos, st.mass, delta);
     if (rc) return rc;
@@ -458,13 +446,11 @@ NB_API int nbody_accel_direct_f32(nbody_ctx* c, float* acc_xy) {
   if (!acc_xy) return fail(c, NBODY_ERR_INVALID, "accel_direct_f32: acc_xy is NULL");
   HIPCHK(c, hipSetDevice(c->device));
   State<float>& s = c->sf;
-  int rc = ctx_ensure_workspace(c, direct_ws_bytes(s.n, s.n));
+  int rc = ctx_ensure_workspace(c, ctx_direct_ws_bytes(s.n, s.n));
   if (rc) return rc;
   rc = ensure_mass_classes(c);
   if (rc) return rc;
-  auto& st = s.set[s.cur];
-  rc = direct_step_dev(c, c->stream, s.n, st.pos, st.mass, direct_mass_hint(s), 0, s.n, nullptr, nullptr, s.acc, 0.f, c->params.clamp,
-                       c->params.arith, c->workspace, c->workspace_bytes, c->timer);
+  rc = direct_step_dev(c, ctx_whole_step(c, s.set[s.cur].pos), DirectBlock{0, s.n, nullptr, nullptr, s.acc, 0.f, c->timer});
   if (rc) return rc;
   if (s.n) HIPCHK(c, hipMemcpyAsync(acc_xy, s.acc, (size_t)s.n * sizeof(float2), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -473,15 +459,15 @@ NB_API int nbody_accel_direct_f32(nbody_ctx* c, float* acc_xy) {
 
 NB_API size_t nbody_direct_workspace_bytes(int64_t n_sources, int64_t n_targets) {
   if (n_sources < 0 || n_targets < 0) return 0;
-  return direct_ws_bytes(n_sources, n_targets);
+  return ctx_direct_ws_bytes(n_sources, n_targets);
 }
 
 NB_API int nbody_direct_step_dev(void* stream, int64_t n_sources, const void* pos_all, const void* mass_all,
                                  float uniform_mass, int64_t target_begin, int64_t n_targets, void* vel, void* pos_out, void* acc_out,
                                  float delta, float clamp, int arith, void* workspace, size_t workspace_bytes,
                                  nbody_timer* timer) {
-  return direct_step_dev(nullptr, (hipStream_t)stream, n_sources, pos_all, mass_all, uniform_mass, target_begin, n_targets, vel,
-                         pos_out, acc_out, delta, clamp, arith, workspace, workspace_bytes, timer);
+  return direct_step_dev(nullptr, DirectStep{(hipStream_t)stream, n_sources, pos_all, mass_all, uniform_mass, clamp, arith, 0, 0, workspace, workspace_bytes},
+                         DirectBlock{target_begin, n_targets, vel, pos_out, acc_out, delta, timer});
 }
 
 NB_API int nbody_direct_workspace_peek(void* stream, const void* workspace, int32_t out[4]) {
@@ -500,15 +486,16 @@ NB_API int nbody_weights_to_mass_dev(void* stream, int64_t n, const void* weight
 NB_API int nbody_direct_prep_dev(void* stream, int64_t n_sources, const void* pos_all, const void* mass_all, float uniform_mass,
                                  int64_t n_targets_total, int64_t n_targets_max, float clamp, int arith, void* workspace,
                                  size_t workspace_bytes) {
-  return ctx_direct_prep(nullptr, (hipStream_t)stream, n_sources, pos_all, mass_all, uniform_mass, n_targets_total, n_targets_max, clamp,
-                     arith, workspace, workspace_bytes);
+  return ctx_direct_prep(nullptr, DirectStep{(hipStream_t)stream, n_sources, pos_all, mass_all, uniform_mass, clamp, arith, n_targets_total,
+                                             n_targets_max, workspace, workspace_bytes});
 }
 NB_API int nbody_direct_run_dev(void* stream, int64_t n_sources, const void* pos_all, const void* mass_all, float uniform_mass,
                                 int64_t target_begin, int64_t n_targets, void* vel, void* pos_out, void* acc_out, float delta,
                                 float clamp, int arith, int64_t n_targets_total, int64_t n_targets_max, void* workspace,
                                 size_t workspace_bytes, nbody_timer* timer) {
-  return ctx_direct_run(nullptr, (hipStream_t)stream, n_sources, pos_all, mass_all, uniform_mass, target_begin, n_targets, vel, pos_out,
-                    acc_out, delta, clamp, arith, n_targets_total, n_targets_max, workspace, workspace_bytes, timer);
+  return ctx_direct_run(nullptr, DirectStep{(hipStream_t)stream, n_sources, pos_all, mass_all, uniform_mass, clamp, arith, n_targets_total,
+                                            n_targets_max, workspace, workspace_bytes},
+                        DirectBlock{target_begin, n_targets, vel, pos_out, acc_out, delta, timer});
 }
 
 

@@ -12,7 +12,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "direct_kernels.h"
+#include "direct_layout.h"
 #include "driver.h"
 #include "target_kernels.h"
 
@@ -82,7 +82,7 @@ int tracers_direct_f32(nbody_ctx* c, const float2* pos, const float* mass, float
   }
   TracerRoute r;
   if (arith == NBODY_ARITH_AUTO) {  // the step's own decision (kFlagState == 2: a body outside FAST's domain), and the per-tracer exception
-    r.word = (const int*)c->workspace;
+    r.word = direct_flags(c->workspace);
     r.word_kind = kTracerWordState;
     r.per_target = 1;
   }

@@ -117,6 +117,94 @@ def test_workspace_size_is_monotone_and_small(nb):
     assert 256 <= a <= 128 << 20 and 256 <= b <= 128 << 20
 
 
+def _lib(nb, which):
+    """The product or the laboratory library with the binding's signatures (no device is touched by loading it)."""
+    lib = nb._capi._load(which)
+    assert lib.nbody_last_error.restype is ctypes.c_char_p
+    return lib
+
+
+# (n_sources, n_targets) -> nbody_direct_workspace_bytes, recorded from a build of commit 6559f51 (the parent of the change that
+# introduced DirectLayout); the product and the laboratory build of that commit agree on every row
+_WORKSPACE_BYTES = [
+    ((0, 0), 276736), ((1, 1), 276992), ((2048, 2048), 615424), ((6000, 2500), 866816),
+    ((65535, 65535), 11281408), ((65536, 65536), 11281408),
+    ((262144, 262080), 29630976), ((262144, 262144), 29631488), ((262145, 262145), 33827328),
+    ((393215, 393215), 38020096), ((393216, 393216), 73147904), ((393216, 393215), 38020096),
+    ((1 << 20, 1 << 20), 113518080), ((1 << 20, 1 << 17), 58991616),
+    ((4194304, 4194304), 755246592), ((4194305, 4194305), 285485568), ((1 << 24, 1 << 21), 704914432),
+]
+
+
+@pytest.mark.parametrize("which", ["product", "lab"])
+def test_workspace_bytes_are_those_of_the_hand_written_layout(nb, which):
+    """The direct workspace (csrc/direct_layout.h) is as large as the pointer arithmetic it replaced made it, for sizes on both
+    sides of every branch: the source-split rules of the partial sums (65 536, 262 144 sources; a short last block), the mutual
+    area's bounds (393 216 and 4 194 304 bodies, one block of all targets) and sizes beyond.  Values from commit 6559f51."""
+    lib = _lib(nb, which)
+    got = [((ns, nt), int(lib.nbody_direct_workspace_bytes(ns, nt))) for (ns, nt), _ in _WORKSPACE_BYTES]
+    assert got == _WORKSPACE_BYTES
+    assert lib.nbody_direct_workspace_bytes(-1, 0) == 0 and lib.nbody_direct_workspace_bytes(4, -1) == 0
+
+
+@pytest.mark.parametrize("which", ["product", "lab"])
+def test_direct_dev_calls_report_bad_arguments_before_touching_a_device(nb, which):
+    """nbody_direct_prep_dev / _run_dev / _step_dev: one case per message, and the cases that pin the ORDER of the checks (texts and
+    order as commit 6559f51 reported them).  Every case ends in a check that fires before any HIP call: the "workspace" is host
+    memory the library never gets to dereference."""
+    C = nb._capi
+    lib = _lib(nb, which)
+    n = 8
+    need = int(lib.nbody_direct_workspace_bytes(n, n))
+    ws = np.zeros(need, np.uint8)
+    pos, mass, out = np.ones((n, 2), np.float32), np.ones(n, np.float32), np.zeros((n, 2), np.float32)
+    W, P, M, O = C._ptr(ws), C._ptr(pos), C._ptr(mass), C._ptr(out)
+    FAST, EXACT, BIG = C.ARITH_FAST, C.ARITH_EXACT, 1 << 31
+
+    def prep(n_src=n, p=P, m=M, total=n, tmax=n, arith=FAST, w=W, wb=need):
+        return lib.nbody_direct_prep_dev(None, n_src, p, m, 0.0, total, tmax, 0.001, arith, w, wb)
+
+    def run(n_src=n, p=P, m=M, begin=0, cnt=n, vel=O, pos_out=O, acc=None, arith=FAST, total=n, tmax=n, w=W, wb=need):
+        return lib.nbody_direct_run_dev(None, n_src, p, m, 0.0, begin, cnt, vel, pos_out, acc, 0.1, 0.001, arith, total, tmax, w, wb, None)
+
+    def step(n_src=n, p=P, m=M, begin=0, cnt=n, vel=O, pos_out=O, acc=None, arith=FAST, w=W, wb=need):
+        return lib.nbody_direct_step_dev(None, n_src, p, m, 0.0, begin, cnt, vel, pos_out, acc, 0.1, 0.001, arith, w, wb, None)
+
+    counts, rng = "direct_step: bad target/source counts", "direct_step: bad target/source range"
+    bad_arith, small = "direct_step: bad arith", "direct_step: workspace too small"
+    null, nothing = "direct_step: null pos_all/mass_all", "direct_step: nothing to compute"
+    both = "direct_step: vel and pos_out must both be given or both be NULL"
+    cases = [
+        # ---- prep: counts, arith, workspace, then (a step with targets, not EXACT) the arrays
+        (lambda: prep(n_src=-1, total=0, tmax=0), counts), (lambda: prep(total=n + 1), counts), (lambda: prep(tmax=n + 1), counts),
+        (lambda: prep(total=-1, tmax=-1), counts), (lambda: prep(n_src=BIG, w=None), counts),
+        (lambda: prep(arith=3, w=None), bad_arith), (lambda: prep(arith=-1, p=None), bad_arith),
+        (lambda: prep(w=None), small), (lambda: prep(wb=need - 1), small), (lambda: prep(p=None, w=None), small),
+        (lambda: prep(p=None), null), (lambda: prep(m=None), null),
+        (lambda: prep(total=0, tmax=0, p=None), None), (lambda: prep(arith=EXACT, p=None), None),
+        # ---- run: range, then the step's checks, then (a block with targets) the arrays and the outputs
+        (lambda: run(cnt=-1), rng), (lambda: run(begin=-1), rng), (lambda: run(begin=1), rng), (lambda: run(cnt=5, tmax=4), rng),
+        (lambda: run(n_src=-1, cnt=0, total=0, tmax=0), rng), (lambda: run(cnt=n, n_src=4, arith=3, w=None), rng),
+        (lambda: run(n_src=BIG), counts), (lambda: run(total=n + 1, arith=3), counts), (lambda: run(total=4, tmax=n), counts),
+        (lambda: run(arith=3, w=None), bad_arith), (lambda: run(w=None, p=None), small), (lambda: run(wb=need - 1), small),
+        (lambda: run(cnt=0, w=None), small), (lambda: run(cnt=0, p=None, vel=None), None),
+        (lambda: run(p=None, vel=None), null), (lambda: run(m=None), null),
+        (lambda: run(vel=None), both), (lambda: run(pos_out=None, acc=O), both), (lambda: run(vel=None, pos_out=None), nothing),
+        # ---- the one-call step: its block's checks come first (an empty block needs nothing else), a source count beyond int is a range
+        (lambda: step(cnt=-1), rng), (lambda: step(begin=1), rng), (lambda: step(n_src=BIG, cnt=0, w=None), rng), (lambda: step(n_src=-1, cnt=0), rng),
+        (lambda: step(cnt=0, w=None, p=None, arith=3), None),
+        (lambda: step(p=None, arith=3, w=None), null), (lambda: step(vel=None, arith=3), both), (lambda: step(vel=None, pos_out=None, w=None), nothing),
+        (lambda: step(arith=3, w=None), bad_arith), (lambda: step(w=None), small), (lambda: step(wb=need - 1), small),
+    ]
+    for i, (call, message) in enumerate(cases):
+        rc = call()
+        if message is None:
+            assert rc == C.OK, (i, rc, lib.nbody_last_error(None))
+        else:
+            assert rc == C.ERR_INVALID and lib.nbody_last_error(None) == message.encode(), (i, rc, message, lib.nbody_last_error(None))
+    assert not ws.any() and np.all(pos == 1) and np.all(mass == 1) and not out.any()
+
+
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 @pytest.mark.parametrize("n,leaf", [(0, 64), (1, 64), (40, 64), (64, 64), (65, 64), (1024, 64), (777, 16), (50000, 64)])
 def test_host_bvh_matches_oracle_bit_exact(nb, orc, dtype, n, leaf):

@@ -245,6 +245,45 @@ def test_device_level_sharded_targets_equal_whole(nb, ctx):
         assert np.array_equal(np.concatenate([a[k], b[k]]), whole[k])
 
 
+@pytest.mark.parametrize("masses", ["equal", "three"])
+def test_prepared_blocks_equal_whole_with_the_split_forced(nb, force_nearfar, masses):
+    """nbody_direct_prep_dev once (n_targets_total = n, n_targets_max = 2500) and nbody_direct_run_dev over blocks of 2500, 2500 and
+    1000 targets, FAST with the near/far split: the partial sums and the near/far scratch of the blocked step lie where the layout
+    for (n, 2500) puts them, those of the whole step where the layout for (n, n) does, and both steps read the same far copy and
+    near list.  Positions, velocities and accelerations bit for bit."""
+    import torch
+    C = nb._capi
+    n = 6000
+    pos, vel, _ = nb.scenes.plummer(n, seed=49)
+    w = np.ones(n, np.uint32) if masses == "equal" else (np.arange(n) % 3 + 1).astype(np.uint32)
+    hint = C.mass_hint(w)
+    dev = torch.device("cuda:0")
+    tp = torch.from_numpy(pos).to(dev)
+    tm = torch.from_numpy(w.astype(F32)).to(dev)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def step(blocks):
+        tmax = max(cnt for _, cnt in blocks)
+        ws_bytes = C.direct_workspace_bytes(n, tmax)
+        ws = torch.zeros(ws_bytes, dtype=torch.uint8, device=dev)
+        v = torch.from_numpy(vel.copy()).to(dev)
+        out = torch.zeros((n, 2), dtype=torch.float32, device=dev)
+        acc = torch.zeros((n, 2), dtype=torch.float32, device=dev)
+        C.direct_prep_dev(stream, n, tp.data_ptr(), tm.data_ptr(), n, tmax, 0.001, C.ARITH_FAST, ws.data_ptr(), ws_bytes, uniform_mass=hint)
+        for begin, cnt in blocks:
+            C.direct_run_dev(stream, n, tp.data_ptr(), tm.data_ptr(), begin, cnt, v[begin:].data_ptr(), out[begin:].data_ptr(),
+                             acc[begin:].data_ptr(), 0.1, 0.001, C.ARITH_FAST, n, tmax, ws.data_ptr(), ws_bytes, uniform_mass=hint)
+        torch.cuda.synchronize()
+        assert C.direct_workspace_peek(stream, ws.data_ptr())[3] == 0        # the split engaged
+        return out.cpu().numpy(), v.cpu().numpy(), acc.cpu().numpy()
+
+    whole = step([(0, n)])
+    blocked = step([(0, 2500), (2500, 2500), (5000, 1000)])
+    assert np.any(whole[2] != 0) and not np.array_equal(whole[1], vel)
+    for a, b in zip(blocked, whole):
+        assert np.array_equal(a, b)
+
+
 # ------------------------------------------------------------------ near/far split of the sources (nearfar.hip)
 def _dev_accel(nb, pos, w, arith=None, uniform=0.0):
     """Acceleration of every body through nbody_direct_step_dev; returns (acc, (hazard, fallback, n_near, state))."""
@@ -540,6 +579,48 @@ def test_captured_direct_graph_is_rebuilt_when_a_tree_step_permutes_the_rows(nb,
     acc = ctx.accel_direct()
     tg = np.arange(0, n, 31)
     check_fast(acc[tg], *_refs(orc, p, w2, targets=tg)[:2], label=" after graph, builds, graph")
+
+
+def test_captured_direct_graph_follows_delta_clamp_and_arith(nb, monkeypatch):
+    """DirectGraphKey (ctx.h): a captured pair of steps bakes delta, the clamp and the arithmetic in.  update_direct(., 6) replays a
+    capture at n = 1024; delta, params.clamp and params.arith change one at a time, each followed by a direct call on the buffers the
+    capture was made for, then by a tree step (the rows move: row_epoch) and another direct call.  Every state equals, bit for bit,
+    that of a second context driven the same way with NBODY_DIRECT_GRAPH=0 (eager steps only)."""
+    C = nb._capi
+    n = 1024
+    pos, vel, w = nb.scenes.plummer(n, seed=149)
+
+    def drive():
+        states = []
+        with C.Context(0) as c:
+            c.set_params(arith=C.ARITH_AUTO, theta=50.0, order=C.ORDER_CONSISTENT)
+            c.upload(pos, vel, w)
+            delta = 0.1
+            c.update_direct(delta, 6)
+            states.append(c.download())
+            for change in ("delta", "clamp", "arith"):
+                if change == "delta":
+                    delta = 0.05
+                elif change == "clamp":
+                    c.set_params(clamp=0.004)
+                else:
+                    c.set_params(arith=C.ARITH_FAST)
+                c.update_direct(delta, 6)
+                states.append(c.download())
+                c.update_tree(C.TREE_BVH, delta, 1)
+                c.update_direct(delta, 6)
+                states.append(c.download())
+        return states
+
+    replayed = drive()
+    monkeypatch.setenv("NBODY_DIRECT_GRAPH", "0")
+    eager = drive()
+    assert len(replayed) == len(eager) == 7
+    for k, (a, b) in enumerate(zip(replayed, eager)):
+        for x, y in zip(a, b):
+            assert np.array_equal(x, y), k
+    for k in range(1, 7):                                     # and the changes did change the physics: no two states alike
+        assert not np.array_equal(replayed[k][0], replayed[k - 1][0])
 
 
 # ------------------------------------------------------------------ the main pass's variants (NBODY_DIRECT_ASM)
