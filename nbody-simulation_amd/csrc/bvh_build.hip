@@ -7,8 +7,8 @@
 // inside each side feeds the next level's sum, so the permutation has to be exact, not just the split.
 //
 //   * min / max / counts are order-independent: plain reductions.
-//   * the sum is a rounding chain: exact_sum.h scans it (addend = map parity -> increment inside one binade; a real
-//     f32 add whenever the chain leaves its binade).
+//   * the sum is a rounding chain: exact_sum.h (here its float instance) scans it (addend = map parity -> increment
+//     inside one binade; a real f32 add whenever the chain leaves its binade).
 //   * the two-pointer partition swaps the k-th misplaced element from the left with the k-th misplaced element from
 //     the right (the pointers only ever stop at misplaced elements): two rank lists from one prefix count, then
 //     independent swaps.
@@ -40,6 +40,10 @@
 namespace nbody {
 
 namespace {
+
+using Chain = xsum::Chain<float>;  // this build is the f32 one
+using Step = xsum::Step<float>;
+using Run = xsum::Run<float>;
 
 constexpr int kEPT = 4;          // consecutive points per thread in the rank-list passes
 constexpr int kSeqRun = 16;      // real adds after every stop of the scan
@@ -150,7 +154,7 @@ __device__ __forceinline__ float sse_min(float a, float b) { return a < b ? a : 
 __device__ __forceinline__ float sse_max(float a, float b) { return a > b ? a : b; }
 
 __device__ __forceinline__ float lane_value(float v, int k) {  // k uniform
-  return xsum::u2f((uint32_t)__builtin_amdgcn_readlane((int)xsum::f2u(v), k));
+  return xsum::from_bits<float>((uint32_t)__builtin_amdgcn_readlane((int)xsum::to_bits(v), k));
 }
 
 // written by another compute unit in this very kernel: read past the local L1
@@ -288,11 +292,11 @@ __device__ __forceinline__ void chain_run_all(const StageView<NT>& V, int begin,
 template <int CTRL, int ROWS> __device__ __forceinline__ uint32_t dpp_or_zero(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWS, 0xf, false);
 }
-template <int CTRL, int ROWS> __device__ __forceinline__ xsum::Step dpp_step(xsum::Step v) {
-  return xsum::Step{dpp_or_zero<CTRL, ROWS>(v.a0), dpp_or_zero<CTRL, ROWS>(v.a1)};
+template <int CTRL, int ROWS> __device__ __forceinline__ Step dpp_step(Step v) {
+  return Step{dpp_or_zero<CTRL, ROWS>(v.a0), dpp_or_zero<CTRL, ROWS>(v.a1)};
 }
 // inclusive scan over the wave's 64 lanes, in lane order
-__device__ __forceinline__ xsum::Step wave_scan_steps(xsum::Step v) {
+__device__ __forceinline__ Step wave_scan_steps(Step v) {
   v = xsum::compose(dpp_step<0x111, 0xf>(v), v);  // row_shr:1
   v = xsum::compose(dpp_step<0x112, 0xf>(v), v);  // row_shr:2
   v = xsum::compose(dpp_step<0x114, 0xf>(v), v);  // row_shr:4
@@ -302,12 +306,12 @@ __device__ __forceinline__ xsum::Step wave_scan_steps(xsum::Step v) {
   return v;
 }
 // the value of the lane before (wave_shr:1), the identity in lane 0
-__device__ __forceinline__ xsum::Step wave_prev_step(xsum::Step v) { return dpp_step<0x138, 0xf>(v); }
+__device__ __forceinline__ Step wave_prev_step(Step v) { return dpp_step<0x138, 0xf>(v); }
 
 // ---- NW waves working on one node --------------------------------------------------------------------------------
 // NW == 1 needs no barrier and no LDS (a wave runs in lock-step); NW > 1 is a whole work-group.
 template <int NW> struct Scratch {
-  xsum::Step w[2][NW];     // wave totals of a scan round; two sets, taken in turn (a round that succeeds has one barrier)
+  Step w[2][NW];     // wave totals of a scan round; two sets, taken in turn (a round that succeeds has one barrier)
   uint32_t wkind[2][NW];   // per wave: 1 a negative increment, 2 a positive one, 4 a step too large for 32-bit sums
   float redf[2][NW];
   int bad;
@@ -364,7 +368,7 @@ __device__ __forceinline__ void exact_fold(const Src& P, int begin, int len, flo
   bool seq = false;       // decided from s: a chain at 0.0 is not in any binade yet
   bool foreseen = false;  // the last thing done was a run of real adds up to a crossing that was seen coming
   while (pos < len) {
-    xsum::Chain ch;
+    Chain ch;
     if (!seq) seq = !xsum::chain_open(s, ch);
     const int gp = chain_off + pos;  // addends behind the chain
     // A chain of same-signed addends leaves its binade about every time the number of addends doubles: near the
@@ -377,7 +381,7 @@ __device__ __forceinline__ void exact_fold(const Src& P, int begin, int len, flo
       // addends away if they go on like that.  The scan stops a little short of that point and real adds carry the
       // chain across (they need no binade), instead of a whole scan failing there and starting over.  A guess: a
       // chain that does something else is scanned and stopped as ever.
-      const float rem = (float)gp * ((float)(xsum::kHi - ch.S) / (float)ch.S);
+      const float rem = (float)gp * ((float)(xsum::kHi<float> - ch.S) / (float)ch.S);
       const int irem = rem < 1.0e9f ? (int)rem : 1000000000;
       const int safe = irem - (irem >> 5) - 8;
       if (safe < 64) {
@@ -414,11 +418,11 @@ __device__ __forceinline__ void exact_fold(const Src& P, int begin, int len, flo
 #endif
     const int limit = pos + span < len ? pos + span : len;
     const int base = pos + tid * EPT;
-    xsum::Step f[EPT];
-    xsum::Step t{0u, 0u};
+    Step f[EPT];
+    Step t = xsum::identity<float>();
     int imin = 0, imax = 0;  // extremes of the increments: their signs, and whether 32-bit totals can be trusted
 #pragma unroll
-    for (int j = 0; j < EPT; ++j) f[j] = xsum::Step{0u, 0u};
+    for (int j = 0; j < EPT; ++j) f[j] = xsum::identity<float>();
     if (base < limit) {
 #pragma unroll
       for (int j = 0; j < EPT; ++j) {
@@ -434,8 +438,8 @@ __device__ __forceinline__ void exact_fold(const Src& P, int begin, int len, flo
         t = xsum::compose(t, f[j]);
       }
     }
-    const xsum::Step inc = wave_scan_steps(t);  // inclusive scan inside the wave
-    xsum::Step ex = wave_prev_step(inc);        // exclusive: everything before my addends
+    const Step inc = wave_scan_steps(t);  // inclusive scan inside the wave
+    Step ex = wave_prev_step(inc);        // exclusive: everything before my addends
     {  // (an increment is below 2^22 in size unless it is the poison: 512 of one sign stay below 2^31)
       const uint32_t kind = (__ballot(imin < 0) != 0ull ? 1u : 0u) | (__ballot(imax > 0) != 0ull ? 2u : 0u) |
                             (__ballot(imax >= (1 << 23)) != 0ull ? 4u : 0u);
@@ -444,7 +448,7 @@ __device__ __forceinline__ void exact_fold(const Src& P, int begin, int len, flo
     if (tid == 0) sh->bad = INT_MAX;
     __syncthreads();
     // every wave scans the NW wave totals for itself (lanes 0..NW-1): no second barrier
-    xsum::Step wi{0u, 0u};
+    Step wi = xsum::identity<float>();
     uint32_t wk = 0u;
     if (lane < NW) { wi = sh->w[par][lane]; wk = sh->wkind[par][lane]; }
     const int w0 = (int)wi.a0, w1 = (int)wi.a1;
@@ -456,14 +460,14 @@ __device__ __forceinline__ void exact_fold(const Src& P, int begin, int len, flo
     if constexpr (NW > 2) wi = xsum::compose(dpp_step<0x112, 0xf>(wi), wi);
     if constexpr (NW > 4) wi = xsum::compose(dpp_step<0x114, 0xf>(wi), wi);
     if constexpr (NW > 8) wi = xsum::compose(dpp_step<0x118, 0xf>(wi), wi);
-    xsum::Step tot;
+    Step tot;
     tot.a0 = (uint32_t)__builtin_amdgcn_readlane((int)wi.a0, NW - 1);
     tot.a1 = (uint32_t)__builtin_amdgcn_readlane((int)wi.a1, NW - 1);
     par ^= 1;
     // Increments of one sign only (the usual case: coordinates of one sign) move S one way: every intermediate S lies
     // between the first and the last, so the last one being inside the binade says all were.  The totals are exact:
     // every wave's is below 2^24 in size, NW of them cannot wrap.
-    if (kind != 3u && kind < 4u && xsum::in_binade(xsum::apply(ch.S, tot))) {
+    if (kind != 3u && kind < 4u && xsum::in_binade<float>(xsum::apply(ch.S, tot))) {
       s = xsum::chain_value(ch, xsum::apply(ch.S, tot));
       pos += span;
 #ifdef NB_FOLD_TIMING
@@ -472,7 +476,7 @@ __device__ __forceinline__ void exact_fold(const Src& P, int begin, int len, flo
       continue;
     }
     if (wave > 0) {
-      xsum::Step pw;  // all the waves before mine
+      Step pw;  // all the waves before mine
       pw.a0 = (uint32_t)__builtin_amdgcn_readlane((int)wi.a0, wave - 1);
       pw.a1 = (uint32_t)__builtin_amdgcn_readlane((int)wi.a1, wave - 1);
       ex = xsum::compose(pw, ex);
@@ -484,7 +488,7 @@ __device__ __forceinline__ void exact_fold(const Src& P, int begin, int len, flo
     for (int j = 0; j < EPT; ++j) {
       if (base + j < limit && bad == INT_MAX) {
         const uint32_t nx = xsum::apply(S, f[j]);
-        if (!xsum::in_binade(nx)) {
+        if (!xsum::in_binade<float>(nx)) {
           bad = tid * EPT + j;
           bs = S;
         } else {
@@ -720,8 +724,8 @@ __global__ __launch_bounds__(256) void bvh_chunk_sums(BvhPtrs a, int level) {
   }
 }
 
-__device__ __forceinline__ xsum::Run shfl_down_run(const xsum::Run& r, int d) {
-  xsum::Run o;
+__device__ __forceinline__ Run shfl_down_run(const Run& r, int d) {
+  Run o;
   o.a0 = __shfl_down(r.a0, d, 64); o.a1 = __shfl_down(r.a1, d, 64);
   o.lo0 = __shfl_down(r.lo0, d, 64); o.lo1 = __shfl_down(r.lo1, d, 64);
   o.hi0 = __shfl_down(r.hi0, d, 64); o.hi1 = __shfl_down(r.hi1, d, 64);
@@ -738,13 +742,13 @@ __host__ __device__ inline int run_mult(int len) {
 }
 constexpr int kGapCap = 2048;  // real adds around powers of two, per chain and walk, fetched ahead into LDS
 constexpr int kRunRec = 24;  // ints per chunk and coordinate: sign, E_a (0: no run), E_b, u0, u1, run A (6), run B (6), [17] where its real adds lie in `gaps` (bvh_big_fold), pad
-__device__ __forceinline__ void store_run(int* o, const xsum::Run& r) {
+__device__ __forceinline__ void store_run(int* o, const Run& r) {
   o[0] = r.a0; o[1] = r.a1; o[2] = r.lo0; o[3] = r.lo1; o[4] = r.hi0; o[5] = r.hi1;
 }
 // ordered reduction over the wave: lane 0 ends with r(lane 0) then r(lane 1) then ...
-__device__ __forceinline__ xsum::Run wave_run_in_order(xsum::Run r, int lane) {
+__device__ __forceinline__ Run wave_run_in_order(Run r, int lane) {
   for (int d = 1; d < 64; d <<= 1) {
-    const xsum::Run o = shfl_down_run(r, d);
+    const Run o = shfl_down_run(r, d);
     if ((lane & (2 * d - 1)) == 0) r = xsum::run_then(r, o);
   }
   return r;
@@ -757,7 +761,7 @@ __device__ __forceinline__ xsum::Run wave_run_in_order(xsum::Run r, int lane) {
 __global__ __launch_bounds__(256) void bvh_chunk_runs(BvhPtrs a, int level) {
   constexpr int PER = kChunk / 256;
   __shared__ double redd[4][4];
-  __shared__ xsum::Run redr[2][2][4];  // [coordinate][A / B][wave]
+  __shared__ Run redr[2][2][4];  // [coordinate][A / B][wave]
   __shared__ int redi[2][4][4];        // [coordinate][#A, #B, #active, shape ok][wave]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nc = a.chunkcount[level];
@@ -797,7 +801,7 @@ __global__ __launch_bounds__(256) void bvh_chunk_runs(BvhPtrs a, int level) {
     const int seg = m * PER;                                                    // consecutive addends per thread
     const int base = tid * seg;
     // does either coordinate cross a power of two in this chunk?  Only then the threads need their own f64 prefix
-    xsum::Chain cax, cbx, cay, cby;
+    Chain cax, cbx, cay, cby;
     const bool hx = xsum::chain_open((float)px, cax) && xsum::chain_open((float)(px + tot.x), cbx) && cax.sign == cbx.sign;
     const bool hy = xsum::chain_open((float)py, cay) && xsum::chain_open((float)(py + tot.y), cby) && cay.sign == cby.sign;
     const bool crossing = (hx && cbx.E == cax.E + 1u) || (hy && cby.E == cay.E + 1u);  // uniform
@@ -822,7 +826,7 @@ __global__ __launch_bounds__(256) void bvh_chunk_runs(BvhPtrs a, int level) {
     const bool active = base < cnt;
     for (int comp = 0; comp < 2; ++comp) {
       const double s0 = comp ? sy0 : sx0, s1 = s0 + (comp ? ly : lx);
-      const xsum::Chain ca = comp ? cay : cax, cb = comp ? cby : cbx;
+      const Chain ca = comp ? cay : cax, cb = comp ? cby : cbx;
       const bool have = (comp ? hy : hx) && (cb.E == ca.E || cb.E == ca.E + 1u);
       int cls = 2;  // 0: run A, 1: run B, 2: left to real adds
       if (have) {
@@ -849,23 +853,23 @@ __global__ __launch_bounds__(256) void bvh_chunk_runs(BvhPtrs a, int level) {
         redi[comp][2][wave] = nAct;
         redi[comp][3][wave] = (mA == lowA && mB == (mAct & ~lowNB)) ? 1 : 0;
       }
-      xsum::Run r = xsum::run_none();
+      Run r = xsum::run_none<float>();
       if (cls == 0 || cls == 1) {
-        const xsum::Chain& ch = cls ? cb : ca;
+        const Chain& ch = cls ? cb : ca;
         for (int j = 0; j < seg && base + j < cnt; ++j) {
           const float2 qq = P[base + j];
           r = xsum::run_then(r, xsum::run_of(xsum::step_of(comp ? qq.y : qq.x, ch.sign, ch.E)));
         }
       }
       // ordered reduction: a wave is usually all A or all B; only a wave that straddles the crossing reduces twice
-      xsum::Run ra = xsum::run_none(), rb = xsum::run_none();
+      Run ra = xsum::run_none<float>(), rb = xsum::run_none<float>();
       if (mB == 0ull) {
-        ra = wave_run_in_order(cls == 0 ? r : xsum::run_none(), lane);
+        ra = wave_run_in_order(cls == 0 ? r : xsum::run_none<float>(), lane);
       } else if (mA == 0ull) {
-        rb = wave_run_in_order(cls == 1 ? r : xsum::run_none(), lane);
+        rb = wave_run_in_order(cls == 1 ? r : xsum::run_none<float>(), lane);
       } else {
-        ra = wave_run_in_order(cls == 0 ? r : xsum::run_none(), lane);
-        rb = wave_run_in_order(cls == 1 ? r : xsum::run_none(), lane);
+        ra = wave_run_in_order(cls == 0 ? r : xsum::run_none<float>(), lane);
+        rb = wave_run_in_order(cls == 1 ? r : xsum::run_none<float>(), lane);
       }
       if (lane == 0) { redr[comp][0][wave] = ra; redr[comp][1][wave] = rb; }
       __syncthreads();
@@ -891,7 +895,7 @@ __global__ __launch_bounds__(256) void bvh_chunk_runs(BvhPtrs a, int level) {
         const int u1 = (nAct - nB) * seg < cnt ? (nAct - nB) * seg : cnt;
         o[3] = u0;
         o[4] = u1 > u0 ? u1 : u0;
-        xsum::Run A = redr[comp][0][0], Bq = redr[comp][1][0];
+        Run A = redr[comp][0][0], Bq = redr[comp][1][0];
         for (int w = 1; w < 4; ++w) { A = xsum::run_then(A, redr[comp][0][w]); Bq = xsum::run_then(Bq, redr[comp][1][w]); }
         store_run(o + 5, A);
         store_run(o + 11, Bq);
@@ -935,7 +939,7 @@ __global__ __launch_bounds__(512) void bvh_big_fold(BvhPtrs a, int level, int us
 #endif
         if (tid < nrun) {
           const int f0 = tid * rm, f1 = f0 + rm < nch ? f0 + rm : nch;
-          xsum::Run A = xsum::run_none(), B = xsum::run_none();
+          Run A = xsum::run_none<float>(), B = xsum::run_none<float>();
           int sign = 0, Ea = 0, Eb = 0, u0 = 0, u1 = 0, pos = 0;
           bool valid = true, crossed = false;
           for (int f = f0; f < f1 && valid; ++f) {
@@ -943,7 +947,7 @@ __global__ __launch_bounds__(512) void bvh_big_fold(BvhPtrs a, int level, int us
             const int cntf = (f + 1) * kChunk < len ? kChunk : len - f * kChunk;
             const int fE = fr[1];
             if (fE == 0) { valid = false; break; }
-            xsum::Run fa, fb;
+            Run fa, fb;
             fa.a0 = fr[5]; fa.a1 = fr[6]; fa.lo0 = fr[7]; fa.lo1 = fr[8]; fa.hi0 = fr[9]; fa.hi1 = fr[10];
             fb.a0 = fr[11]; fb.a1 = fr[12]; fb.lo0 = fr[13]; fb.lo1 = fr[14]; fb.hi0 = fr[15]; fb.hi1 = fr[16];
             const bool whole = fr[3] >= cntf;  // one run over the whole chunk
@@ -1019,7 +1023,7 @@ __global__ __launch_bounds__(512) void bvh_big_fold(BvhPtrs a, int level, int us
           // one wave runs ahead as long as the prepared runs hold (a few dozen instructions per chunk, no barrier) ...
           if (tid < 64) {
             // The chain's state stays (sign, E, S) from run to run; it turns into a float only where real adds need one.
-            xsum::Chain ch;
+            Chain ch;
             bool open = xsum::chain_open(sum, ch);
             for (; ci < b0 + nb; ++ci) {
               // the whole record in one go (LDS latency once per chunk, not once per field)
@@ -1028,11 +1032,11 @@ __global__ __launch_bounds__(512) void bvh_big_fold(BvhPtrs a, int level, int us
               if (r0.y == 0 || !open) break;  // no run prepared, or a state no run applies to: the scan's
               const int lo = ci * rlen, hi = lo + rlen < len ? lo + rlen : len;
               const int u0 = r0.w, u1 = r1.x;
-              xsum::Chain tc = ch;
+              Chain tc = ch;
               bool good = true;
               int u = 0;
               if (u0 > 0) {  // part A: [lo, lo + u0)
-                xsum::Run r;
+                Run r;
                 r.a0 = r1.y; r.a1 = r1.z; r.lo0 = r1.w; r.lo1 = r2.x; r.hi0 = r2.y; r.hi1 = r2.z;
                 good = (int)tc.E == r0.y && (int)tc.sign == r0.x && xsum::run_fits(tc.S, r);
                 tc.S = (uint32_t)((int)tc.S + ((tc.S & 1u) ? r.a1 : r.a0));
@@ -1045,7 +1049,7 @@ __global__ __launch_bounds__(512) void bvh_big_fold(BvhPtrs a, int level, int us
               }
               if (good && lo + u1 < hi) {  // part B: [lo + u1, hi), in the binade above
                 good = (int)tc.E == r0.z && (int)tc.sign == r0.x;
-                xsum::Run r;
+                Run r;
                 r.a0 = r2.w; r.a1 = r3.x; r.lo0 = r3.y; r.lo1 = r3.z; r.hi0 = r3.w; r.hi1 = r4.x;
                 good = good && xsum::run_fits(tc.S, r);
                 tc.S = (uint32_t)((int)tc.S + ((tc.S & 1u) ? r.a1 : r.a0));
@@ -1056,13 +1060,13 @@ __global__ __launch_bounds__(512) void bvh_big_fold(BvhPtrs a, int level, int us
               used += u;
             }
             if (open) sum = xsum::chain_value(ch, ch.S);
-            if (tid == 0) { sh.bad_s = xsum::f2u(sum); sh.bad = ci; }
+            if (tid == 0) { sh.bad_s = xsum::to_bits(sum); sh.bad = ci; }
           }
           __syncthreads();
 #ifdef NB_FOLD_TIMING
           { const long long t = wall_clock64(); NB_FT_ADD(10, t - tr0) tr0 = t; }
 #endif
-          sum = xsum::u2f(sh.bad_s);
+          sum = xsum::from_bits<float>(sh.bad_s);
           ci = sh.bad;
           __syncthreads();
           if (ci >= b0 + nb) break;

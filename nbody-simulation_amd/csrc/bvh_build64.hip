@@ -6,8 +6,8 @@
 // written plainly, level by level over ALL open nodes at once, because what it replaces is a 50-65 ms host build at
 // N = 4 M (HISTORY.md §4.3c), not a 0.7 ms device one:
 //   per level   fold64      one work-group per (open node, coordinate): min / max and the sum EXACTLY as the sequential chain
-//                           `sum = sum + p` rounds it (bvh_tree.rs:58-61) — the parity-map scan of exact_sum64.h, a tile of
-//                           addends per round, real adds wherever the chain leaves its binade;
+//                           `sum = sum + p` rounds it (bvh_tree.rs:58-61) — the parity-map scan of exact_sum.h (its double
+//                           instance), a tile of addends per round, real adds wherever the chain leaves its binade;
 //               plan64      mean = sum / len (:67); the node's 2048-point chunks join the level's chunk table;
 //               count64     per chunk: #{x > mean.x}, #{y > mean.y} (:70-72) -> the node's counters;
 //               mis64       axis rule `vert > hori -> x` (:73), split = the count of predicate-true points; per chunk the
@@ -32,11 +32,15 @@
 #include <algorithm>
 
 #include "bvh_build64.h"
-#include "exact_sum64.h"
+#include "exact_sum.h"
 
 namespace nbody {
 
 namespace {
+
+using Chain = xsum::Chain<double>;  // this build is the f64 one
+using Step = xsum::Step<double>;
+using Run = xsum::Run<double>;
 
 constexpr int kChunk = 2048;   // points per work-group in the per-chunk passes (256 threads x 8)
 constexpr int kEPT = 8;        // ... per thread
@@ -61,7 +65,7 @@ struct Ptrs {
   int *nseg0, *seg_node, *seg_index;
   double2 *seg_sum, *seg_min, *seg_max, *seg_prefix;
   uint64_t* seg_pred;       // [seg][coord]: predicted (sign << 32 | E), 0 = no run
-  xsum64::Run* seg_run;     // [seg][coord]
+  Run* seg_run;             // [seg][coord]
   int node_cap, open_cap, chunk_cap, seg_cap, n;
 };
 
@@ -88,7 +92,7 @@ Ptrs make_ptrs(char* s, const Bvh64Layout& L, int n) {
   a.seg_sum = (double2*)(s + L.seg_sum); a.seg_min = (double2*)(s + L.seg_min); a.seg_max = (double2*)(s + L.seg_max);
   a.seg_prefix = (double2*)(s + L.seg_prefix);
   a.seg_pred = (uint64_t*)(s + L.seg_pred);
-  a.seg_run = (xsum64::Run*)(s + L.seg_run);
+  a.seg_run = (Run*)(s + L.seg_run);
   a.node_cap = L.node_cap; a.open_cap = L.open_cap; a.chunk_cap = L.chunk_cap; a.seg_cap = L.seg_cap; a.n = n;
   return a;
 }
@@ -100,7 +104,7 @@ __device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, int d) {
   const unsigned lo = (unsigned)__shfl_up((int)(unsigned)v, d, 64), hi = (unsigned)__shfl_up((int)(unsigned)(v >> 32), d, 64);
   return ((uint64_t)hi << 32) | lo;
 }
-__device__ __forceinline__ xsum64::Step shfl_up_step(xsum64::Step v, int d) { return {shfl_up_u64(v.a0, d), shfl_up_u64(v.a1, d)}; }
+__device__ __forceinline__ Step shfl_up_step(Step v, int d) { return {shfl_up_u64(v.a0, d), shfl_up_u64(v.a1, d)}; }
 
 // ---- begin: copy the rows in, seed the root --------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void b64_init(Ptrs a, const double2* __restrict__ pos) {
@@ -131,7 +135,7 @@ constexpr int kLongNode = 65536;  // ... long meaning more points than this: the
 // for a 4 M-point root.  But a segment's effect on the chain — the map {state at its start} -> {state at its end} — can be
 // prepared by any other work-group beforehand, IF it is told which binade the chain will be in: that is predicted from
 // plain f64 partial sums, and the run carries the bounds that prove, when it is applied, that every add inside stayed in
-// that binade (exact_sum64.h: Run, run_fits).  A wrong prediction or a crossing costs that segment's scan, never a bit.
+// that binade (exact_sum.h: Run, run_fits).  A wrong prediction or a crossing costs that segment's scan, never a bit.
 __global__ __launch_bounds__(64) void b64_seg_plan(Ptrs a, int level) {
   const int nopen = a.opencount[level] < a.open_cap ? a.opencount[level] : a.open_cap;
   const int lane = threadIdx.x;
@@ -205,8 +209,8 @@ __global__ __launch_bounds__(64) void b64_seg_prefix(Ptrs a, int level) {
 }
 
 __device__ __forceinline__ int64_t shfl_up_i64(int64_t v, int d) { return (int64_t)shfl_up_u64((uint64_t)v, d); }
-__device__ __forceinline__ xsum64::Run shfl_up_run(const xsum64::Run& r, int d) {
-  xsum64::Run o;
+__device__ __forceinline__ Run shfl_up_run(const Run& r, int d) {
+  Run o;
   o.a0 = shfl_up_i64(r.a0, d); o.a1 = shfl_up_i64(r.a1, d);
   o.lo0 = shfl_up_i64(r.lo0, d); o.lo1 = shfl_up_i64(r.lo1, d);
   o.hi0 = shfl_up_i64(r.hi0, d); o.hi1 = shfl_up_i64(r.hi1, d);
@@ -216,14 +220,14 @@ __device__ __forceinline__ xsum64::Run shfl_up_run(const xsum64::Run& r, int d) 
 // the run of every segment, for the binade its two ends are predicted to lie in
 __global__ __launch_bounds__(512) void b64_seg_runs(Ptrs a, int level) {
   __shared__ double stage[kSeg + kSeg / 16];
-  __shared__ xsum64::Run wrun[8];
+  __shared__ Run wrun[8];
   const int nseg = a.segcount[level] < a.seg_cap ? a.segcount[level] : a.seg_cap;
   const int comp = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int sg = blockIdx.x; sg < nseg; sg += gridDim.x) {
     const double p0 = comp == 0 ? a.seg_prefix[sg].x : a.seg_prefix[sg].y;
     const double p1 = p0 + (comp == 0 ? a.seg_sum[sg].x : a.seg_sum[sg].y);
-    xsum64::Chain c;
-    if (!xsum64::predict_binade(p0, p1, c)) {  // (uniform) the chain's start, a crossing, a sum near zero: scanned by the fold
+    Chain c;
+    if (!xsum::predict_binade(p0, p1, c)) {  // (uniform) the chain's start, a crossing, a sum near zero: scanned by the fold
       if (tid == 0) a.seg_pred[2 * (size_t)sg + comp] = 0;
       continue;
     }
@@ -231,21 +235,21 @@ __global__ __launch_bounds__(512) void b64_seg_runs(Ptrs a, int level) {
     const double* __restrict__ X = reinterpret_cast<const double*>(a.P + a.nbegin[node] + (size_t)k * kSeg) + comp;
     for (int e = tid; e < kSeg; e += 512) stage[e + (e >> 4)] = X[2 * (size_t)e];
     __syncthreads();
-    xsum64::Run r = xsum64::run_none();
+    Run r = xsum::run_none<double>();
 #pragma unroll 4
     for (int j = 0; j < 16; ++j) {
       const int e = tid * 16 + j;
-      r = xsum64::run_then(r, xsum64::run_of(xsum64::step_of(stage[e + (e >> 4)], c.sign, c.E)));
+      r = xsum::run_then(r, xsum::run_of(xsum::step_of(stage[e + (e >> 4)], c.sign, c.E)));
     }
     for (int d = 1; d < 64; d <<= 1) {  // in thread order: lane 63 ends up with the wave's run
-      const xsum64::Run o = shfl_up_run(r, d);
-      if (lane >= d) r = xsum64::run_then(o, r);
+      const Run o = shfl_up_run(r, d);
+      if (lane >= d) r = xsum::run_then(o, r);
     }
     if (lane == 63) wrun[wave] = r;
     __syncthreads();
     if (tid == 0) {
-      xsum64::Run t = wrun[0];
-      for (int w = 1; w < 8; ++w) t = xsum64::run_then(t, wrun[w]);
+      Run t = wrun[0];
+      for (int w = 1; w < 8; ++w) t = xsum::run_then(t, wrun[w]);
       a.seg_run[2 * (size_t)sg + comp] = t;
       a.seg_pred[2 * (size_t)sg + comp] = (c.sign << 32) | c.E;
     }
@@ -261,7 +265,7 @@ template <int NT, int kFoldEPT>
 __global__ __launch_bounds__(NT) void b64_fold(Ptrs a, int level) {
   constexpr int NW = NT / 64, TILE = NT * kFoldEPT;
   __shared__ double stage[TILE + TILE / 16];
-  __shared__ xsum64::Step wtot[NW];
+  __shared__ Step wtot[NW];
   __shared__ unsigned long long sh_S;
   __shared__ int sh_bad;
   __shared__ double red[2][NW];
@@ -277,8 +281,8 @@ __global__ __launch_bounds__(NT) void b64_fold(Ptrs a, int level) {
     int pos = 0, stops = 0;
     const int seg0 = (TILE == kSeg && len > kLongNode) ? a.nseg0[node] : -1;  // this node's prepared segments, if any
     while (pos < len) {
-      xsum64::Chain c;
-      if (!xsum64::chain_open(s, c)) {  // not inside a binade (zero, subnormal, a power of two, non-finite): real adds
+      Chain c;
+      if (!xsum::chain_open(s, c)) {  // not inside a binade (zero, subnormal, a power of two, non-finite): real adds
         int cnt = pos == 0 ? kSeqStart : kSeqRun;
         cnt = len - pos < cnt ? len - pos : cnt;
         for (int k = 0; k < cnt; ++k) {  // every thread the same adds: no hand-over
@@ -297,9 +301,9 @@ __global__ __launch_bounds__(NT) void b64_fold(Ptrs a, int level) {
           const size_t sg = 2 * (size_t)(seg0 + (pos >> 13)) + comp;
           static_assert(kSeg == 1 << 13, "pos >> 13 is the segment index");
           if (a.seg_pred[sg] == ((c.sign << 32) | c.E)) {
-            const xsum64::Run r = a.seg_run[sg];
-            if (xsum64::run_fits(c.S, r)) {
-              s = xsum64::chain_value(c, (uint64_t)((int64_t)c.S + ((c.S & 1ull) ? r.a1 : r.a0)));
+            const Run r = a.seg_run[sg];
+            if (xsum::run_fits(c.S, r)) {
+              s = xsum::chain_value(c, (uint64_t)((int64_t)c.S + ((c.S & 1ull) ? r.a1 : r.a0)));
               const double2 smn = a.seg_min[sg >> 1], smx = a.seg_max[sg >> 1];
               mn = sse_min(mn, comp == 0 ? smn.x : smn.y);
               mx = sse_max(mx, comp == 0 ? smx.x : smx.y);
@@ -316,38 +320,38 @@ __global__ __launch_bounds__(NT) void b64_fold(Ptrs a, int level) {
       if (tid == 0) sh_bad = INT_MAX;
       __syncthreads();
       const int base = tid * kFoldEPT;  // tile-relative
-      xsum64::Step f[kFoldEPT];
-      xsum64::Step F = xsum64::identity();
+      Step f[kFoldEPT];
+      Step F = xsum::identity<double>();
 #pragma unroll
       for (int j = 0; j < kFoldEPT; ++j) {
         if (base + j < cnt) {
           const double v = stage[base + j + ((base + j) >> 4)];
-          f[j] = xsum64::step_of(v, c.sign, c.E);
+          f[j] = xsum::step_of(v, c.sign, c.E);
         } else {
-          f[j] = xsum64::identity();
+          f[j] = xsum::identity<double>();
         }
-        F = xsum64::compose(F, f[j]);
+        F = xsum::compose(F, f[j]);
       }
-      xsum64::Step inc = F;  // inclusive scan of the threads' maps, in thread order
+      Step inc = F;  // inclusive scan of the threads' maps, in thread order
       for (int d = 1; d < 64; d <<= 1) {
-        const xsum64::Step o = shfl_up_step(inc, d);
-        if (lane >= d) inc = xsum64::compose(o, inc);
+        const Step o = shfl_up_step(inc, d);
+        if (lane >= d) inc = xsum::compose(o, inc);
       }
       if (lane == 63) wtot[wave] = inc;
       __syncthreads();
-      xsum64::Step excl = xsum64::identity();
-      for (int w = 0; w < wave; ++w) excl = xsum64::compose(excl, wtot[w]);
-      xsum64::Step prev = shfl_up_step(inc, 1);
-      if (lane == 0) prev = xsum64::identity();
-      excl = xsum64::compose(excl, prev);
-      uint64_t S = xsum64::apply(c.S, excl);  // the state this thread's first addend meets (if every earlier add stayed in the binade)
+      Step excl = xsum::identity<double>();
+      for (int w = 0; w < wave; ++w) excl = xsum::compose(excl, wtot[w]);
+      Step prev = shfl_up_step(inc, 1);
+      if (lane == 0) prev = xsum::identity<double>();
+      excl = xsum::compose(excl, prev);
+      uint64_t S = xsum::apply(c.S, excl);  // the state this thread's first addend meets (if every earlier add stayed in the binade)
       int bad = INT_MAX;
       uint64_t S_at_bad = 0;
 #pragma unroll
       for (int j = 0; j < kFoldEPT; ++j) {
         if (base + j < cnt && bad == INT_MAX) {
-          const uint64_t after = xsum64::apply(S, f[j]);
-          if (!xsum64::in_binade(after)) { bad = base + j; S_at_bad = S; }
+          const uint64_t after = xsum::apply(S, f[j]);
+          if (!xsum::in_binade<double>(after)) { bad = base + j; S_at_bad = S; }
           else S = after;
         }
       }
@@ -363,12 +367,12 @@ __global__ __launch_bounds__(NT) void b64_fold(Ptrs a, int level) {
       if (first_bad == INT_MAX) {
         if (base <= cnt - 1 && cnt - 1 < base + kFoldEPT) sh_S = S;  // the owner of the tile's last addend
         __syncthreads();
-        s = xsum64::chain_value(c, sh_S);
+        s = xsum::chain_value(c, sh_S);
         pos = end;
       } else {
         if (bad == first_bad) sh_S = S_at_bad;
         __syncthreads();
-        s = xsum64::chain_value(c, sh_S);
+        s = xsum::chain_value(c, sh_S);
         ++stops;
         pos += first_bad;
         const int run = cnt - first_bad < kSeqRun ? cnt - first_bad : kSeqRun;  // real adds, as far as the tile holds them
@@ -791,7 +795,7 @@ Bvh64Layout bvh64_layout(int64_t n, int leaf_size) {
   L.seg_node = take(4 * SC); L.seg_index = take(4 * SC);
   L.seg_sum = take(16 * SC); L.seg_min = take(16 * SC); L.seg_max = take(16 * SC); L.seg_prefix = take(16 * SC);
   L.seg_pred = take(16 * SC);
-  L.seg_run = take(2 * sizeof(xsum64::Run) * SC);
+  L.seg_run = take(2 * sizeof(Run) * SC);
   L.P = take(16 * N);
   L.ID = take(4 * N);
   L.nbegin = take(4 * C); L.nlen = take(4 * C); L.ndepth = take(4 * C); L.nchild = take(4 * C); L.nleaf = take(4 * C);

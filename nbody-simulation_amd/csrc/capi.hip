@@ -15,8 +15,7 @@
 
 #include "direct_kernels.h"
 #include "driver.h"
-#include "exact_sum.h"
-#include "exact_sum64.h"
+#include "exact_sum_emulate.h"
 
 using namespace nbody;
 
@@ -369,7 +368,7 @@ NB_API int nbody_get_counting(const nbody_ctx* c, nbody_counting* out) {
 
 NB_API int nbody_selftest_exact_sum(const float* x, int64_t n, int tile, int seq_run, float* out_sum, int64_t* out_restarts) {
   if ((!x && n > 0) || n < 0 || tile < 1 || seq_run < 1 || !out_sum) return NBODY_ERR_INVALID;
-  *out_sum = xsum::emulate_fold(x, n, tile, seq_run, out_restarts);
+  *out_sum = xsum::emulate_fold<float>(x, n, tile, seq_run, out_restarts);
   return NBODY_OK;
 }
 NB_API int nbody_selftest_div_pair(int device, const float* nx, const float* ny, const float* den, int64_t n, float* qx, float* qy) {
@@ -396,12 +395,12 @@ NB_API int nbody_selftest_exact_sum_chunked(const float* x, int64_t n, int chunk
 }
 NB_API int nbody_selftest_exact_sum_f64(const double* x, int64_t n, int tile, int seq_run, double* out_sum, int64_t* out_restarts) {
   if ((!x && n > 0) || n < 0 || tile < 1 || seq_run < 1 || !out_sum) return NBODY_ERR_INVALID;
-  *out_sum = xsum64::emulate_fold(x, n, tile, seq_run, out_restarts);
+  *out_sum = xsum::emulate_fold<double>(x, n, tile, seq_run, out_restarts);
   return NBODY_OK;
 }
 NB_API int nbody_selftest_exact_sum_f64_segmented(const double* x, int64_t n, int seg, double* out_sum, int64_t* out_runs_used) {
   if ((!x && n > 0) || n < 0 || seg < 1 || !out_sum) return NBODY_ERR_INVALID;
-  *out_sum = xsum64::emulate_fold_segmented(x, n, seg, out_runs_used);
+  *out_sum = xsum::emulate_fold_segmented(x, n, seg, out_runs_used);
   return NBODY_OK;
 }
 NB_API int nbody_bvh_build_restarts(const nbody_ctx* ctx) {

@@ -354,7 +354,7 @@ def _bits64(v):
 
 @pytest.mark.parametrize("tile,seq_run", [(4096, 16), (1024, 16), (4, 1), (7, 3)])
 def test_exact_sum_scan_f64_reproduces_the_sequential_chain(nb, tile, seq_run):
-    """The f64 twin (csrc/exact_sum64.h) that the device build of f64 BVHs runs: 53-bit significands, 64-bit increments."""
+    """The f64 twin (csrc/exact_sum.h) that the device build of f64 BVHs runs: 53-bit significands, 64-bit increments."""
     C = nb._capi
     rng = np.random.default_rng(199)
     cases = {}

@@ -37,6 +37,14 @@ def test_delta_decoder_asan_ubsan_on_damaged_streams(tmp_path):
                    src=os.path.join(ROOT, "tests", "native", "delta_decoder_sanitize.cpp"))
 
 
+def test_exact_sum_scan_asan_ubsan(tmp_path):
+    """csrc/exact_sum.h, f32 and f64 from the one template: the scan against the plain loop on random bit patterns, the
+    algebra the device scans rely on (compose, runs that fit are exact), poison steps; under UBSan also that saturated
+    run offsets add without wrapping."""
+    _build_and_run(tmp_path, ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"],
+                   src=os.path.join(ROOT, "tests", "native", "exact_sum_check.cpp"))
+
+
 def test_multi_device_barrier_and_pool_tsan(tmp_path):
     """csrc/multi_sync.hpp (the barrier in front of every collective, the one-worker-per-device pool) under TSan: votes,
     a rank failing before a barrier, and a rank failing right after the final barrier while the others still wake from it
