@@ -53,7 +53,9 @@ extern "C" {
  * 3: nbody_update_direct_f64, nbody_accel_direct_f64 (the direct O(N^2) step on an f64 context);
  *    nbody_accel_direct_at_f32 / _f64 (the direct sum at arbitrary points) were added under 3: new symbols only, nothing
  *    that existed changed; nbody_tracers_upload_f32 / _f64, nbody_tracers_download_f32 / _f64 and nbody_num_tracers (massless
- *    tracers that step with the bodies) likewise: new symbols only;
+ *    tracers that step with the bodies) likewise: new symbols only; nbody_render_rgba_tracers, nbody_snapshot_num_tracers,
+ *    nbody_snapshot_tracers_f32 / _f64 and nbody_tracers_delta_begin / _pending / _end / _reset (the tracers in the frame, the
+ *    snapshot and a delta stream of their own) likewise: new symbols only;
  *    a binding compares nbody_abi_version() with the value it was written against before it binds anything else. */
 #define NBODY_ABI_VERSION 3
 
@@ -240,8 +242,10 @@ int nbody_accel_direct_at_f64(nbody_ctx* ctx, int64_t n_targets, const double* t
  * is.  The timer of nbody_set_timer keeps bracketing the bodies' dominant kernel only; a direct step's tracer time is booked
  * under sum_gravity with the rest of the call (force and integration are fused), a tree step's tracer walk under sum_gravity
  * and their integration under post_calculations.
- * nbody_upload_* of bodies removes the tracers (a new world).  Snapshots, delta streams, nbody_render_rgba and the parity
- * hooks (nbody_accel_*, nbody_walk_tree_*) see bodies only and leave the tracers alone.
+ * nbody_upload_* of bodies removes the tracers (a new world).  Tracers leave the device the way bodies do, through calls of their
+ * own beside the bodies': nbody_snapshot_begin takes them along (nbody_snapshot_tracers_*), nbody_tracers_delta_* streams their
+ * positions as a second NBD1 sequence, nbody_render_rgba_tracers paints them into the frame.  nbody_render_rgba, nbody_delta_* and
+ * the parity hooks (nbody_accel_*, nbody_walk_tree_*) still see bodies only and give the same bytes whether tracers exist or not.
  * NBODY_ERR_INVALID (the message names "tracers"): ctx NULL, m < 0, a NULL array with m > 0, the other precision, no particles
  * uploaded, a context made by nbody_create_multi*; and nbody_update_tree_async_f32, nbody_update_tree_shard_*,
  * nbody_export_slice_dev, nbody_import_rows_dev while tracers are present.
@@ -373,6 +377,17 @@ int nbody_snapshot_pending(const nbody_ctx* ctx);
 int nbody_snapshot_end_f32(nbody_ctx* ctx, float* pos_xy, float* vel_xy, uint32_t* weight, uint32_t* ids, uint64_t* step_out);
 int nbody_snapshot_end_f64(nbody_ctx* ctx, double* pos_xy, double* vel_xy, uint32_t* weight, uint32_t* ids, uint64_t* step_out);
 
+/* The tracers of the pending snapshot.  nbody_snapshot_begin on a context that holds tracers copies their positions and
+ * velocities aside too — on the device, in the same place in stream order as the rows — and sends them to pinned host memory
+ * on the copy stream with the rest.  These calls are valid while a snapshot is pending: they wait for the transfer and copy
+ * out the tracers as they were at begin, in upload order (either pointer may be NULL), whatever happened to the context's
+ * tracers since (a tracer upload or removal, a body upload).  They do not end the snapshot: nbody_snapshot_end_* still does.
+ * nbody_snapshot_num_tracers: tracers of the pending snapshot, 0 if none is pending; with 0 tracers the copy-out succeeds and
+ * writes nothing.  NBODY_ERR_INVALID: ctx NULL, a context made by nbody_create_multi*, no snapshot pending, the other precision. */
+int64_t nbody_snapshot_num_tracers(const nbody_ctx* ctx);
+int nbody_snapshot_tracers_f32(nbody_ctx* ctx, float* pos_xy, float* vel_xy);
+int nbody_snapshot_tracers_f64(nbody_ctx* ctx, double* pos_xy, double* vel_xy);
+
 /* ---- delta snapshots (the commented experiment of main.rs:107-134) ------------------------------------------ */
 /* Upstream tried, and left commented out, taking the difference of the positions across an update and printing its
  * zstd-compressed size.  There is no behaviour or format to match; this is the device-side counterpart of that idea
@@ -389,6 +404,18 @@ int nbody_delta_pending(const nbody_ctx* ctx);
 int nbody_delta_end(nbody_ctx* ctx, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* step_out);
 int nbody_delta_reset(nbody_ctx* ctx);
 size_t nbody_delta_bound(int64_t n, int is_f64);
+/* The same for the tracers' positions: a second sequence of NBD1 streams with key arrays and a key-frame sequence of its own.
+ * The header's body count is m and the positions are the tracers' in upload order; semantics as nbody_delta_* — ordered after
+ * the last step, one tracers stream in flight per context (beside the bodies' one: one of each may be pending at once, taken
+ * in either order), a too small cap leaves the stream pending (nbody_delta_bound(m, is_f64) sizes it), the first stream after
+ * nbody_tracers_upload_* or nbody_tracers_delta_reset is a key frame.  The bodies' streams are the same bytes whether or not
+ * tracers exist or a tracers stream is in flight.  The receiving side is a second nbody_delta_decoder.
+ * NBODY_ERR_INVALID: ctx NULL, a context made by nbody_create_multi*, begin without tracers or while a tracers stream is
+ * pending, end with none pending, reset while one is pending. */
+int nbody_tracers_delta_begin(nbody_ctx* ctx);
+int nbody_tracers_delta_pending(const nbody_ctx* ctx);
+int nbody_tracers_delta_end(nbody_ctx* ctx, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* step_out);
+int nbody_tracers_delta_reset(nbody_ctx* ctx);
 /* The receiving side (host only, no device needed): a decoder holds the keys of the last two snapshots. */
 typedef struct nbody_delta_decoder nbody_delta_decoder;
 nbody_delta_decoder* nbody_delta_decoder_create(void);
@@ -416,6 +443,13 @@ int nbody_delta_decoder_positions_f64(const nbody_delta_decoder* dec, double* po
  * 0xef)) of the LAST such row on the pixel, alpha = min(10 * rows, 250).  rgba_out: host, render_px^2 * 4 bytes.
  * render_px must divide height (upstream indexes out of range otherwise). */
 int nbody_render_rgba(nbody_ctx* ctx, uint32_t height, uint32_t render_px, uint8_t* rgba_out);
+/* The frame with the tracers in it: draw() of the rows followed by the context's tracers, in upload order, as rows n .. n+m-1
+ * of weight 1.  A tracer is a light row: it adds 10 to its pixel's alpha (saturating at 250 with the light bodies there),
+ * colours the pixel if it is the last light row on it, and never turns a heavy body's green pixel.  Without tracers the frame
+ * is nbody_render_rgba's.  Arguments as nbody_render_rgba; the row packing holds 2^24 rows, so n + m > 2^24 is refused before
+ * anything is launched (the message names "tracers"), as nbody_render_rgba refuses n > 2^24.  NBODY_ERR_INVALID also: ctx
+ * NULL, a context made by nbody_create_multi*. */
+int nbody_render_rgba_tracers(nbody_ctx* ctx, uint32_t height, uint32_t render_px, uint8_t* rgba_out);
 /* Same on caller-owned device arrays and stream (n <= 2^24 rows; work_u32: 2 * render_px^2 u32 scratch;
  * rgba_dev: render_px^2 * 4 bytes).  Asynchronous. */
 int nbody_render_rgba_dev(void* stream, int64_t n, int is_f64, const void* pos_xy, const void* vel_xy, const void* weight_u32,

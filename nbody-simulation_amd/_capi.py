@@ -112,11 +112,18 @@ _SIGS = {
     "nbody_snapshot_pending": (C.c_int, [_vp]),
     "nbody_snapshot_end_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
     "nbody_snapshot_end_f64": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
+    "nbody_snapshot_num_tracers": (_i64, [_vp]),
+    "nbody_snapshot_tracers_f32": (C.c_int, [_vp, _vp, _vp]),
+    "nbody_snapshot_tracers_f64": (C.c_int, [_vp, _vp, _vp]),
     "nbody_delta_begin": (C.c_int, [_vp]),
     "nbody_delta_pending": (C.c_int, [_vp]),
     "nbody_delta_end": (C.c_int, [_vp, _vp, _sz, C.POINTER(_sz), C.POINTER(C.c_uint64)]),
     "nbody_delta_reset": (C.c_int, [_vp]),
     "nbody_delta_bound": (_sz, [_i64, C.c_int]),
+    "nbody_tracers_delta_begin": (C.c_int, [_vp]),
+    "nbody_tracers_delta_pending": (C.c_int, [_vp]),
+    "nbody_tracers_delta_end": (C.c_int, [_vp, _vp, _sz, C.POINTER(_sz), C.POINTER(C.c_uint64)]),
+    "nbody_tracers_delta_reset": (C.c_int, [_vp]),
     "nbody_delta_decoder_create": (_vp, []),
     "nbody_delta_decoder_destroy": (None, [_vp]),
     "nbody_delta_decoder_apply": (C.c_int, [_vp, _vp, _sz]),
@@ -128,6 +135,7 @@ _SIGS = {
     "nbody_delta_decoder_positions_f32": (C.c_int, [_vp, _vp]),
     "nbody_delta_decoder_positions_f64": (C.c_int, [_vp, _vp]),
     "nbody_render_rgba": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp]),
+    "nbody_render_rgba_tracers": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp]),
     "nbody_render_rgba_dev": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
     "nbody_selftest_exact_sum": (C.c_int, [_vp, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int64)]),
     "nbody_selftest_exact_sum_f64": (C.c_int, [_vp, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
@@ -617,6 +625,18 @@ class Context:
         check(self.h, f(self.h, _ptr(pos), _ptr(vel), _ptr(w), _ptr(ids), C.byref(step)))
         return pos, vel, w, ids, step.value
 
+    def snapshot_tracers(self):
+        """-> (position[m,2], velocity[m,2]) of the tracers the context held at snapshot_begin, in upload order; the snapshot
+        stays pending (snapshot_end takes the bodies)."""
+        m = int(self.lib.nbody_snapshot_num_tracers(self.h))
+        if m < 0:
+            raise _err(self.h, m)
+        dt = self.dtype
+        pos, vel = np.zeros((m, 2), dt), np.zeros((m, 2), dt)
+        f = self.lib.nbody_snapshot_tracers_f64 if dt == np.float64 else self.lib.nbody_snapshot_tracers_f32
+        check(self.h, f(self.h, _ptr(pos), _ptr(vel)))
+        return pos, vel
+
     def delta_begin(self):
         """Encode the positions (id order) against the previous delta snapshot and start the stream's hand-off."""
         check(self.h, self.lib.nbody_delta_begin(self.h))
@@ -636,10 +656,31 @@ class Context:
     def delta_reset(self):
         check(self.h, self.lib.nbody_delta_reset(self.h))
 
-    def render(self, height=100_000, render_px=1250):
-        """The reference's draw() of the current rows -> uint8 array (render_px, render_px, 4), RGBA."""
+    def tracers_delta_begin(self):
+        """delta_begin for the tracers' positions (upload order): a sequence of streams of its own, beside the bodies'."""
+        check(self.h, self.lib.nbody_tracers_delta_begin(self.h))
+
+    def tracers_delta_pending(self) -> bool:
+        return self.lib.nbody_tracers_delta_pending(self.h) == 1
+
+    def tracers_delta_end(self, cap=None):
+        """-> (the tracers' stream as bytes, steps done when it was taken); a second DeltaDecoder decodes the sequence."""
+        if cap is None:   # sized for the tracers the context holds now; pass `cap` if they were replaced since the begin
+            cap = int(self.lib.nbody_delta_bound(self.n_tracers, 1 if self.dtype == np.float64 else 0))
+        buf = np.zeros(max(int(cap), 1), np.uint8)
+        size, step = _sz(0), C.c_uint64(0)
+        check(self.h, self.lib.nbody_tracers_delta_end(self.h, _ptr(buf), int(cap), C.byref(size), C.byref(step)))
+        return buf[:size.value].tobytes(), step.value
+
+    def tracers_delta_reset(self):
+        check(self.h, self.lib.nbody_tracers_delta_reset(self.h))
+
+    def render(self, height=100_000, render_px=1250, tracers=False):
+        """The reference's draw() of the current rows -> uint8 array (render_px, render_px, 4), RGBA.  tracers=True: of the
+        rows followed by the tracers as rows of weight 1 (nbody_render_rgba_tracers)."""
         out = np.zeros((render_px, render_px, 4), np.uint8)
-        check(self.h, self.lib.nbody_render_rgba(self.h, int(height), int(render_px), _ptr(out)))
+        f = self.lib.nbody_render_rgba_tracers if tracers else self.lib.nbody_render_rgba
+        check(self.h, f(self.h, int(height), int(render_px), _ptr(out)))
         return out
 
     def last_build_on_device(self) -> bool:

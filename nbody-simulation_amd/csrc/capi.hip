@@ -95,7 +95,7 @@ template <class T> int upload(nbody_ctx* c, int64_t n, const T* pos, const T* ve
   free_state(c->sd);
   free_tracers(c);  // a new world
   c->has_f32 = c->has_f64 = false;
-  c->dl_key_next = true;  // new bodies: the next delta snapshot starts a sequence
+  c->dl.key_next = true;  // new bodies: the next delta snapshot starts a sequence
   State<T>& s = state_of<T>(c);
   using T2 = typename State<T>::T2;
   s.n = n;
@@ -188,6 +188,7 @@ template <class T> int tracers_upload(nbody_ctx* c, int64_t m, const T* pos, con
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   free_tracers(c);
+  c->tdl.key_next = true;  // new tracers: their next delta snapshot starts a sequence
   if (m == 0) return NBODY_OK;
   Tracers& tr = c->tracers;
   const size_t bytes = (size_t)m * sizeof(T2);

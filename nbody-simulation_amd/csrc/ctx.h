@@ -98,6 +98,24 @@ struct Tracers {
   uint8_t* mark = nullptr;
 };
 
+// One sequence of delta snapshots (delta_snapshot.hip): three key arrays in rotation (this / previous / the one before), the pieces
+// of the stream on the device, the assembled stream in pinned memory.
+struct DeltaStream {
+  void* keys[3] = {nullptr, nullptr, nullptr};
+  int cur = 0;
+  uint8_t* widths = nullptr;
+  uint32_t *words = nullptr, *offsets = nullptr;
+  void* scan = nullptr;
+  size_t scan_bytes = 0;
+  uint64_t *payload = nullptr, *total = nullptr, *htotal = nullptr;
+  uint8_t* host = nullptr;
+  int64_t n = -1;  // elements the buffers are sized for
+  int bits = 0;
+  bool key_next = true, pending = false;
+  size_t stream_bytes = 0;
+  uint64_t step = 0;
+};
+
 // The `uniform_mass` argument of the direct step for this state: > 0 all equal, < 0 all equal to its magnitude but a few, 0 neither.
 template <class T> inline float direct_mass_hint(const State<T>& s) { return s.uniform_mass > 0.f ? s.uniform_mass : -s.sparse_base; }
 
@@ -198,21 +216,12 @@ struct nbody_ctx {
   size_t snap_bytes2 = 0;  // bytes of one position array the staging holds
   int64_t snap_n = 0;
   bool snap_f64 = false;
-  // delta snapshots (delta_snapshot.hip): three key arrays in rotation (this / previous / the one before), the pieces
-  // of the stream on the device, the assembled stream in pinned memory
-  void* dl_keys[3] = {nullptr, nullptr, nullptr};
-  int dl_cur = 0;
-  uint8_t* dl_widths = nullptr;
-  uint32_t *dl_words = nullptr, *dl_offsets = nullptr;
-  void* dl_scan = nullptr;
-  size_t dl_scan_bytes = 0;
-  uint64_t *dl_payload = nullptr, *dl_total = nullptr, *dl_htotal = nullptr;
-  uint8_t* dl_host = nullptr;
-  int64_t dl_n = -1;
-  int dl_bits = 0;
-  bool dl_key_next = true, dl_pending = false;
-  size_t dl_stream_bytes = 0;
-  uint64_t dl_step = 0;
+  // ... and of the tracers the context held at begin (nbody_snapshot_tracers_*); the staging grows with m
+  void *snap_tpos = nullptr, *snap_tvel = nullptr, *snap_htpos = nullptr, *snap_htvel = nullptr;
+  size_t snap_tcap = 0;    // bytes each of the four holds
+  int64_t snap_m = 0;      // tracers of the pending snapshot
+  nbody::DeltaStream dl;   // delta snapshots of the bodies' positions, in id order
+  nbody::DeltaStream tdl;  // ... and of the tracers', in upload order: a sequence of its own (nbody_tracers_delta_*)
   uint8_t* frame_rgba = nullptr;
   uint32_t frame_px = 0;
   unsigned long long last_stats[3] = {0, 0, 0};

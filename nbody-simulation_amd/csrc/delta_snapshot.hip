@@ -28,6 +28,17 @@ __global__ __launch_bounds__(256) void delta_scatter(int64_t n, int64_t npad, co
   out[npad + id] = delta_key(p[1]);
 }
 
+// the same for rows that are in id order already (the tracers: upload order for ever)
+template <class T> __global__ __launch_bounds__(256) void delta_keys_in_order(int64_t n, int64_t npad, const void* pos, void* cur) {
+  using K = typename KeyOf<T>::type;
+  const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (row >= n) return;
+  const K* p = reinterpret_cast<const K*>(pos) + 2 * row;
+  K* out = reinterpret_cast<K*>(cur);
+  out[row] = delta_key(p[0]);
+  out[npad + row] = delta_key(p[1]);
+}
+
 __device__ __forceinline__ uint32_t wave_or(uint32_t v) {
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) v |= (uint32_t)__shfl_xor((int)v, d, 64);
@@ -107,7 +118,10 @@ hipError_t launch_delta_encode(hipStream_t s, int64_t n, const void* pos, const 
   using K = typename KeyOf<T>::type;
   if (n <= 0) return hipMemsetAsync(total, 0, 8, s);
   const int64_t nblk = (int64_t)delta_blocks(n), npad = nblk * 64;
-  hipLaunchKernelGGL((delta_scatter<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, npad, pos, ids, cur);
+  if (ids)
+    hipLaunchKernelGGL((delta_scatter<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, npad, pos, ids, cur);
+  else
+    hipLaunchKernelGGL((delta_keys_in_order<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, npad, pos, cur);
   const dim3 grid((unsigned)((nblk + 3) / 4));
   hipLaunchKernelGGL((delta_widths<K>), grid, dim3(256), 0, s, nblk, npad, (const K*)cur, (const K*)prev, (const K*)prev2, widths,
                      words);

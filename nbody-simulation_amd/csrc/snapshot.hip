@@ -24,12 +24,24 @@ using namespace nbody;
     }                                            \
   } while (0)
 
+// What every call that hands tracers out refuses first: no context, or one that fronts several devices (those hold no tracers).
+static int tracers_handoff_check(const nbody_ctx* c, const char* what) {
+  if (!c) return fail(nullptr, NBODY_ERR_INVALID, std::string(what) + ": the context is NULL (tracers)");
+  if (c->multi)
+    return fail(const_cast<nbody_ctx*>(c), NBODY_ERR_INVALID, std::string(what) + ": tracers are not available on a context made by nbody_create_multi");
+  return NBODY_OK;
+}
+
 // ---- snapshot hand-off (main.rs:136-139) --------------------------------------------------------------------------
 void nbody::free_snapshot(nbody_ctx* c) {
   free_dev(c->snap_pos); free_dev(c->snap_vel); free_dev(c->snap_w); free_dev(c->snap_ids);
   free_host(c->snap_hpos); free_host(c->snap_hvel); free_host(c->snap_hw); free_host(c->snap_hids);
+  free_dev(c->snap_tpos); free_dev(c->snap_tvel);
+  free_host(c->snap_htpos); free_host(c->snap_htvel);
   c->snap_bytes2 = 0;
+  c->snap_tcap = 0;
   c->snap_n = 0;
+  c->snap_m = 0;
   c->snap_pending = false;
 }
 template <class T> int snapshot_begin(nbody_ctx* c, State<T>& s) {
@@ -50,22 +62,48 @@ template <class T> int snapshot_begin(nbody_ctx* c, State<T>& s) {
     c->snap_n = s.n;
     c->snap_bytes2 = b2;
   }
+  // the tracers the context holds now go with the rows (nbody_snapshot_tracers_*)
+  const Tracers& tr = c->tracers;
+  const size_t tb = (size_t)tr.m * sizeof(T2);
+  if (c->snap_tcap < tb) {
+    free_dev(c->snap_tpos); free_dev(c->snap_tvel);
+    free_host(c->snap_htpos); free_host(c->snap_htvel);
+    c->snap_tcap = 0;
+    HIPCHK(c, hipMalloc(&c->snap_tpos, tb));
+    HIPCHK(c, hipMalloc(&c->snap_tvel, tb));
+    HIPCHK(c, hipHostMalloc(&c->snap_htpos, tb, hipHostMallocDefault));
+    HIPCHK(c, hipHostMalloc(&c->snap_htvel, tb, hipHostMallocDefault));
+    c->snap_tcap = tb;
+  }
   c->snap_f64 = sizeof(T) == 8;
   auto& st = s.set[s.cur];
+  // the rows (and the tracers) are copied aside on the stream the steps run on (ordered after the last step, microseconds), so
+  // that later steps may overwrite them; the slow leg to the host runs on its own stream, alongside those steps
   if (n) {
-    // the rows are copied aside on the stream the steps run on (ordered after the last step, microseconds), so that
-    // later steps may overwrite them; the slow leg to the host runs on its own stream, alongside those steps
     HIPCHK(c, hipMemcpyAsync(c->snap_pos, st.pos, b2, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->snap_vel, st.vel, b2, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->snap_w, st.weight, n * 4, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->snap_ids, st.ids, n * 4, hipMemcpyDeviceToDevice, c->stream));
+  }
+  if (tb) {
+    HIPCHK(c, hipMemcpyAsync(c->snap_tpos, tr.pos, tb, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->snap_tvel, tr.vel, tb, hipMemcpyDeviceToDevice, c->stream));
+  }
+  if (n || tb) {
     HIPCHK(c, hipEventRecord(c->snap_event, c->stream));
     HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->snap_event, 0));
+  }
+  if (n) {
     HIPCHK(c, hipMemcpyAsync(c->snap_hpos, c->snap_pos, b2, hipMemcpyDeviceToHost, c->copy_stream));
     HIPCHK(c, hipMemcpyAsync(c->snap_hvel, c->snap_vel, b2, hipMemcpyDeviceToHost, c->copy_stream));
     HIPCHK(c, hipMemcpyAsync(c->snap_hw, c->snap_w, n * 4, hipMemcpyDeviceToHost, c->copy_stream));
     HIPCHK(c, hipMemcpyAsync(c->snap_hids, c->snap_ids, n * 4, hipMemcpyDeviceToHost, c->copy_stream));
   }
+  if (tb) {
+    HIPCHK(c, hipMemcpyAsync(c->snap_htpos, c->snap_tpos, tb, hipMemcpyDeviceToHost, c->copy_stream));
+    HIPCHK(c, hipMemcpyAsync(c->snap_htvel, c->snap_tvel, tb, hipMemcpyDeviceToHost, c->copy_stream));
+  }
+  c->snap_m = tr.m;
   c->snap_step = c->steps_done;
   c->snap_pending = true;
   return NBODY_OK;
@@ -107,55 +145,80 @@ NB_API int nbody_snapshot_end_f64(nbody_ctx* c, double* pos, double* vel, uint32
   return snapshot_end(c, true, pos, vel, w, ids, step);
 }
 
-// ---- delta snapshots (the commented experiment of main.rs:107-134; format: delta_codec.h) -------------------------
-void nbody::free_delta(nbody_ctx* c) {
-  for (auto& k : c->dl_keys) free_dev(k);
-  free_dev(c->dl_widths); free_dev(c->dl_words); free_dev(c->dl_offsets); free_dev(c->dl_scan); free_dev(c->dl_payload);
-  free_dev(c->dl_total);
-  free_host(c->dl_host); free_host(c->dl_htotal);
-  c->dl_n = -1;
-  c->dl_bits = 0;
-  c->dl_key_next = true;
-  c->dl_pending = false;
+NB_API int64_t nbody_snapshot_num_tracers(const nbody_ctx* c) {
+  const int rc = tracers_handoff_check(c, "snapshot_num_tracers");
+  if (rc) return rc;
+  return c->snap_pending ? c->snap_m : 0;
 }
-template <class T> int delta_begin(nbody_ctx* c, State<T>& s) {
+// The pending snapshot's tracers: as they were at begin, whatever happened to the context's tracers since.  Does not end the snapshot.
+static int snapshot_tracers(nbody_ctx* c, bool f64, void* pos, void* vel) {
+  const int rc = tracers_handoff_check(c, "snapshot_tracers");
+  if (rc) return rc;
+  if (!c->snap_pending) return fail(c, NBODY_ERR_INVALID, "snapshot_tracers: no snapshot pending");
+  if (c->snap_f64 != f64) return fail(c, NBODY_ERR_INVALID, "snapshot_tracers: the pending snapshot has the other precision");
+  if (c->snap_m == 0) return NBODY_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->copy_stream));
+  const size_t tb = (size_t)c->snap_m * 2 * (f64 ? sizeof(double) : sizeof(float));
+  if (pos) std::memcpy(pos, c->snap_htpos, tb);
+  if (vel) std::memcpy(vel, c->snap_htvel, tb);
+  return NBODY_OK;
+}
+NB_API int nbody_snapshot_tracers_f32(nbody_ctx* c, float* pos, float* vel) { return snapshot_tracers(c, false, pos, vel); }
+NB_API int nbody_snapshot_tracers_f64(nbody_ctx* c, double* pos, double* vel) { return snapshot_tracers(c, true, pos, vel); }
+
+// ---- delta snapshots (the commented experiment of main.rs:107-134; format: delta_codec.h) -------------------------
+static void free_delta_stream(DeltaStream& d) {
+  for (auto& k : d.keys) free_dev(k);
+  free_dev(d.widths); free_dev(d.words); free_dev(d.offsets); free_dev(d.scan); free_dev(d.payload);
+  free_dev(d.total);
+  free_host(d.host); free_host(d.htotal);
+  d.n = -1;
+  d.bits = 0;
+  d.key_next = true;
+  d.pending = false;
+}
+void nbody::free_delta(nbody_ctx* c) {
+  free_delta_stream(c->dl);
+  free_delta_stream(c->tdl);
+}
+// One stream of the sequence `d`: n positions of precision T, put in id order by `ids` (nullptr: they are in id order).
+template <class T> int delta_begin(nbody_ctx* c, DeltaStream& d, int64_t n, const void* pos, const uint32_t* ids) {
   const int bits = (int)sizeof(T) * 8;
-  const int64_t n = s.n;
   const size_t nblk = delta_blocks(n), npad = nblk * 64, kb = 2 * npad * sizeof(T), wb = delta_width_bytes(n);
-  if (c->dl_n != n || c->dl_bits != bits) {
-    free_delta(c);
-    for (auto& k : c->dl_keys) HIPCHK(c, hipMalloc(&k, kb ? kb : 8));
-    HIPCHK(c, hipMalloc((void**)&c->dl_widths, wb ? wb : 8));
-    HIPCHK(c, hipMalloc((void**)&c->dl_words, 2 * nblk * 4 + 8));
-    HIPCHK(c, hipMalloc((void**)&c->dl_offsets, 2 * nblk * 4 + 8));
-    c->dl_scan_bytes = delta_scan_temp_bytes(n);
-    HIPCHK(c, hipMalloc(&c->dl_scan, c->dl_scan_bytes ? c->dl_scan_bytes : 8));
-    HIPCHK(c, hipMalloc((void**)&c->dl_payload, 2 * nblk * (size_t)bits * 8 + 8));
-    HIPCHK(c, hipMalloc((void**)&c->dl_total, 8));
-    HIPCHK(c, hipHostMalloc((void**)&c->dl_host, delta_bound(n, bits), hipHostMallocDefault));
-    HIPCHK(c, hipHostMalloc((void**)&c->dl_htotal, 8, hipHostMallocDefault));
-    if (wb) HIPCHK(c, hipMemsetAsync(c->dl_widths, 0, wb, c->stream));  // the padding bytes stay zero
-    c->dl_n = n;
-    c->dl_bits = bits;
-    c->dl_key_next = true;
+  if (d.n != n || d.bits != bits) {
+    free_delta_stream(d);
+    for (auto& k : d.keys) HIPCHK(c, hipMalloc(&k, kb ? kb : 8));
+    HIPCHK(c, hipMalloc((void**)&d.widths, wb ? wb : 8));
+    HIPCHK(c, hipMalloc((void**)&d.words, 2 * nblk * 4 + 8));
+    HIPCHK(c, hipMalloc((void**)&d.offsets, 2 * nblk * 4 + 8));
+    d.scan_bytes = delta_scan_temp_bytes(n);
+    HIPCHK(c, hipMalloc(&d.scan, d.scan_bytes ? d.scan_bytes : 8));
+    HIPCHK(c, hipMalloc((void**)&d.payload, 2 * nblk * (size_t)bits * 8 + 8));
+    HIPCHK(c, hipMalloc((void**)&d.total, 8));
+    HIPCHK(c, hipHostMalloc((void**)&d.host, delta_bound(n, bits), hipHostMallocDefault));
+    HIPCHK(c, hipHostMalloc((void**)&d.htotal, 8, hipHostMallocDefault));
+    if (wb) HIPCHK(c, hipMemsetAsync(d.widths, 0, wb, c->stream));  // the padding bytes stay zero
+    d.n = n;
+    d.bits = bits;
+    d.key_next = true;
   }
-  const bool key = c->dl_key_next;
+  const bool key = d.key_next;
   if (key && kb)
-    for (auto& k : c->dl_keys) HIPCHK(c, hipMemsetAsync(k, 0, kb, c->stream));
-  void* cur = c->dl_keys[c->dl_cur];
-  const void* prev = c->dl_keys[(c->dl_cur + 2) % 3];
-  const void* prev2 = c->dl_keys[(c->dl_cur + 1) % 3];
-  auto& st = s.set[s.cur];
-  HIPCHK(c, launch_delta_encode<T>(c->stream, n, st.pos, st.ids, cur, prev, prev2, c->dl_widths, c->dl_words, c->dl_offsets,
-                                   c->dl_scan, c->dl_scan_bytes, c->dl_payload, c->dl_total));
+    for (auto& k : d.keys) HIPCHK(c, hipMemsetAsync(k, 0, kb, c->stream));
+  void* cur = d.keys[d.cur];
+  const void* prev = d.keys[(d.cur + 2) % 3];
+  const void* prev2 = d.keys[(d.cur + 1) % 3];
+  HIPCHK(c, launch_delta_encode<T>(c->stream, n, pos, ids, cur, prev, prev2, d.widths, d.words, d.offsets, d.scan, d.scan_bytes,
+                                   d.payload, d.total));
   HIPCHK(c, hipEventRecord(c->snap_event, c->stream));
   HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->snap_event, 0));
   // the size of the stream is known on the device only: fetch it, then start the transfer proper (which later steps overlap)
-  HIPCHK(c, hipMemcpyAsync(c->dl_htotal, c->dl_total, 8, hipMemcpyDeviceToHost, c->copy_stream));
+  HIPCHK(c, hipMemcpyAsync(d.htotal, d.total, 8, hipMemcpyDeviceToHost, c->copy_stream));
   HIPCHK(c, hipStreamSynchronize(c->copy_stream));
-  const uint64_t total = *c->dl_htotal;
+  const uint64_t total = *d.htotal;
   if (total > 2 * nblk * (uint64_t)bits) return fail(c, NBODY_ERR_HIP, "delta_begin: the encoder reported an impossible size");
-  uint8_t* h = c->dl_host;
+  uint8_t* h = d.host;
   std::memset(h, 0, kDeltaHeader);
   h[0] = 'N'; h[1] = 'B'; h[2] = 'D'; h[3] = '1';
   h[4] = (uint8_t)bits;
@@ -164,45 +227,82 @@ template <class T> int delta_begin(nbody_ctx* c, State<T>& s) {
   std::memcpy(h + 8, &n64, 8);
   std::memcpy(h + 16, &step, 8);
   std::memcpy(h + 24, &total, 8);
-  if (wb) HIPCHK(c, hipMemcpyAsync(h + kDeltaHeader, c->dl_widths, wb, hipMemcpyDeviceToHost, c->copy_stream));
-  if (total) HIPCHK(c, hipMemcpyAsync(h + kDeltaHeader + wb, c->dl_payload, total * 8, hipMemcpyDeviceToHost, c->copy_stream));
-  c->dl_stream_bytes = kDeltaHeader + wb + (size_t)total * 8;
-  c->dl_cur = (c->dl_cur + 1) % 3;  // the oldest keys are overwritten next time
-  c->dl_key_next = false;
-  c->dl_step = step;
-  c->dl_pending = true;
+  if (wb) HIPCHK(c, hipMemcpyAsync(h + kDeltaHeader, d.widths, wb, hipMemcpyDeviceToHost, c->copy_stream));
+  if (total) HIPCHK(c, hipMemcpyAsync(h + kDeltaHeader + wb, d.payload, total * 8, hipMemcpyDeviceToHost, c->copy_stream));
+  d.stream_bytes = kDeltaHeader + wb + (size_t)total * 8;
+  d.cur = (d.cur + 1) % 3;  // the oldest keys are overwritten next time
+  d.key_next = false;
+  d.step = step;
+  d.pending = true;
+  return NBODY_OK;
+}
+static int delta_end(nbody_ctx* c, DeltaStream& d, const char* what, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* step_out) {
+  if (!d.pending) return fail(c, NBODY_ERR_INVALID, std::string(what) + ": no stream pending");
+  if (bytes_out) *bytes_out = d.stream_bytes;
+  if (step_out) *step_out = d.step;
+  if (!out || cap < d.stream_bytes) return fail(c, NBODY_ERR_INVALID, std::string(what) + ": the output buffer is smaller than the stream");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->copy_stream));
+  std::memcpy(out, d.host, d.stream_bytes);
+  d.pending = false;
   return NBODY_OK;
 }
 NB_API int nbody_delta_begin(nbody_ctx* c) {
   if (!c) return NBODY_ERR_INVALID;
   NB_VIA_PRIMARY(c, false, nbody_delta_begin(p));
   if (!c->has_f32 && !c->has_f64) return fail(c, NBODY_ERR_INVALID, "delta_begin: no particles uploaded");
-  if (c->dl_pending) return fail(c, NBODY_ERR_INVALID, "delta_begin: a stream is still pending (take it with nbody_delta_end)");
+  if (c->dl.pending) return fail(c, NBODY_ERR_INVALID, "delta_begin: a stream is still pending (take it with nbody_delta_end)");
   HIPCHK(c, hipSetDevice(c->device));
-  return c->has_f32 ? delta_begin<float>(c, c->sf) : delta_begin<double>(c, c->sd);
+  if (c->has_f32) {
+    auto& st = c->sf.set[c->sf.cur];
+    return delta_begin<float>(c, c->dl, c->sf.n, st.pos, st.ids);
+  }
+  auto& st = c->sd.set[c->sd.cur];
+  return delta_begin<double>(c, c->dl, c->sd.n, st.pos, st.ids);
 }
 NB_API int nbody_delta_pending(const nbody_ctx* c) {
   if (c && c->multi) return nbody_delta_pending(nbody::multi_peek(c));
-  return c && c->dl_pending ? 1 : 0;
+  return c && c->dl.pending ? 1 : 0;
 }
 NB_API int nbody_delta_end(nbody_ctx* c, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* step_out) {
   if (!c) return NBODY_ERR_INVALID;
   NB_VIA_FIRST(c, nbody_delta_end(p, out, cap, bytes_out, step_out));
-  if (!c->dl_pending) return fail(c, NBODY_ERR_INVALID, "delta_end: no stream pending");
-  if (bytes_out) *bytes_out = c->dl_stream_bytes;
-  if (step_out) *step_out = c->dl_step;
-  if (!out || cap < c->dl_stream_bytes) return fail(c, NBODY_ERR_INVALID, "delta_end: the output buffer is smaller than the stream");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->copy_stream));
-  std::memcpy(out, c->dl_host, c->dl_stream_bytes);
-  c->dl_pending = false;
-  return NBODY_OK;
+  return delta_end(c, c->dl, "delta_end", out, cap, bytes_out, step_out);
 }
 NB_API int nbody_delta_reset(nbody_ctx* c) {
   if (!c) return NBODY_ERR_INVALID;
   NB_VIA_FIRST(c, nbody_delta_reset(p));
-  if (c->dl_pending) return fail(c, NBODY_ERR_INVALID, "delta_reset: a stream is still pending");
-  c->dl_key_next = true;
+  if (c->dl.pending) return fail(c, NBODY_ERR_INVALID, "delta_reset: a stream is still pending");
+  c->dl.key_next = true;
+  return NBODY_OK;
+}
+
+// The tracers' positions as a second sequence of the same format: the header's count is m, the order the upload's.
+NB_API int nbody_tracers_delta_begin(nbody_ctx* c) {
+  const int rc = tracers_handoff_check(c, "tracers_delta_begin");
+  if (rc) return rc;
+  if (c->tracers.m == 0) return fail(c, NBODY_ERR_INVALID, "tracers_delta_begin: the context holds no tracers");
+  if (c->tdl.pending)
+    return fail(c, NBODY_ERR_INVALID, "tracers_delta_begin: a tracers stream is still pending (take it with nbody_tracers_delta_end)");
+  HIPCHK(c, hipSetDevice(c->device));
+  return c->has_f32 ? delta_begin<float>(c, c->tdl, c->tracers.m, c->tracers.pos, nullptr)
+                    : delta_begin<double>(c, c->tdl, c->tracers.m, c->tracers.pos, nullptr);
+}
+NB_API int nbody_tracers_delta_pending(const nbody_ctx* c) {
+  const int rc = tracers_handoff_check(c, "tracers_delta_pending");
+  if (rc) return rc;
+  return c->tdl.pending ? 1 : 0;
+}
+NB_API int nbody_tracers_delta_end(nbody_ctx* c, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* step_out) {
+  const int rc = tracers_handoff_check(c, "tracers_delta_end");
+  if (rc) return rc;
+  return delta_end(c, c->tdl, "tracers_delta_end", out, cap, bytes_out, step_out);
+}
+NB_API int nbody_tracers_delta_reset(nbody_ctx* c) {
+  const int rc = tracers_handoff_check(c, "tracers_delta_reset");
+  if (rc) return rc;
+  if (c->tdl.pending) return fail(c, NBODY_ERR_INVALID, "tracers_delta_reset: a tracers stream is still pending");
+  c->tdl.key_next = true;
   return NBODY_OK;
 }
 NB_API size_t nbody_delta_bound(int64_t n, int is_f64) { return n < 0 ? 0 : delta_bound(n, is_f64 ? 64 : 32); }
@@ -237,16 +337,17 @@ NB_API int nbody_delta_decoder_positions_f64(const nbody_delta_decoder* d, doubl
   return d && d->d.positions<double, uint64_t>(pos) ? NBODY_OK : NBODY_ERR_INVALID;
 }
 
-template <class T> int render_rows(nbody_ctx* c, State<T>& s, uint32_t height, uint32_t render_px, uint8_t* rgba_out) {
+template <class T> int render_rows(nbody_ctx* c, State<T>& s, bool tracers, uint32_t height, uint32_t render_px, uint8_t* rgba_out) {
   auto& st = s.set[s.cur];
-  HIPCHK(c, launch_render<T>(c->stream, s.n, st.pos, st.vel, st.weight, height, render_px, c->frame_work, c->frame_rgba));
+  const Tracers& tr = c->tracers;
+  HIPCHK(c, launch_render_tracers<T>(c->stream, s.n, st.pos, st.vel, st.weight, tracers ? tr.m : 0, tr.pos, tr.vel, height, render_px,
+                                     c->frame_work, c->frame_rgba));
   HIPCHK(c, hipMemcpyAsync(rgba_out, c->frame_rgba, (size_t)render_px * render_px * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return NBODY_OK;
 }
-NB_API int nbody_render_rgba(nbody_ctx* c, uint32_t height, uint32_t render_px, uint8_t* rgba_out) {
-  if (!c) return NBODY_ERR_INVALID;
-  NB_VIA_PRIMARY(c, false, nbody_render_rgba(p, height, render_px, rgba_out));
+// What nbody_render_rgba and nbody_render_rgba_tracers share, past the handle: the arguments, the frame's buffers, the frame.
+static int render_frame(nbody_ctx* c, bool tracers, uint32_t height, uint32_t render_px, uint8_t* rgba_out) {
   if (!rgba_out) return fail(c, NBODY_ERR_INVALID, "render: null output");
   if (!c->has_f32 && !c->has_f64) return fail(c, NBODY_ERR_INVALID, "render: no particles uploaded");
   // main.rs:51-52 divide by HEIGHT / RENDER_HEIGHT: a cell of 0 world units or a last cell past the frame is an
@@ -255,6 +356,7 @@ NB_API int nbody_render_rgba(nbody_ctx* c, uint32_t height, uint32_t render_px, 
     return fail(c, NBODY_ERR_INVALID, "render: render_px must divide height (both > 0, height <= 2^24, render_px <= 16384)");
   const int64_t n = c->has_f32 ? c->sf.n : c->sd.n;
   if (n > (1 << 24)) return fail(c, NBODY_ERR_INVALID, "render: more than 2^24 rows");
+  if (tracers && n + c->tracers.m > (1 << 24)) return fail(c, NBODY_ERR_INVALID, "render: more than 2^24 rows, bodies and tracers together");
   HIPCHK(c, hipSetDevice(c->device));
   if (c->frame_px != render_px) {
     free_dev(c->frame_work); free_dev(c->frame_rgba);
@@ -263,7 +365,18 @@ NB_API int nbody_render_rgba(nbody_ctx* c, uint32_t height, uint32_t render_px, 
     HIPCHK(c, hipMalloc((void**)&c->frame_rgba, (size_t)render_px * render_px * 4));
     c->frame_px = render_px;
   }
-  return c->has_f32 ? render_rows<float>(c, c->sf, height, render_px, rgba_out) : render_rows<double>(c, c->sd, height, render_px, rgba_out);
+  return c->has_f32 ? render_rows<float>(c, c->sf, tracers, height, render_px, rgba_out)
+                    : render_rows<double>(c, c->sd, tracers, height, render_px, rgba_out);
+}
+NB_API int nbody_render_rgba(nbody_ctx* c, uint32_t height, uint32_t render_px, uint8_t* rgba_out) {
+  if (!c) return NBODY_ERR_INVALID;
+  NB_VIA_PRIMARY(c, false, nbody_render_rgba(p, height, render_px, rgba_out));
+  return render_frame(c, false, height, render_px, rgba_out);
+}
+NB_API int nbody_render_rgba_tracers(nbody_ctx* c, uint32_t height, uint32_t render_px, uint8_t* rgba_out) {
+  const int rc = tracers_handoff_check(c, "render");
+  if (rc) return rc;
+  return render_frame(c, true, height, render_px, rgba_out);
 }
 NB_API int nbody_render_rgba_dev(void* stream, int64_t n, int is_f64, const void* pos_xy, const void* vel_xy, const void* weight_u32,
                                  uint32_t height, uint32_t render_px, void* work_u32, void* rgba_dev) {

@@ -84,6 +84,11 @@ class World:
         """-> (position, velocity, weight, ids, updates) of the pending snapshot."""
         return self.ctx.snapshot_end()
 
+    def snapshot_tracers(self):
+        """-> (position[m,2], velocity[m,2]) of the tracers as they were at snapshot_begin, in the order they were given; call it
+        before snapshot_end, which ends the snapshot."""
+        return self.ctx.snapshot_tracers()
+
     def delta_begin(self):
         """Like snapshot_begin, but hands over only what changed: the positions, in id order, as a lossless stream
         of the change against the previous delta snapshot (the idea of the commented experiment, main.rs:107-134)."""
@@ -93,14 +98,24 @@ class World:
         """-> (stream bytes, updates); feed the streams in order to a `DeltaDecoder`."""
         return self.ctx.delta_end()
 
-    def frame(self, height=100_000, render_px=1250):
-        """The frame the reference's render thread would draw from these particles (`draw`, main.rs:41-72):
-        uint8 array (render_px, render_px, 4), RGBA."""
-        return self.ctx.render(height, render_px)
+    def tracers_delta_begin(self):
+        """delta_begin for the tracers' positions, in the order they were given: a sequence of its own, independent of the
+        bodies' (one of each may be pending at once)."""
+        self.ctx.tracers_delta_begin()
 
-    def save_frame(self, path, height=100_000, render_px=1250):
+    def tracers_delta_end(self):
+        """-> (stream bytes, updates); feed the streams in order to a `DeltaDecoder` kept for the tracers."""
+        return self.ctx.tracers_delta_end()
+
+    def frame(self, height=100_000, render_px=1250, tracers=False):
+        """The frame the reference's render thread would draw from these particles (`draw`, main.rs:41-72):
+        uint8 array (render_px, render_px, 4), RGBA.  `tracers=True`: from the particles followed by the tracers, each a
+        particle of weight 1."""
+        return self.ctx.render(height, render_px, tracers)
+
+    def save_frame(self, path, height=100_000, render_px=1250, tracers=False):
         """Write the frame as an RGBA PNG (what the reference shows in its window)."""
-        write_png(path, self.frame(height, render_px))
+        write_png(path, self.frame(height, render_px, tracers))
 
     def close(self):
         self.ctx.close()
