@@ -1,0 +1,58 @@
+/*
+ * nbody_ensemble.h — the ensemble calls of the C ABI of include/nbody_hip.h (which includes this file where its types are
+ * complete: include nbody_hip.h, not this).  New symbols under NBODY_ABI_VERSION 3; conventions as nbody_hip.h states them.
+ */
+#ifndef NBODY_ENSEMBLE_H
+#define NBODY_ENSEMBLE_H
+#ifndef NBODY_HIP_H
+#error "include nbody_hip.h: it includes nbody_ensemble.h after the types these declarations need"
+#endif
+
+/* ---- ensembles: many small worlds of one size, stepped together ------------------------------------------------
+ * The same scene under many seeds, a sweep over initial conditions, many independent clusters: worlds too small to fill the
+ * device one at a time (below a few thousand bodies a direct step is a handful of launches that cannot occupy it, whatever the
+ * kernel does).  An ensemble holds n_worlds worlds of n_bodies bodies each in world-major device arrays and steps ALL of them
+ * with one launch per step: the grid runs over worlds x target tiles and every block stages its world's sources whole in LDS.
+ * The handle is opaque and its own (no nbody_ctx is involved); it belongs to one host thread at a time; calls are synchronous.
+ *   Step.  Every world takes the step of nbody_update_direct_f32, independently of the others: a_i = sum_j
+ *     calculate_gravity(p_i, p_j, w_j) over the bodies of its own world, j ascending (main.rs:234-253), then main.rs:419-423
+ *     (multiply then add, no contraction).  Rows never move, so there are no ids.
+ *   Limits.  1 <= n_bodies <= 4096 (a world's positions and masses are 48 KB at the top size and stage whole in LDS; above
+ *     that a context per world is the tool — where the crossover lies is unmeasured), n_worlds >= 1, n_worlds * n_bodies <= 2^26.
+ *     Anything outside gives NBODY_ERR_INVALID before anything is allocated, and the message names "ensemble".
+ *   EXACT.  Every world is bit-identical to the CPU restatement's update_direct of that world alone.
+ *   FAST.  Every body within the tolerance of DESIGN.md (2e-5 of sum_j |term_ij|): one v_rcp_f32 per pair, fused multiply-adds,
+ *     the 2^-90 biased denominator.
+ *   AUTO.  FAST, decided per world, per step, on the device: a world takes EXACT for a step when one of its positions is outside
+ *     FAST's domain (non-finite, >= 2^60 in magnitude, or non-zero below 2^-22) at the start of that step; with a clamp below
+ *     2^-19, or NaN, every world takes EXACT (FAST asked for by name, too).  Nothing is read back and there is no host
+ *     synchronisation between the steps of a call.
+ *   Independence.  A world's bits depend only on its own rows, n_bodies and the params: not on the number of worlds, its index
+ *     among them, the other worlds' contents or routes, nor on how the steps are split over calls.  This holds for FAST too: its
+ *     summation order is a fixed function of n_bodies.
+ *   Trivial calls and errors.  n_steps == 0 is a no-op; an update, accel or download before an upload is NBODY_ERR_INVALID.  There
+ *     is no CPU fallback: without a gfx950 device nbody_ensemble_create fails with NBODY_ERR_NO_DEVICE.  A NULL handle gives
+ *     NBODY_ERR_INVALID (0 from nbody_ensemble_num_worlds / _num_bodies).  nbody_ensemble_last_error(NULL): the last failed
+ *     nbody_ensemble_create on this thread.
+ *   Booking.  Force and integration are fused, so the whole call's seconds are booked under sum_gravity, as the direct step
+ *     books them (`counter` may be NULL).
+ *   Params.  nbody_default_params' values at creation; clamp and arith are used, the rest is kept and ignored.
+ *   Not offered: f64; worlds of different sizes; a per-world delta or clamp; tree methods; tracers; several devices; snapshots,
+ *     delta streams and frames of an ensemble; hipGraph replay.  The library reads no environment variable for any of this.
+ * Arrays are world-major, [n_worlds][n_bodies] rows, pos / vel interleaved x,y; weight may be NULL (all 1); an upload replaces
+ * the previous ensemble, whatever its shape. */
+typedef struct nbody_ensemble nbody_ensemble;
+int nbody_ensemble_create(nbody_ensemble** out, int device_id);
+void nbody_ensemble_destroy(nbody_ensemble* e);
+const char* nbody_ensemble_last_error(const nbody_ensemble* e);
+int nbody_ensemble_set_params(nbody_ensemble* e, const nbody_params* p);
+int nbody_ensemble_get_params(const nbody_ensemble* e, nbody_params* out);
+int nbody_ensemble_upload_f32(nbody_ensemble* e, int64_t n_worlds, int64_t n_bodies, const float* pos_xy, const float* vel_xy,
+                              const uint32_t* weight);
+int nbody_ensemble_download_f32(nbody_ensemble* e, float* pos_xy, float* vel_xy); /* either may be NULL */
+int64_t nbody_ensemble_num_worlds(const nbody_ensemble* e);
+int64_t nbody_ensemble_num_bodies(const nbody_ensemble* e);                       /* per world */
+int nbody_ensemble_update_f32(nbody_ensemble* e, float delta, int n_steps, nbody_counting* counter);
+int nbody_ensemble_accel_f32(nbody_ensemble* e, float* acc_xy);                   /* force only, state untouched */
+
+#endif /* NBODY_ENSEMBLE_H */

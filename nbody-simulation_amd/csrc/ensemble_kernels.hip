@@ -1,0 +1,207 @@
+// Ensemble step: worlds x target tiles in one launch, a world's sources staged whole in LDS (ensemble_kernels.h).
+//
+// What every world computes is the direct step (direct_kernels.hip):
+//   a_i = sum_j calculate_gravity(p_i, p_j, w_j) over the bodies of its own world      src/main.rs:234-253
+//   v_i += a_i*dt ; x_i += v_i*dt                                                        src/main.rs:419-423
+// EXACT  one thread per target, one ascending-j chain of pair_as_written<float> (pair.h: IEEE divide through div_pair, the
+//        is_normal skip, no contraction): bit-identical to the oracle's update_direct of that world alone.
+// FAST   direct_kernels.hip's pair (one v_rcp_f32, fused multiply-adds, the 2^-90 biased denominator) over source COUPLES
+//        {xA, xB, yA, yB}: every multiply-add is a packed op over two sources (a packed op fills its 4-cycle
+//        issue slot with two values per lane); per couple 2 v_pk_add, 2 v_pk_mul, 4 v_pk_fma, 2 v_add, 2 v_max, 2 v_rcp.
+//        Order of additions, a function of n_bodies alone: with SPLIT = ensemble_split(n) lanes per target, lane `part` takes
+//        the couples part, part + SPLIT, ... in ascending order; the even and the odd sources of its couples are summed apart,
+//        64 couples at a time (two-level summation: each run of 64 couples is added as one value to the lane's running
+//        total, even half first); the SPLIT totals meet in a butterfly — lanes ^1, ^2, mirrored within 8, ^8, rows of 16, halves
+//        of the wave — whose additions are commutative pairs, so every lane of the group ends with the same bits.
+//        Worst case 64 + 32 + 6 roundings of 2^-24 on sum |term| at n = 4096 (6e-6), against the 2e-5 of tests/_tol.py.
+// AUTO   every block of a world stages all of that world's rows, so it sees every position of the world: the block-wide OR of
+//        outside_fast() over the rows it loads IS the world's decision for this step, the same in each of the world's blocks.
+//        No flag buffer, no extra kernel, nothing read back.
+// Padding: an odd n leaves the last couple's second source at (0, 0) with mass 0: FAST adds exactly 0 for it (s = 0 * rcp),
+// EXACT never reads it.  Lanes past the end of a world compute target 0 again (the butterfly needs every lane) and store nothing.
+//
+// This translation unit is compiled with -ffp-contract=off: nothing fuses unless written as an fma.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/nbody_hip.h"
+#include "ensemble_kernels.h"
+#include "fast_domain.h"
+#include "pair.h"
+
+namespace nbody {
+namespace {
+
+typedef float ens_v2f __attribute__((ext_vector_type(2)));
+typedef float ens_v4f __attribute__((ext_vector_type(4)));
+
+constexpr float kEnsDenBias = 8.0779356694631609e-28f;  // 2^-90, as direct_kernels.hip
+constexpr int kEnsRun = 64;                              // couples of one lane summed on their own before they join its total
+
+// |a| + |b| as ONE v_add_f32 with abs modifiers (left to itself the compiler packs the add and pays four v_and for the moduli)
+__device__ __forceinline__ float ens_abs_sum(float a, float b) {
+  float r;
+  asm("v_add_f32 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+
+template <int CTRL> __device__ __forceinline__ float ens_dpp(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
+}
+// v_permlane16_swap / v_permlane32_swap through inline asm, as walk_split.hip does (the s_nop covers "VALU writes a VGPR, a
+// permlane swap reads it"): with both operands a copy of r, the sum of the two results is r of this row + r of its neighbour
+// row (rows 0|1, 2|3), resp. r of this half + r of the other half of the wave.
+__device__ __forceinline__ float ens_add_neighbour_row(float r) {
+  float a = r, b = r;
+  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+  return a + b;
+}
+__device__ __forceinline__ float ens_add_other_half(float r) {
+  float a = r, b = r;
+  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+  return a + b;
+}
+// The total of r over the SPLIT consecutive lanes of a group, in every one of them.
+template <int SPLIT> __device__ __forceinline__ float ens_group_sum(float r) {
+  if constexpr (SPLIT >= 2) r = r + ens_dpp<0xB1>(r);    // quad_perm [1,0,3,2]
+  if constexpr (SPLIT >= 4) r = r + ens_dpp<0x4E>(r);    // quad_perm [2,3,0,1]
+  if constexpr (SPLIT >= 8) r = r + ens_dpp<0x141>(r);   // row_half_mirror
+  if constexpr (SPLIT >= 16) r = r + ens_dpp<0x128>(r);  // row_ror:8
+  if constexpr (SPLIT >= 32) r = ens_add_neighbour_row(r);
+  if constexpr (SPLIT >= 64) r = ens_add_other_half(r);
+  return r;
+}
+
+// main.rs:419-423, multiply then add, no contraction (TU flag); `row` is the body's row among all worlds.
+__device__ __forceinline__ void ens_integrate(const EnsembleArgs& a, size_t row, float px, float py, float ax, float ay) {
+  if (a.acc_out) a.acc_out[row] = make_float2(ax, ay);
+  if (a.vel) {
+    float2 v = a.vel[row];
+    v.x = v.x + ax * a.delta;
+    v.y = v.y + ay * a.delta;
+    const float sx = v.x * a.delta, sy = v.y * a.delta;
+    a.vel[row] = v;
+    a.pos_out[row] = make_float2(px + sx, py + sy);
+  }
+}
+
+template <int SPLIT>
+__global__ __launch_bounds__(kEnsembleBlock) void ensemble_step(const EnsembleArgs a) {
+  constexpr int TPB = kEnsembleBlock / SPLIT;  // targets per block
+  extern __shared__ __attribute__((aligned(16))) unsigned char ens_lds[];
+  const int n = a.n_bodies;
+  const int nc = (n + 1) >> 1;  // couples
+  float* const cplf = reinterpret_cast<float*>(ens_lds);
+  const ens_v4f* const cpl = reinterpret_cast<const ens_v4f*>(ens_lds);
+  float* const massf = cplf + 4 * nc;
+  const ens_v2f* const mass2 = reinterpret_cast<const ens_v2f*>(massf);
+
+  const unsigned world = blockIdx.x / a.tiles, tile = blockIdx.x - world * a.tiles;
+  const size_t row0 = (size_t)world * (size_t)n;
+
+  // ---- the world's sources into LDS, and its AUTO decision on the way
+  int bad = 0;
+  for (int s = (int)threadIdx.x; s < 2 * nc; s += kEnsembleBlock) {
+    float2 p = make_float2(0.f, 0.f);
+    float m = 0.f;
+    if (s < n) {
+      p = a.pos_in[row0 + s];
+      m = a.mass[row0 + s];
+      bad |= (int)outside_fast(p.x) | (int)outside_fast(p.y);
+    }
+    const int o = 4 * (s >> 1) + (s & 1);
+    cplf[o] = p.x;
+    cplf[o + 2] = p.y;
+    massf[s] = m;
+  }
+  const int hazard = __syncthreads_or(a.arith == NBODY_ARITH_AUTO ? bad : 0);
+  const float clamp = a.clamp;
+
+  if (a.arith == NBODY_ARITH_EXACT || hazard) {
+    // ---- EXACT: thread = target, j ascending (no barrier follows: threads without a target leave)
+    if ((int)threadIdx.x >= TPB) return;
+    const int t = (int)tile * TPB + (int)threadIdx.x;
+    if (t >= n) return;
+    const int ot = 4 * (t >> 1) + (t & 1);
+    const float px = cplf[ot], py = cplf[ot + 2];
+    float ax = 0.f, ay = 0.f;
+    for (int c = 0; c < (n >> 1); ++c) {
+      const ens_v4f s = cpl[c];
+      const ens_v2f m = mass2[c];
+      pair_as_written<float>(px, py, s.x, s.z, m.x, clamp, ax, ay);
+      pair_as_written<float>(px, py, s.y, s.w, m.y, clamp, ax, ay);
+    }
+    if (n & 1) {
+      const ens_v4f s = cpl[nc - 1];
+      pair_as_written<float>(px, py, s.x, s.z, massf[n - 1], clamp, ax, ay);
+    }
+    ens_integrate(a, row0 + t, px, py, ax, ay);
+    return;
+  }
+
+  // ---- FAST: SPLIT consecutive lanes per target
+  const int part = (int)threadIdx.x % SPLIT;
+  const int t = (int)tile * TPB + (int)threadIdx.x / SPLIT;
+  const bool live = t < n;
+  const int ot = live ? 4 * (t >> 1) + (t & 1) : 0;
+  const float px = cplf[ot], py = cplf[ot + 2];
+  const ens_v2f tx = {px, px}, ty = {py, py};
+  const ens_v2f bias = {kEnsDenBias, kEnsDenBias};
+  float ax = 0.f, ay = 0.f;
+  for (int c0 = part; c0 < nc; c0 += SPLIT * kEnsRun) {
+    const int c1 = c0 + SPLIT * kEnsRun < nc ? c0 + SPLIT * kEnsRun : nc;
+    ens_v2f accx = {0.f, 0.f}, accy = {0.f, 0.f};
+    auto couple = [&](int c) {
+      const ens_v4f s = cpl[c];
+      const ens_v2f m = mass2[c];
+      const ens_v2f dx = s.xy - tx, dy = s.zw - ty;
+      ens_v2f d2 = __builtin_elementwise_fma(dy, dy, dx * dx);
+      const ens_v2f sum = {ens_abs_sum(dx.x, dy.x), ens_abs_sum(dx.y, dy.y)};
+      d2.x = __builtin_fmaxf(d2.x, clamp);
+      d2.y = __builtin_fmaxf(d2.y, clamp);
+      const ens_v2f den = __builtin_elementwise_fma(sum, d2, bias);
+      const ens_v2f r = {__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
+      const ens_v2f sc = m * r;
+      accx = __builtin_elementwise_fma(dx, sc, accx);
+      accy = __builtin_elementwise_fma(dy, sc, accy);
+    };
+    int c = c0;
+    for (; c + 3 * SPLIT < c1; c += 4 * SPLIT) {  // (unrolled by hand: a loop with an asm statement in it is not unrolled for us)
+      couple(c);
+      couple(c + SPLIT);
+      couple(c + 2 * SPLIT);
+      couple(c + 3 * SPLIT);
+    }
+    for (; c < c1; c += SPLIT) couple(c);
+    ax = ax + (accx.x + accx.y);
+    ay = ay + (accy.x + accy.y);
+  }
+  ax = ens_group_sum<SPLIT>(ax);
+  ay = ens_group_sum<SPLIT>(ay);
+  if (live && part == 0) ens_integrate(a, row0 + t, px, py, ax, ay);
+}
+
+}  // namespace
+
+hipError_t launch_ensemble_step(hipStream_t s, int64_t n_worlds, EnsembleArgs a) {
+  if (n_worlds < 1 || a.n_bodies < 1 || a.n_bodies > kEnsembleMaxBodies || n_worlds * a.n_bodies > kEnsembleMaxRows) return hipErrorInvalidValue;
+  const int split = ensemble_split(a.n_bodies);
+  const int tpb = kEnsembleBlock / split;
+  a.tiles = (unsigned)((a.n_bodies + tpb - 1) / tpb);
+  const dim3 grid((unsigned)(n_worlds * a.tiles));  // <= 2^26 blocks
+  const size_t lds = ensemble_lds_bytes(a.n_bodies);
+#define NB_ENS_GO(S) hipLaunchKernelGGL(ensemble_step<S>, grid, dim3(kEnsembleBlock), lds, s, a)
+  switch (split) {
+    case 1: NB_ENS_GO(1); break;
+    case 2: NB_ENS_GO(2); break;
+    case 4: NB_ENS_GO(4); break;
+    case 8: NB_ENS_GO(8); break;
+    case 16: NB_ENS_GO(16); break;
+    case 32: NB_ENS_GO(32); break;
+    default: NB_ENS_GO(64); break;
+  }
+#undef NB_ENS_GO
+  return hipGetLastError();
+}
+
+}  // namespace nbody
