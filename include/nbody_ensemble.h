@@ -37,8 +37,9 @@
  *   Booking.  Force and integration are fused, so the whole call's seconds are booked under sum_gravity, as the direct step
  *     books them (`counter` may be NULL).
  *   Params.  nbody_default_params' values at creation; clamp and arith are used, the rest is kept and ignored.
- *   Not offered: f64; worlds of different sizes; a per-world delta or clamp; tree methods; tracers; several devices; snapshots,
- *     delta streams and frames of an ensemble; hipGraph replay.  The library reads no environment variable for any of this.
+ *   Not offered: f64 on this handle (nbody_ensemble64_* below is the double-precision sibling); worlds of different sizes; a
+ *     per-world delta or clamp; tree methods; tracers; several devices; snapshots, delta streams and frames of an ensemble;
+ *     hipGraph replay.  The library reads no environment variable for any of this.
  * Arrays are world-major, [n_worlds][n_bodies] rows, pos / vel interleaved x,y; weight may be NULL (all 1); an upload replaces
  * the previous ensemble, whatever its shape. */
 typedef struct nbody_ensemble nbody_ensemble;
@@ -54,5 +55,35 @@ int64_t nbody_ensemble_num_worlds(const nbody_ensemble* e);
 int64_t nbody_ensemble_num_bodies(const nbody_ensemble* e);                       /* per world */
 int nbody_ensemble_update_f32(nbody_ensemble* e, float delta, int n_steps, nbody_counting* counter);
 int nbody_ensemble_accel_f32(nbody_ensemble* e, float* acc_xy);                   /* force only, state untouched */
+
+/* ---- ensembles in f64: the double-precision sibling, a handle of its own ------------------------------------------
+ * Everything above holds with these differences (limits, conventions, errors, booking and the "not offered" list are the same;
+ * a study of how fast neighbouring trajectories separate wants a state whose own rounding does not decide the answer).
+ *   Step.  Every world takes the step of nbody_update_direct_f64: the pair of main.rs:234-253 in T = double (two correctly
+ *     rounded divisions, no contraction, the is_normal skip), mass `weight as f64`, the clamp params.clamp widened to double,
+ *     then main.rs:419-423, multiply then add.
+ *   EXACT and AUTO.  One ascending-j chain of IEEE additions per target: every world is bit-identical to the CPU restatement's
+ *     update_direct of that world alone on float64 arrays.  AUTO is EXACT, as it is for an f64 context.
+ *   FAST (opt-in).  |a - a_ref|_1 <= 1e-12 * sum_j |term_ij|_1 per body: v_rcp_f64 plus one Newton step, fused
+ *     multiply-adds, the 2^-700 biased denominator.  Gated per world, per step, on the device: a world with a position outside
+ *     the f64 FAST domain (non-finite, >= 2^100 in magnitude, or non-zero below 2^-300) at the start of a step takes EXACT for
+ *     that step; with a clamp that is not > 0, or NaN, every world takes EXACT.  FAST's order of additions is a fixed function
+ *     of n_bodies (ensemble64_kernels.hip), so independence holds for it too.
+ *   Staging.  A world's positions and u32 weights are 80 KB of LDS at n_bodies = 4096 (two blocks are the CU's 160 KB exactly:
+ *     the kernel uses no other LDS).
+ *   The two handles are independent: an nbody_ensemble and an nbody_ensemble64 (and contexts) may be used side by side. */
+typedef struct nbody_ensemble64 nbody_ensemble64;
+int nbody_ensemble64_create(nbody_ensemble64** out, int device_id);
+void nbody_ensemble64_destroy(nbody_ensemble64* e);
+const char* nbody_ensemble64_last_error(const nbody_ensemble64* e);
+int nbody_ensemble64_set_params(nbody_ensemble64* e, const nbody_params* p);
+int nbody_ensemble64_get_params(const nbody_ensemble64* e, nbody_params* out);
+int nbody_ensemble64_upload(nbody_ensemble64* e, int64_t n_worlds, int64_t n_bodies, const double* pos_xy, const double* vel_xy,
+                            const uint32_t* weight);
+int nbody_ensemble64_download(nbody_ensemble64* e, double* pos_xy, double* vel_xy); /* either may be NULL */
+int64_t nbody_ensemble64_num_worlds(const nbody_ensemble64* e);
+int64_t nbody_ensemble64_num_bodies(const nbody_ensemble64* e);                     /* per world */
+int nbody_ensemble64_update(nbody_ensemble64* e, double delta, int n_steps, nbody_counting* counter);
+int nbody_ensemble64_accel(nbody_ensemble64* e, double* acc_xy);                    /* force only, state untouched */
 
 #endif /* NBODY_ENSEMBLE_H */

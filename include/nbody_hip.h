@@ -56,7 +56,8 @@ extern "C" {
  *    tracers that step with the bodies) likewise: new symbols only; nbody_render_rgba_tracers, nbody_snapshot_num_tracers,
  *    nbody_snapshot_tracers_f32 / _f64 and nbody_tracers_delta_begin / _pending / _end / _reset (the tracers in the frame, the
  *    snapshot and a delta stream of their own) likewise: new symbols only; nbody_ensemble_* (many small worlds stepped
- *    together, on a handle of their own) likewise: new symbols only;
+ *    together, on a handle of their own) likewise: new symbols only; nbody_ensemble64_* (the same in double precision, a
+ *    second handle) likewise: new symbols only;
  *    a binding compares nbody_abi_version() with the value it was written against before it binds anything else. */
 #define NBODY_ABI_VERSION 3
 
@@ -257,8 +258,9 @@ int nbody_tracers_download_f32(nbody_ctx* ctx, float* pos_xy, float* vel_xy);
 int nbody_tracers_download_f64(nbody_ctx* ctx, double* pos_xy, double* vel_xy);
 int64_t nbody_num_tracers(const nbody_ctx* ctx);
 
-/* ---- ensembles: many small worlds of one size, stepped together in one launch per step (nbody_ensemble_*) --------
- * A handle of their own and a header of their own, part of this ABI: declared and documented in nbody_ensemble.h. */
+/* ---- ensembles: many small worlds of one size, stepped together in one launch per step (nbody_ensemble_* in f32,
+ * nbody_ensemble64_* in f64) -------- A handle of their own each and a header of their own, part of this ABI: declared and
+ * documented in nbody_ensemble.h. */
 #include "nbody_ensemble.h"
 
 /* Linearised tree of the last build (pre-order; node i's first child is i+1; `skip` is the pre-order index

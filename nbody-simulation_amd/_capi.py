@@ -99,6 +99,17 @@ _SIGS = {
     "nbody_ensemble_num_bodies": (_i64, [_vp]),
     "nbody_ensemble_update_f32": (C.c_int, [_vp, _f32, _i32, C.POINTER(Counting)]),
     "nbody_ensemble_accel_f32": (C.c_int, [_vp, _vp]),
+    "nbody_ensemble64_create": (C.c_int, [C.POINTER(_vp), _i32]),
+    "nbody_ensemble64_destroy": (None, [_vp]),
+    "nbody_ensemble64_last_error": (C.c_char_p, [_vp]),
+    "nbody_ensemble64_set_params": (C.c_int, [_vp, C.POINTER(Params)]),
+    "nbody_ensemble64_get_params": (C.c_int, [_vp, C.POINTER(Params)]),
+    "nbody_ensemble64_upload": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    "nbody_ensemble64_download": (C.c_int, [_vp, _vp, _vp]),
+    "nbody_ensemble64_num_worlds": (_i64, [_vp]),
+    "nbody_ensemble64_num_bodies": (_i64, [_vp]),
+    "nbody_ensemble64_update": (C.c_int, [_vp, _f64, _i32, C.POINTER(Counting)]),
+    "nbody_ensemble64_accel": (C.c_int, [_vp, _vp]),
     "nbody_accel_tree_f32": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_accel_tree_f64": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_tree_info": (C.c_int, [_vp, C.POINTER(TreeView)]),
@@ -826,6 +837,71 @@ class EnsembleHandle:
         b, n = self.shape
         acc = np.zeros((b, n, 2), np.float32)
         self._check(self.lib.nbody_ensemble_accel_f32(self.h, _ptr(acc)))
+        return acc
+
+
+class Ensemble64Handle:
+    """Owner of one nbody_ensemble64 (one GPU): many worlds of one size, world-major float64 arrays, every step of all of them one
+    launch (nbody_ensemble64_*, the f64 sibling of EnsembleHandle).  Arrays come in contiguous and checked (ensemble.py does that); this class only passes them on."""
+
+    def __init__(self, device: int = 0):
+        self.lib = load()
+        self.h = _vp()
+        rc = self.lib.nbody_ensemble64_create(C.byref(self.h), int(device))
+        if rc != OK:
+            self.h = None
+            raise self._err(rc)
+
+    def _err(self, code):
+        msg = self.lib.nbody_ensemble64_last_error(self.h)
+        return NBodyError(code, msg.decode() if msg else "")
+
+    def _check(self, code):
+        if code != OK:
+            raise self._err(code)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.nbody_ensemble64_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def get_params(self) -> Params:
+        p = Params()
+        self._check(self.lib.nbody_ensemble64_get_params(self.h, C.byref(p)))
+        return p
+
+    def set_params(self, **kw):
+        p = self.get_params()
+        for k, v in kw.items():
+            if not hasattr(p, k):
+                raise AttributeError(k)
+            setattr(p, k, v)
+        self._check(self.lib.nbody_ensemble64_set_params(self.h, C.byref(p)))
+
+    @property
+    def shape(self):
+        """(worlds, bodies per world) of the current upload; (0, 0) before one."""
+        return int(self.lib.nbody_ensemble64_num_worlds(self.h)), int(self.lib.nbody_ensemble64_num_bodies(self.h))
+
+    def upload(self, n_worlds, n_bodies, pos, vel, weight):
+        self._check(self.lib.nbody_ensemble64_upload(self.h, int(n_worlds), int(n_bodies), _ptr(pos), _ptr(vel), _ptr(weight)))
+
+    def download(self):
+        b, n = self.shape
+        pos, vel = np.zeros((b, n, 2), np.float64), np.zeros((b, n, 2), np.float64)
+        self._check(self.lib.nbody_ensemble64_download(self.h, _ptr(pos), _ptr(vel)))
+        return pos, vel
+
+    def update(self, delta, n_steps=1, counter: "Counting | None" = None):
+        self._check(self.lib.nbody_ensemble64_update(self.h, float(delta), int(n_steps),
+                                                       C.byref(counter) if counter is not None else None))
+
+    def accel(self):
+        b, n = self.shape
+        acc = np.zeros((b, n, 2), np.float64)
+        self._check(self.lib.nbody_ensemble64_accel(self.h, _ptr(acc)))
         return acc
 
 

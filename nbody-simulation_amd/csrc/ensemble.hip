@@ -2,11 +2,11 @@
 // size in world-major device arrays, every step of all of them one launch of ensemble_kernels.hip on the handle's stream.
 // The positions are double-buffered across steps (a world's other blocks still read the old ones), velocities are updated in
 // place.  No CPU path and no host synchronisation between the steps of a call.
-#include <cstring>
 #include <new>
 #include <vector>
 
 #include "driver.h"
+#include "ensemble_host.h"
 #include "ensemble_kernels.h"
 
 using namespace nbody;
@@ -63,40 +63,27 @@ EnsembleArgs ens_args(const nbody_ensemble* e) {
 NB_API int nbody_ensemble_create(nbody_ensemble** out, int device_id) {
   if (!out) return ens_fail(nullptr, NBODY_ERR_INVALID, "nbody_ensemble_create: out is NULL");
   *out = nullptr;
-  int count = 0;
-  hipError_t h = hipGetDeviceCount(&count);
-  if (h != hipSuccess || count <= 0)
-    return ens_fail(nullptr, NBODY_ERR_NO_DEVICE,
-                    std::string("nbody_ensemble_create: no HIP device (") + (h != hipSuccess ? hipGetErrorString(h) : "count 0") +
-                        "); this library has no CPU path");
-  if (device_id < 0 || device_id >= count) return ens_fail(nullptr, NBODY_ERR_INVALID, "nbody_ensemble_create: device_id out of range");
-  hipDeviceProp_t prop;
-  h = hipGetDeviceProperties(&prop, device_id);
-  if (h != hipSuccess) return ens_fail_hip(nullptr, h, "hipGetDeviceProperties");
-  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return ens_fail(nullptr, NBODY_ERR_NO_DEVICE, std::string("nbody_ensemble_create: device is ") + prop.gcnArchName +
-                                                      ", kernels are built for gfx950 (MI355X) only");
+  hipStream_t stream = nullptr;
+  std::string msg;
+  const int rc = ensemble_open_device("nbody_ensemble_create", device_id, &stream, msg);
+  if (rc != NBODY_OK) return ens_fail(nullptr, rc, msg);
   nbody_ensemble* e = new (std::nothrow) nbody_ensemble();
-  if (!e) return ens_fail(nullptr, NBODY_ERR_NOMEM, "nbody_ensemble_create: out of host memory");
-  e->device = device_id;
-  nbody_default_params(&e->params);
-  h = hipSetDevice(device_id);
-  if (h == hipSuccess) h = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
-  if (h != hipSuccess) {
-    const int rc = ens_fail_hip(nullptr, h, "nbody_ensemble_create");
-    delete e;
-    return rc;
+  if (!e) {
+    ensemble_close_stream(stream);
+    return ens_fail(nullptr, NBODY_ERR_NOMEM, "nbody_ensemble_create: out of host memory");
   }
+  e->device = device_id;
+  e->stream = stream;
+  nbody_default_params(&e->params);
   *out = e;
   return NBODY_OK;
 }
 
 NB_API void nbody_ensemble_destroy(nbody_ensemble* e) {
   if (!e) return;
-  (void)hipSetDevice(e->device);
-  if (e->stream) (void)hipStreamSynchronize(e->stream);
+  ensemble_drain(e->device, e->stream);
   ens_free(e);
-  if (e->stream) (void)hipStreamDestroy(e->stream);
+  ensemble_close_stream(e->stream);
   delete e;
 }
 

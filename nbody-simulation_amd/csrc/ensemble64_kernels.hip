@@ -1,0 +1,238 @@
+// Ensemble step in f64: worlds x target tiles in one launch, a world's sources staged whole in LDS (ensemble64_kernels.h).
+//
+// What every world computes is the f64 direct step (direct64.hip):
+//   a_i = sum_j calculate_gravity(p_i, p_j, w_j as f64) over the bodies of its own world, in double      src/main.rs:234-253
+//   v_i += a_i*dt ; x_i += v_i*dt                                                                        src/main.rs:419-423
+// EXACT  one thread per target.  The terms of kEns64TermBlock sources are evaluated first, branch-free (pair_term_select,
+//        pair.h: two IEEE divisions, the is_normal skip as a select), and then added in ascending j — one chain of IEEE
+//        additions per target, bit-identical to the oracle's update_direct of that world alone; the block's division chains
+//        are independent and overlap (the kernel is bound by the two compiler-expanded f64 divisions per pair).  The pad that
+//        completes the last term block has NaN positions: its pairs are skipped, a -0.0 term, the identity of IEEE addition.
+// FAST   pair_fast(double...) of pair.h: v_rcp_f64 plus one Newton step, fused multiply-adds, the 2^-700 biased denominator.
+//        Order of additions, a function of n_bodies alone: with SPLIT = ensemble_split(n) lanes per target, lane `part` takes
+//        the sources part, part + SPLIT, part + 2 SPLIT, ... in ascending order, kEns64Run = 64 of them at a time (a run).
+//        Within a run the lane's 1st, 3rd, ... source accumulate by fma into one sum and its 2nd, 4th, ... into another (two
+//        independent chains); the run ends with total = total + (sum_odd_places + sum_even_places) — two-level summation.
+//        The SPLIT totals then meet in a butterfly — lanes ^1, ^2, mirrored within 8, ^8, rows of 16, halves of the wave —
+//        each step the sum of a value and its partner's (the same two operands in both lanes), so every lane of the group
+//        ends with the same bits.  A 64-bit value crosses lanes as two 32-bit DPP / permlane moves.
+//        Rounding count, worst case n = 4096 (SPLIT 1, 64 runs): 32 fma roundings inside a run's chain, 1 to join its two
+//        chains, 64 to add the runs: 97 roundings of 2^-53 on sum |term|, 1.08e-14.  (Smaller n: at most 32 + 1 + ceil(n /
+//        (64 SPLIT)) + log2 SPLIT, never more.)  A FAST term differs from the reference's by at most 16 roundings (fma'd
+//        d2 and denominator, reciprocal + Newton <= 2 ulp, force * r, against the reference's two products, sum, product and
+//        division; the bias is below 2^-199 of any denominator, direct64.h).  (97 + 16) * 2^-53 = 1.25e-14 of sum |term|
+//        from the exact sum of the reference's terms; the oracle's own double chain that the tests compare with is within
+//        4095 * 2^-53 = 4.55e-13 of that sum in the worst case, so 4.7e-13 against it — a bound, under the contract's 1e-12.
+//        Lanes past the end of a world compute target 0 again (the butterfly needs every lane) and store nothing; FAST reads
+//        no padding.
+// Route  FAST is opt-in (args.fast).  Every block of a world stages all of that world's rows, so it sees every position of the
+//        world: the block-wide OR of outside_fast() over the rows it loads IS the world's decision for this step, the same in
+//        each of the world's blocks.  No flag buffer, no extra kernel, nothing read back.  The OR goes through one borrowed
+//        word of the staged weights and plain barriers, not __syncthreads_or: the kernel has no static LDS at all.
+//
+// This translation unit is compiled with -ffp-contract=off: nothing fuses unless written as an fma.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <atomic>
+
+#include "../../include/nbody_hip.h"
+#include "ensemble64_kernels.h"
+#include "fast_domain.h"
+#include "pair.h"
+
+namespace nbody {
+namespace {
+
+constexpr int kEns64Run = 64;  // sources of one lane summed on their own before they join its total
+
+__device__ __forceinline__ double ens64_join(uint32_t lo, uint32_t hi) {
+  return __builtin_bit_cast(double, (uint64_t)lo | ((uint64_t)hi << 32));
+}
+template <int CTRL> __device__ __forceinline__ double ens64_dpp(double v) {
+  const uint64_t u = __builtin_bit_cast(uint64_t, v);
+  const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, CTRL, 0xf, 0xf, true);
+  const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), CTRL, 0xf, 0xf, true);
+  return ens64_join((uint32_t)lo, (uint32_t)hi);
+}
+// v_permlane16_swap / v_permlane32_swap as ensemble_kernels.hip uses them, once per 32-bit half: with both operands a copy of
+// r, the two results are r of the even and r of the odd row of the pair (resp. of the lower and the upper half of the wave),
+// in that order in both — their sum has the same bits in both.
+__device__ __forceinline__ double ens64_add_neighbour_row(double r) {
+  const uint64_t u = __builtin_bit_cast(uint64_t, r);
+  uint32_t alo = (uint32_t)u, blo = (uint32_t)u, ahi = (uint32_t)(u >> 32), bhi = (uint32_t)(u >> 32);
+  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\tv_permlane16_swap_b32 %2, %3" : "+v"(alo), "+v"(blo), "+v"(ahi), "+v"(bhi));
+  return ens64_join(alo, ahi) + ens64_join(blo, bhi);
+}
+__device__ __forceinline__ double ens64_add_other_half(double r) {
+  const uint64_t u = __builtin_bit_cast(uint64_t, r);
+  uint32_t alo = (uint32_t)u, blo = (uint32_t)u, ahi = (uint32_t)(u >> 32), bhi = (uint32_t)(u >> 32);
+  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\tv_permlane32_swap_b32 %2, %3" : "+v"(alo), "+v"(blo), "+v"(ahi), "+v"(bhi));
+  return ens64_join(alo, ahi) + ens64_join(blo, bhi);
+}
+// The total of r over the SPLIT consecutive lanes of a group, in every one of them.
+template <int SPLIT> __device__ __forceinline__ double ens64_group_sum(double r) {
+  if constexpr (SPLIT >= 2) r = r + ens64_dpp<0xB1>(r);    // quad_perm [1,0,3,2]
+  if constexpr (SPLIT >= 4) r = r + ens64_dpp<0x4E>(r);    // quad_perm [2,3,0,1]
+  if constexpr (SPLIT >= 8) r = r + ens64_dpp<0x141>(r);   // row_half_mirror
+  if constexpr (SPLIT >= 16) r = r + ens64_dpp<0x128>(r);  // row_ror:8
+  if constexpr (SPLIT >= 32) r = ens64_add_neighbour_row(r);
+  if constexpr (SPLIT >= 64) r = ens64_add_other_half(r);
+  return r;
+}
+
+// main.rs:419-423 in double, multiply then add, no contraction (TU flag); `row` is the body's row among all worlds.
+__device__ __forceinline__ void ens64_integrate(const Ensemble64Args& a, size_t row, double px, double py, double ax, double ay) {
+  if (a.acc_out) a.acc_out[row] = double2{ax, ay};
+  if (a.vel) {
+    double2 v = a.vel[row];
+    v.x = v.x + ax * a.delta;
+    v.y = v.y + ay * a.delta;
+    const double sx = v.x * a.delta, sy = v.y * a.delta;
+    a.vel[row] = v;
+    a.pos_out[row] = double2{px + sx, py + sy};
+  }
+}
+
+template <int SPLIT>
+__global__ __launch_bounds__(kEnsembleBlock) void ensemble64_step(const Ensemble64Args a) {
+  constexpr int TPB = kEnsembleBlock / SPLIT;  // targets per block
+  constexpr int TB = kEns64TermBlock;
+  extern __shared__ __attribute__((aligned(16))) unsigned char ens64_lds[];
+  const int n = a.n_bodies;
+  const int npad = (n + TB - 1) / TB * TB;
+  double2* const spos = reinterpret_cast<double2*>(ens64_lds);
+  uint32_t* const sw = reinterpret_cast<uint32_t*>(spos + npad);
+
+  const unsigned world = blockIdx.x / a.tiles, tile = blockIdx.x - world * a.tiles;
+  const size_t row0 = (size_t)world * (size_t)n;
+
+  // ---- the world's sources into LDS, and FAST's decision on the way
+  int bad = 0;
+  uint32_t w0 = 0;  // thread 0: the weight of source 0, whose LDS word carries the world's decision before it carries the weight
+  for (int s = (int)threadIdx.x; s < npad; s += kEnsembleBlock) {
+    double2 p = double2{__builtin_nan(""), __builtin_nan("")};
+    uint32_t w = 0;
+    if (s < n) {
+      p = a.pos_in[row0 + s];
+      w = a.weight[row0 + s];
+      bad |= (int)outside_fast(p.x) | (int)outside_fast(p.y);
+    }
+    if (a.fast && s == 0) {
+      w0 = w;
+      w = 0;
+    }
+    spos[s] = p;
+    sw[s] = w;
+  }
+  __syncthreads();
+  // The block-wide OR without __syncthreads_or: its reduction takes 256 B of static LDS, and 2 x 81 920 B of dynamic LDS are
+  // the CU's 160 KiB to the byte.  So sw[0] is borrowed: 0 from the staging, 1 from every wave that saw a position outside the
+  // domain (the same value, whoever writes), read by all, then given its weight.  (a.fast is uniform: every thread takes the
+  // same barriers.)
+  int hazard = 1;
+  if (a.fast) {
+    if (__builtin_amdgcn_ballot_w64(bad != 0) != 0 && (threadIdx.x & 63) == 0) sw[0] = 1u;
+    __syncthreads();
+    hazard = (int)sw[0];
+    __syncthreads();
+    if (threadIdx.x == 0) sw[0] = w0;
+    __syncthreads();
+  }
+  const double clamp = a.clamp;
+
+  if (hazard) {
+    // ---- EXACT: thread = target, term blocks in ascending j (no barrier follows: threads without a target leave)
+    if ((int)threadIdx.x >= TPB) return;
+    const int t = (int)tile * TPB + (int)threadIdx.x;
+    if (t >= n) return;
+    const double2 p = spos[t];
+    double ax = 0.0, ay = 0.0;
+    for (int k0 = 0; k0 < npad; k0 += TB) {
+      double2 term[TB];
+#pragma unroll
+      for (int jj = 0; jj < TB; ++jj) {  // any order of evaluation ...
+        const double2 q = spos[k0 + jj];
+        term[jj] = pair_term_select(p.x, p.y, q.x, q.y, (double)sw[k0 + jj], clamp);
+      }
+#pragma unroll
+      for (int jj = 0; jj < TB; ++jj) {  // ... one order of addition: ascending j
+        ax = ax + term[jj].x;
+        ay = ay + term[jj].y;
+      }
+    }
+    ens64_integrate(a, row0 + t, p.x, p.y, ax, ay);
+    return;
+  }
+
+  // ---- FAST: SPLIT consecutive lanes per target
+  const int part = (int)threadIdx.x % SPLIT;
+  const int t = (int)tile * TPB + (int)threadIdx.x / SPLIT;
+  const bool live = t < n;
+  const double2 p = spos[live ? t : 0];
+  const int cnt = (n - part + SPLIT - 1) / SPLIT;  // this lane's sources: part + k * SPLIT, k < cnt
+  double ax = 0.0, ay = 0.0;
+  for (int k0 = 0; k0 < cnt; k0 += kEns64Run) {
+    const int k1 = k0 + kEns64Run < cnt ? k0 + kEns64Run : cnt;
+    double x0 = 0.0, y0 = 0.0, x1 = 0.0, y1 = 0.0;
+    int s = part + k0 * SPLIT;
+    const int s1 = part + k1 * SPLIT;
+#pragma unroll 2
+    for (; s + SPLIT < s1; s += 2 * SPLIT) {
+      const double2 qa = spos[s], qb = spos[s + SPLIT];
+      pair_fast(p.x, p.y, qa.x, qa.y, (double)sw[s], clamp, x0, y0);
+      pair_fast(p.x, p.y, qb.x, qb.y, (double)sw[s + SPLIT], clamp, x1, y1);
+    }
+    if (s < s1) {
+      const double2 qa = spos[s];
+      pair_fast(p.x, p.y, qa.x, qa.y, (double)sw[s], clamp, x0, y0);
+    }
+    ax = ax + (x0 + x1);
+    ay = ay + (y0 + y1);
+  }
+  ax = ens64_group_sum<SPLIT>(ax);
+  ay = ens64_group_sum<SPLIT>(ay);
+  if (live && part == 0) ens64_integrate(a, row0 + t, p.x, p.y, ax, ay);
+}
+
+// Dynamic LDS above 64 KB (n > 3272: rows are padded to 8 and 3280 x 20 B = 65 600; the one-target-per-lane layout only) needs the function's limit raised: once per device.
+hipError_t ens64_raise_lds_limit() {
+  static std::atomic<bool> raised[64];  // (zero-initialised: false)
+  int dev = 0;
+  hipError_t h = hipGetDevice(&dev);
+  if (h != hipSuccess) return h;
+  if (dev >= 0 && dev < 64 && raised[dev]) return hipSuccess;
+  h = hipFuncSetAttribute(reinterpret_cast<const void*>(&ensemble64_step<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)ensemble64_lds_bytes(kEnsembleMaxBodies));
+  if (h == hipSuccess && dev >= 0 && dev < 64) raised[dev] = true;
+  return h;
+}
+
+}  // namespace
+
+hipError_t launch_ensemble64_step(hipStream_t s, int64_t n_worlds, Ensemble64Args a) {
+  if (n_worlds < 1 || a.n_bodies < 1 || a.n_bodies > kEnsembleMaxBodies || n_worlds * a.n_bodies > kEnsembleMaxRows) return hipErrorInvalidValue;
+  const int split = ensemble_split(a.n_bodies);
+  const int tpb = kEnsembleBlock / split;
+  a.tiles = (unsigned)((a.n_bodies + tpb - 1) / tpb);
+  const dim3 grid((unsigned)(n_worlds * a.tiles));  // <= 2^26 blocks
+  const size_t lds = ensemble64_lds_bytes(a.n_bodies);
+  if (lds > 65536) {
+    const hipError_t h = ens64_raise_lds_limit();
+    if (h != hipSuccess) return h;
+  }
+#define NB_ENS64_GO(S) hipLaunchKernelGGL(ensemble64_step<S>, grid, dim3(kEnsembleBlock), lds, s, a)
+  switch (split) {
+    case 1: NB_ENS64_GO(1); break;
+    case 2: NB_ENS64_GO(2); break;
+    case 4: NB_ENS64_GO(4); break;
+    case 8: NB_ENS64_GO(8); break;
+    case 16: NB_ENS64_GO(16); break;
+    case 32: NB_ENS64_GO(32); break;
+    default: NB_ENS64_GO(64); break;
+  }
+#undef NB_ENS64_GO
+  return hipGetLastError();
+}
+
+}  // namespace nbody

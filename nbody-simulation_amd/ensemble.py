@@ -6,7 +6,10 @@ of n bodies each (n <= 4096) on the device and steps all of them with one launch
 `World(method="direct")`, independently of the others — EXACT bit-identical to the oracle's update_direct of that world alone,
 FAST within the tolerance of DESIGN.md, AUTO choosing between them per world and per step on the device.
 
-Everything is float32.  Shapes, dtypes and the size limits are checked here, with ValueError, before a handle exists.
+`Ensemble` is float32 and takes float32 arrays only; `Ensemble64` (nbody_ensemble64_*) is its double-precision sibling with the
+same constructor and methods, float64 arrays only: every world takes the step of an f64 `World(method="direct")` — EXACT and AUTO
+bit-identical to the oracle's update_direct on float64, FAST (opt-in, per world and per step on the device) within 1e-12 of
+sum |term|.  Shapes, dtypes and the size limits are checked here, with ValueError, before a handle exists.
 """
 from __future__ import annotations
 
@@ -21,12 +24,15 @@ MAX_ROWS = 1 << 26         # worlds * bodies
 _ARITH = {"auto": _capi.ARITH_AUTO, "fast": _capi.ARITH_FAST, "exact": _capi.ARITH_EXACT}
 
 
-def _checked(position, velocity, weight):
-    """-> (B, n, position[B,n,2], velocity[B,n,2], weight[B,n] or None), contiguous; ValueError for anything else."""
+def _checked(position, velocity, weight, dtype=np.float32):
+    """-> (B, n, position[B,n,2], velocity[B,n,2], weight[B,n] or None), contiguous; ValueError for anything else.  The
+    messages name the class of that dtype: Ensemble (float32) or Ensemble64 (float64)."""
     position, velocity = np.asarray(position), np.asarray(velocity)
+    dtype = np.dtype(dtype)
+    who, other = ("Ensemble", "Ensemble64 takes float64") if dtype == np.float32 else ("Ensemble64", "Ensemble takes float32")
     for name, a in (("position", position), ("velocity", velocity)):
-        if a.dtype != np.float32:
-            raise ValueError(f"Ensemble: {name} must be float32 (got {a.dtype}); ensembles are f32 only")
+        if a.dtype != dtype:
+            raise ValueError(f"{who}: {name} must be {dtype} (got {a.dtype}); {other}")
     if position.ndim == 2:   # one world
         position = position[None]
         if velocity.ndim == 2:
@@ -34,34 +40,41 @@ def _checked(position, velocity, weight):
         if weight is not None and np.ndim(weight) == 1:
             weight = np.asarray(weight)[None]
     if position.ndim != 3 or position.shape[2] != 2:
-        raise ValueError(f"Ensemble: position must be [B, n, 2] (or [n, 2] for one world), got {position.shape}")
+        raise ValueError(f"{who}: position must be [B, n, 2] (or [n, 2] for one world), got {position.shape}")
     if velocity.shape != position.shape:
-        raise ValueError(f"Ensemble: velocity {velocity.shape} does not match position {position.shape}")
+        raise ValueError(f"{who}: velocity {velocity.shape} does not match position {position.shape}")
     b, n = position.shape[:2]
     if b < 1:
-        raise ValueError("Ensemble: at least one world")
+        raise ValueError(f"{who}: at least one world")
     if not 1 <= n <= MAX_BODIES:
-        raise ValueError(f"Ensemble: 1 .. {MAX_BODIES} bodies per world, got {n} (above that a World per world is the tool)")
+        raise ValueError(f"{who}: 1 .. {MAX_BODIES} bodies per world, got {n} (above that a World per world is the tool)")
     if b * n > MAX_ROWS:
-        raise ValueError(f"Ensemble: worlds * bodies = {b * n} exceeds 2^26")
+        raise ValueError(f"{who}: worlds * bodies = {b * n} exceeds 2^26")
     if weight is not None:
         weight = np.asarray(weight)
         if weight.shape != (b, n):
-            raise ValueError(f"Ensemble: weight must be [B, n] = {(b, n)}, got {weight.shape}")
+            raise ValueError(f"{who}: weight must be [B, n] = {(b, n)}, got {weight.shape}")
         if weight.dtype.kind not in "ui":
-            raise ValueError(f"Ensemble: weight must be an integer array (u32 upstream), got {weight.dtype}")
+            raise ValueError(f"{who}: weight must be an integer array (u32 upstream), got {weight.dtype}")
         weight = np.ascontiguousarray(weight, dtype=np.uint32)
     return b, n, np.ascontiguousarray(position), np.ascontiguousarray(velocity), weight
 
 
-class Ensemble:
+class _EnsembleBase:
+    """What Ensemble and Ensemble64 share; each names its dtype and makes its own kind of handle."""
+    _dtype = None
+
+    @staticmethod
+    def _new_handle(device):
+        raise NotImplementedError
+
     def __init__(self, position, velocity, weight=None, *, device=0, clamp=0.001, arith="auto"):
-        """position, velocity [B, n, 2] float32 (2-D: one world), weight [B, n] integers or None (all 1)."""
+        """position, velocity [B, n, 2] of the class's dtype (2-D: one world), weight [B, n] integers or None (all 1)."""
         if arith not in _ARITH:
             raise ValueError(f"arith must be one of {sorted(_ARITH)}")
         self.h = None
-        args = _checked(position, velocity, weight)
-        self.h = _capi.EnsembleHandle(device)
+        args = _checked(position, velocity, weight, self._dtype)
+        self.h = self._new_handle(device)
         self.h.set_params(clamp=float(clamp), arith=_ARITH[arith])
         self._upload(*args)
 
@@ -71,7 +84,7 @@ class Ensemble:
 
     def upload(self, position, velocity, weight=None):
         """Replaces the ensemble by another one, of any shape."""
-        self._upload(*_checked(position, velocity, weight))
+        self._upload(*_checked(position, velocity, weight, self._dtype))
 
     @property
     def shape(self):
@@ -104,3 +117,22 @@ class Ensemble:
 
     def __exit__(self, *a):
         self.close()
+
+
+class Ensemble(_EnsembleBase):
+    """The ensemble in single precision: position, velocity [B, n, 2] float32."""
+    _dtype = np.float32
+
+    @staticmethod
+    def _new_handle(device):
+        return _capi.EnsembleHandle(device)
+
+
+class Ensemble64(_EnsembleBase):
+    """The ensemble in double precision: position, velocity [B, n, 2] float64.  arith "auto" and "exact" are the exact chain;
+    "fast" is opt-in and gated per world and per step on the device; clamp is a float, widened to double by the library."""
+    _dtype = np.float64
+
+    @staticmethod
+    def _new_handle(device):
+        return _capi.Ensemble64Handle(device)
