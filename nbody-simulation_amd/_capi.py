@@ -775,20 +775,25 @@ class MultiContext(Context):
         raise NBodyError(ERR_INVALID, "download_tracers: tracers are not available on a multi-device context")
 
 
-class EnsembleHandle:
-    """Owner of one nbody_ensemble (one GPU): many worlds of one size, world-major float32 arrays, every step of all of them one
-    launch (nbody_ensemble_*).  Arrays come in contiguous and checked (ensemble.py does that); this class only passes them on."""
+class _EnsembleHandleBase:
+    """Owner of one ensemble handle of the C API (one GPU): many worlds of one size, world-major arrays of `_dtype`, every step
+    of all of them one launch.  The C calls are `_prefix` + name, the typed ones with `_suffix`.  Arrays come in contiguous and
+    checked (ensemble.py does that); this class only passes them on."""
+    _prefix = _suffix = _dtype = None
+
+    def _call(self, name, *args):
+        return getattr(self.lib, self._prefix + name)(self.h, *args)
 
     def __init__(self, device: int = 0):
         self.lib = load()
         self.h = _vp()
-        rc = self.lib.nbody_ensemble_create(C.byref(self.h), int(device))
+        rc = getattr(self.lib, self._prefix + "_create")(C.byref(self.h), int(device))
         if rc != OK:
             self.h = None
             raise self._err(rc)
 
     def _err(self, code):
-        msg = self.lib.nbody_ensemble_last_error(self.h)
+        msg = self._call("_last_error")
         return NBodyError(code, msg.decode() if msg else "")
 
     def _check(self, code):
@@ -797,14 +802,14 @@ class EnsembleHandle:
 
     def close(self):
         if getattr(self, "h", None):
-            self.lib.nbody_ensemble_destroy(self.h)
+            self._call("_destroy")
             self.h = None
 
     __del__ = close
 
     def get_params(self) -> Params:
         p = Params()
-        self._check(self.lib.nbody_ensemble_get_params(self.h, C.byref(p)))
+        self._check(self._call("_get_params", C.byref(p)))
         return p
 
     def set_params(self, **kw):
@@ -813,96 +818,41 @@ class EnsembleHandle:
             if not hasattr(p, k):
                 raise AttributeError(k)
             setattr(p, k, v)
-        self._check(self.lib.nbody_ensemble_set_params(self.h, C.byref(p)))
+        self._check(self._call("_set_params", C.byref(p)))
 
     @property
     def shape(self):
         """(worlds, bodies per world) of the current upload; (0, 0) before one."""
-        return int(self.lib.nbody_ensemble_num_worlds(self.h)), int(self.lib.nbody_ensemble_num_bodies(self.h))
+        return int(self._call("_num_worlds")), int(self._call("_num_bodies"))
 
     def upload(self, n_worlds, n_bodies, pos, vel, weight):
-        self._check(self.lib.nbody_ensemble_upload_f32(self.h, int(n_worlds), int(n_bodies), _ptr(pos), _ptr(vel), _ptr(weight)))
+        self._check(self._call("_upload" + self._suffix, int(n_worlds), int(n_bodies), _ptr(pos), _ptr(vel), _ptr(weight)))
 
     def download(self):
         b, n = self.shape
-        pos, vel = np.zeros((b, n, 2), np.float32), np.zeros((b, n, 2), np.float32)
-        self._check(self.lib.nbody_ensemble_download_f32(self.h, _ptr(pos), _ptr(vel)))
+        pos, vel = np.zeros((b, n, 2), self._dtype), np.zeros((b, n, 2), self._dtype)
+        self._check(self._call("_download" + self._suffix, _ptr(pos), _ptr(vel)))
         return pos, vel
 
     def update(self, delta, n_steps=1, counter: "Counting | None" = None):
-        self._check(self.lib.nbody_ensemble_update_f32(self.h, float(delta), int(n_steps),
-                                                       C.byref(counter) if counter is not None else None))
+        self._check(self._call("_update" + self._suffix, float(delta), int(n_steps),
+                               C.byref(counter) if counter is not None else None))
 
     def accel(self):
         b, n = self.shape
-        acc = np.zeros((b, n, 2), np.float32)
-        self._check(self.lib.nbody_ensemble_accel_f32(self.h, _ptr(acc)))
+        acc = np.zeros((b, n, 2), self._dtype)
+        self._check(self._call("_accel" + self._suffix, _ptr(acc)))
         return acc
 
 
-class Ensemble64Handle:
-    """Owner of one nbody_ensemble64 (one GPU): many worlds of one size, world-major float64 arrays, every step of all of them one
-    launch (nbody_ensemble64_*, the f64 sibling of EnsembleHandle).  Arrays come in contiguous and checked (ensemble.py does that); this class only passes them on."""
+class EnsembleHandle(_EnsembleHandleBase):
+    """nbody_ensemble_*: float32 worlds."""
+    _prefix, _suffix, _dtype = "nbody_ensemble", "_f32", np.float32
 
-    def __init__(self, device: int = 0):
-        self.lib = load()
-        self.h = _vp()
-        rc = self.lib.nbody_ensemble64_create(C.byref(self.h), int(device))
-        if rc != OK:
-            self.h = None
-            raise self._err(rc)
 
-    def _err(self, code):
-        msg = self.lib.nbody_ensemble64_last_error(self.h)
-        return NBodyError(code, msg.decode() if msg else "")
-
-    def _check(self, code):
-        if code != OK:
-            raise self._err(code)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.nbody_ensemble64_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
-    def get_params(self) -> Params:
-        p = Params()
-        self._check(self.lib.nbody_ensemble64_get_params(self.h, C.byref(p)))
-        return p
-
-    def set_params(self, **kw):
-        p = self.get_params()
-        for k, v in kw.items():
-            if not hasattr(p, k):
-                raise AttributeError(k)
-            setattr(p, k, v)
-        self._check(self.lib.nbody_ensemble64_set_params(self.h, C.byref(p)))
-
-    @property
-    def shape(self):
-        """(worlds, bodies per world) of the current upload; (0, 0) before one."""
-        return int(self.lib.nbody_ensemble64_num_worlds(self.h)), int(self.lib.nbody_ensemble64_num_bodies(self.h))
-
-    def upload(self, n_worlds, n_bodies, pos, vel, weight):
-        self._check(self.lib.nbody_ensemble64_upload(self.h, int(n_worlds), int(n_bodies), _ptr(pos), _ptr(vel), _ptr(weight)))
-
-    def download(self):
-        b, n = self.shape
-        pos, vel = np.zeros((b, n, 2), np.float64), np.zeros((b, n, 2), np.float64)
-        self._check(self.lib.nbody_ensemble64_download(self.h, _ptr(pos), _ptr(vel)))
-        return pos, vel
-
-    def update(self, delta, n_steps=1, counter: "Counting | None" = None):
-        self._check(self.lib.nbody_ensemble64_update(self.h, float(delta), int(n_steps),
-                                                       C.byref(counter) if counter is not None else None))
-
-    def accel(self):
-        b, n = self.shape
-        acc = np.zeros((b, n, 2), np.float64)
-        self._check(self.lib.nbody_ensemble64_accel(self.h, _ptr(acc)))
-        return acc
+class Ensemble64Handle(_EnsembleHandleBase):
+    """nbody_ensemble64_*: float64 worlds, the sibling of EnsembleHandle."""
+    _prefix, _suffix, _dtype = "nbody_ensemble64", "", np.float64
 
 
 def mass_hint(weight) -> float:

@@ -38,6 +38,7 @@
 
 #include "../../include/nbody_hip.h"
 #include "ensemble64_kernels.h"
+#include "ensemble_device.h"
 #include "fast_domain.h"
 #include "pair.h"
 
@@ -45,54 +46,6 @@ namespace nbody {
 namespace {
 
 constexpr int kEns64Run = 64;  // sources of one lane summed on their own before they join its total
-
-__device__ __forceinline__ double ens64_join(uint32_t lo, uint32_t hi) {
-  return __builtin_bit_cast(double, (uint64_t)lo | ((uint64_t)hi << 32));
-}
-template <int CTRL> __device__ __forceinline__ double ens64_dpp(double v) {
-  const uint64_t u = __builtin_bit_cast(uint64_t, v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, CTRL, 0xf, 0xf, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), CTRL, 0xf, 0xf, true);
-  return ens64_join((uint32_t)lo, (uint32_t)hi);
-}
-// v_permlane16_swap / v_permlane32_swap as ensemble_kernels.hip uses them, once per 32-bit half: with both operands a copy of
-// r, the two results are r of the even and r of the odd row of the pair (resp. of the lower and the upper half of the wave),
-// in that order in both — their sum has the same bits in both.
-__device__ __forceinline__ double ens64_add_neighbour_row(double r) {
-  const uint64_t u = __builtin_bit_cast(uint64_t, r);
-  uint32_t alo = (uint32_t)u, blo = (uint32_t)u, ahi = (uint32_t)(u >> 32), bhi = (uint32_t)(u >> 32);
-  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\tv_permlane16_swap_b32 %2, %3" : "+v"(alo), "+v"(blo), "+v"(ahi), "+v"(bhi));
-  return ens64_join(alo, ahi) + ens64_join(blo, bhi);
-}
-__device__ __forceinline__ double ens64_add_other_half(double r) {
-  const uint64_t u = __builtin_bit_cast(uint64_t, r);
-  uint32_t alo = (uint32_t)u, blo = (uint32_t)u, ahi = (uint32_t)(u >> 32), bhi = (uint32_t)(u >> 32);
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\tv_permlane32_swap_b32 %2, %3" : "+v"(alo), "+v"(blo), "+v"(ahi), "+v"(bhi));
-  return ens64_join(alo, ahi) + ens64_join(blo, bhi);
-}
-// The total of r over the SPLIT consecutive lanes of a group, in every one of them.
-template <int SPLIT> __device__ __forceinline__ double ens64_group_sum(double r) {
-  if constexpr (SPLIT >= 2) r = r + ens64_dpp<0xB1>(r);    // quad_perm [1,0,3,2]
-  if constexpr (SPLIT >= 4) r = r + ens64_dpp<0x4E>(r);    // quad_perm [2,3,0,1]
-  if constexpr (SPLIT >= 8) r = r + ens64_dpp<0x141>(r);   // row_half_mirror
-  if constexpr (SPLIT >= 16) r = r + ens64_dpp<0x128>(r);  // row_ror:8
-  if constexpr (SPLIT >= 32) r = ens64_add_neighbour_row(r);
-  if constexpr (SPLIT >= 64) r = ens64_add_other_half(r);
-  return r;
-}
-
-// main.rs:419-423 in double, multiply then add, no contraction (TU flag); `row` is the body's row among all worlds.
-__device__ __forceinline__ void ens64_integrate(const Ensemble64Args& a, size_t row, double px, double py, double ax, double ay) {
-  if (a.acc_out) a.acc_out[row] = double2{ax, ay};
-  if (a.vel) {
-    double2 v = a.vel[row];
-    v.x = v.x + ax * a.delta;
-    v.y = v.y + ay * a.delta;
-    const double sx = v.x * a.delta, sy = v.y * a.delta;
-    a.vel[row] = v;
-    a.pos_out[row] = double2{px + sx, py + sy};
-  }
-}
 
 template <int SPLIT>
 __global__ __launch_bounds__(kEnsembleBlock) void ensemble64_step(const Ensemble64Args a) {
@@ -161,7 +114,7 @@ __global__ __launch_bounds__(kEnsembleBlock) void ensemble64_step(const Ensemble
         ay = ay + term[jj].y;
       }
     }
-    ens64_integrate(a, row0 + t, p.x, p.y, ax, ay);
+    ens_integrate(a, row0 + t, p.x, p.y, ax, ay);
     return;
   }
 
@@ -190,9 +143,9 @@ __global__ __launch_bounds__(kEnsembleBlock) void ensemble64_step(const Ensemble
     ax = ax + (x0 + x1);
     ay = ay + (y0 + y1);
   }
-  ax = ens64_group_sum<SPLIT>(ax);
-  ay = ens64_group_sum<SPLIT>(ay);
-  if (live && part == 0) ens64_integrate(a, row0 + t, p.x, p.y, ax, ay);
+  ax = ens_group_sum<SPLIT>(ax);
+  ay = ens_group_sum<SPLIT>(ay);
+  if (live && part == 0) ens_integrate(a, row0 + t, p.x, p.y, ax, ay);
 }
 
 // Dynamic LDS above 64 KB (n > 3272: rows are padded to 8 and 3280 x 20 B = 65 600; the one-target-per-lane layout only) needs the function's limit raised: once per device.

@@ -1,0 +1,209 @@
+// libnbody_hip — ensembles: the host driver behind nbody_ensemble_* (ensemble.hip) and nbody_ensemble64_* (ensemble64.hip),
+// written once over a precision P.  Internal.  Many worlds of one size in world-major device arrays, every step of all of them
+// one launch on the handle's stream.  The positions are double-buffered across steps (a world's other blocks still read the
+// old ones), velocities are updated in place.  No CPU path and no host synchronisation between the steps of a call.
+//
+// P supplies: Real, Vec2 (the element types), Mass (what the device keeps per body), Args (the kernel's arguments);
+//   kCreate                        the create call's name, the prefix of its messages;
+//   stage(weight, rows, tmp)       -> the rows Mass values to upload (tmp is theirs to fill);
+//   route(args, mass, params)      the masses and the arithmetic of a launch, from the handle's parameters;
+//   launch(stream, n_worlds, args) one step, or one force evaluation, of all worlds.
+// A handle is a struct of its own derived from EnsembleState<P>: the C header declares two distinct opaque types.
+#pragma once
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "driver.h"
+#include "ensemble_kernels.h"
+
+namespace nbody {
+
+template <class P> struct EnsembleState {
+  using Precision = P;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  std::string err;
+  nbody_params params{};
+  nbody_counting counting{};
+  int64_t n_worlds = 0, n_bodies = 0;  // 0: nothing uploaded
+  typename P::Vec2* pos[2] = {nullptr, nullptr};
+  int cur = 0;
+  typename P::Vec2* vel = nullptr;
+  typename P::Mass* mass = nullptr;
+  typename P::Vec2* acc = nullptr;
+};
+
+template <class P> thread_local std::string g_ens_create_error;  // one per precision: what a failed create left for its thread
+
+template <class P> int ens_fail(EnsembleState<P>* e, int code, const std::string& msg) {
+  if (e) e->err = msg; else g_ens_create_error<P> = msg;
+  return code;
+}
+template <class P> int ens_fail_hip(EnsembleState<P>* e, hipError_t h, const char* what) {
+  return ens_fail<P>(e, NBODY_ERR_HIP, std::string("ensemble: ") + what + ": " + hipGetErrorString(h));
+}
+#define ENS_HIPCHK(e, call)                                        \
+  do {                                                             \
+    hipError_t h__ = (call);                                       \
+    if (h__ != hipSuccess) return ens_fail_hip<P>(e, h__, #call);  \
+  } while (0)
+
+template <class P> void ens_free(EnsembleState<P>* e) {
+  free_dev(e->pos[0]); free_dev(e->pos[1]); free_dev(e->vel); free_dev(e->mass); free_dev(e->acc);
+  e->n_worlds = e->n_bodies = 0;
+  e->cur = 0;
+}
+
+template <class P> typename P::Args ens_args(const EnsembleState<P>* e) {
+  typename P::Args a;
+  a.pos_in = e->pos[e->cur];
+  a.n_bodies = (int)e->n_bodies;
+  P::route(a, e->mass, e->params);
+  return a;
+}
+
+// Checks that device_id is a gfx950, makes it current, creates the handle's stream and then the handle H.
+template <class H> int ens_create(H** out, int device_id) {
+  using P = typename H::Precision;
+  const std::string who = P::kCreate;
+  if (!out) return ens_fail<P>(nullptr, NBODY_ERR_INVALID, who + ": out is NULL");
+  *out = nullptr;
+  int count = 0;
+  hipError_t h = hipGetDeviceCount(&count);
+  if (h != hipSuccess || count <= 0)
+    return ens_fail<P>(nullptr, NBODY_ERR_NO_DEVICE,
+                       who + ": no HIP device (" + (h != hipSuccess ? hipGetErrorString(h) : "count 0") + "); this library has no CPU path");
+  if (device_id < 0 || device_id >= count) return ens_fail<P>(nullptr, NBODY_ERR_INVALID, who + ": device_id out of range");
+  hipDeviceProp_t prop;
+  h = hipGetDeviceProperties(&prop, device_id);
+  if (h != hipSuccess) return ens_fail_hip<P>(nullptr, h, "hipGetDeviceProperties");
+  if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+    return ens_fail<P>(nullptr, NBODY_ERR_NO_DEVICE, who + ": device is " + prop.gcnArchName + ", kernels are built for gfx950 (MI355X) only");
+  hipStream_t stream = nullptr;
+  h = hipSetDevice(device_id);
+  if (h == hipSuccess) h = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+  if (h != hipSuccess) return ens_fail_hip<P>(nullptr, h, P::kCreate);
+  H* e = new (std::nothrow) H();
+  if (!e) {
+    (void)hipStreamDestroy(stream);
+    return ens_fail<P>(nullptr, NBODY_ERR_NOMEM, who + ": out of host memory");
+  }
+  e->device = device_id;
+  e->stream = stream;
+  nbody_default_params(&e->params);
+  *out = e;
+  return NBODY_OK;
+}
+
+// The handle's device current and its stream drained before its buffers are freed.
+template <class H> void ens_destroy(H* e) {
+  if (!e) return;
+  (void)hipSetDevice(e->device);
+  if (e->stream) (void)hipStreamSynchronize(e->stream);
+  ens_free(e);
+  if (e->stream) (void)hipStreamDestroy(e->stream);
+  delete e;
+}
+
+template <class P> const char* ens_last_error(const EnsembleState<P>* e) { return e ? e->err.c_str() : g_ens_create_error<P>.c_str(); }
+
+template <class P> int ens_set_params(EnsembleState<P>* e, const nbody_params* p) {
+  if (!e || !p) return NBODY_ERR_INVALID;
+  if (p->arith < NBODY_ARITH_AUTO || p->arith > NBODY_ARITH_EXACT) return ens_fail(e, NBODY_ERR_INVALID, "ensemble set_params: bad arith");
+  e->params = *p;
+  return NBODY_OK;
+}
+template <class P> int ens_get_params(const EnsembleState<P>* e, nbody_params* out) {
+  if (!e || !out) return NBODY_ERR_INVALID;
+  *out = e->params;
+  return NBODY_OK;
+}
+
+template <class P>
+int ens_upload(EnsembleState<P>* e, int64_t n_worlds, int64_t n_bodies, const typename P::Real* pos, const typename P::Real* vel,
+               const uint32_t* weight) {
+  using Vec2 = typename P::Vec2;
+  using Mass = typename P::Mass;
+  if (!e) return NBODY_ERR_INVALID;
+  if (n_bodies < 1 || n_bodies > kEnsembleMaxBodies)
+    return ens_fail(e, NBODY_ERR_INVALID, "ensemble upload: n_bodies must be 1 .. 4096 (above that a context per world is the tool)");
+  if (n_worlds < 1 || n_worlds > kEnsembleMaxRows / n_bodies)
+    return ens_fail(e, NBODY_ERR_INVALID, "ensemble upload: n_worlds must be >= 1 and n_worlds * n_bodies <= 2^26");
+  if (!pos || !vel) return ens_fail(e, NBODY_ERR_INVALID, "ensemble upload: pos_xy or vel_xy is NULL");
+  ENS_HIPCHK(e, hipSetDevice(e->device));
+  ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
+  ens_free(e);
+  const size_t rows = (size_t)(n_worlds * n_bodies);
+  std::vector<Mass> tmp;
+  const Mass* const mass = P::stage(weight, rows, tmp);
+  hipError_t h = hipMalloc((void**)&e->pos[0], rows * sizeof(Vec2));
+  if (h == hipSuccess) h = hipMalloc((void**)&e->pos[1], rows * sizeof(Vec2));
+  if (h == hipSuccess) h = hipMalloc((void**)&e->vel, rows * sizeof(Vec2));
+  if (h == hipSuccess) h = hipMalloc((void**)&e->mass, rows * sizeof(Mass));
+  if (h == hipSuccess) h = hipMemcpyAsync(e->pos[0], pos, rows * sizeof(Vec2), hipMemcpyHostToDevice, e->stream);
+  if (h == hipSuccess) h = hipMemcpyAsync(e->vel, vel, rows * sizeof(Vec2), hipMemcpyHostToDevice, e->stream);
+  if (h == hipSuccess) h = hipMemcpyAsync(e->mass, mass, rows * sizeof(Mass), hipMemcpyHostToDevice, e->stream);
+  if (h == hipSuccess) h = hipStreamSynchronize(e->stream);
+  if (h != hipSuccess) {
+    ens_free(e);
+    return ens_fail_hip(e, h, "upload");
+  }
+  e->n_worlds = n_worlds;
+  e->n_bodies = n_bodies;
+  return NBODY_OK;
+}
+
+template <class P> int ens_download(EnsembleState<P>* e, typename P::Real* pos, typename P::Real* vel) {
+  if (!e) return NBODY_ERR_INVALID;
+  if (!e->n_worlds) return ens_fail(e, NBODY_ERR_INVALID, "ensemble download: nothing uploaded");
+  ENS_HIPCHK(e, hipSetDevice(e->device));
+  const size_t bytes = (size_t)(e->n_worlds * e->n_bodies) * sizeof(typename P::Vec2);
+  if (pos) ENS_HIPCHK(e, hipMemcpyAsync(pos, e->pos[e->cur], bytes, hipMemcpyDeviceToHost, e->stream));
+  if (vel) ENS_HIPCHK(e, hipMemcpyAsync(vel, e->vel, bytes, hipMemcpyDeviceToHost, e->stream));
+  ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
+  return NBODY_OK;
+}
+
+template <class P> int ens_update(EnsembleState<P>* e, typename P::Real delta, int n_steps, nbody_counting* counter) {
+  if (!e) return NBODY_ERR_INVALID;
+  if (!e->n_worlds) return ens_fail(e, NBODY_ERR_INVALID, "ensemble update: nothing uploaded");
+  if (n_steps < 0) return ens_fail(e, NBODY_ERR_INVALID, "ensemble update: n_steps < 0");
+  if (n_steps == 0) return NBODY_OK;
+  ENS_HIPCHK(e, hipSetDevice(e->device));
+  const double t_begin = now_s();
+  for (int step = 0; step < n_steps; ++step) {
+    typename P::Args a = ens_args(e);
+    a.pos_out = e->pos[1 - e->cur];
+    a.vel = e->vel;
+    a.delta = delta;
+    ENS_HIPCHK(e, P::launch(e->stream, e->n_worlds, a));
+    e->cur = 1 - e->cur;  // (the launches are in stream order: the next one reads what this one writes)
+  }
+  ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
+  // force and integration are one fused kernel: the whole call is booked under sum_gravity, as the direct step books it
+  const double dt = now_s() - t_begin;
+  e->counting.sum_gravity += dt;
+  if (counter) counter->sum_gravity += dt;
+  return NBODY_OK;
+}
+
+template <class P> int ens_accel(EnsembleState<P>* e, typename P::Real* acc_xy) {
+  if (!e) return NBODY_ERR_INVALID;
+  if (!e->n_worlds) return ens_fail(e, NBODY_ERR_INVALID, "ensemble accel: nothing uploaded");
+  if (!acc_xy) return ens_fail(e, NBODY_ERR_INVALID, "ensemble accel: acc_xy is NULL");
+  ENS_HIPCHK(e, hipSetDevice(e->device));
+  const size_t bytes = (size_t)(e->n_worlds * e->n_bodies) * sizeof(typename P::Vec2);
+  if (!e->acc) ENS_HIPCHK(e, hipMalloc((void**)&e->acc, bytes));
+  typename P::Args a = ens_args(e);
+  a.acc_out = e->acc;
+  ENS_HIPCHK(e, P::launch(e->stream, e->n_worlds, a));
+  ENS_HIPCHK(e, hipMemcpyAsync(acc_xy, e->acc, bytes, hipMemcpyDeviceToHost, e->stream));
+  ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
+  return NBODY_OK;
+}
+
+#undef ENS_HIPCHK
+
+}  // namespace nbody

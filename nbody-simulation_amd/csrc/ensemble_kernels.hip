@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "../../include/nbody_hip.h"
+#include "ensemble_device.h"
 #include "ensemble_kernels.h"
 #include "fast_domain.h"
 #include "pair.h"
@@ -43,46 +44,6 @@ __device__ __forceinline__ float ens_abs_sum(float a, float b) {
   float r;
   asm("v_add_f32 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b));
   return r;
-}
-
-template <int CTRL> __device__ __forceinline__ float ens_dpp(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-// v_permlane16_swap / v_permlane32_swap through inline asm, as walk_split.hip does (the s_nop covers "VALU writes a VGPR, a
-// permlane swap reads it"): with both operands a copy of r, the sum of the two results is r of this row + r of its neighbour
-// row (rows 0|1, 2|3), resp. r of this half + r of the other half of the wave.
-__device__ __forceinline__ float ens_add_neighbour_row(float r) {
-  float a = r, b = r;
-  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-  return a + b;
-}
-__device__ __forceinline__ float ens_add_other_half(float r) {
-  float a = r, b = r;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-  return a + b;
-}
-// The total of r over the SPLIT consecutive lanes of a group, in every one of them.
-template <int SPLIT> __device__ __forceinline__ float ens_group_sum(float r) {
-  if constexpr (SPLIT >= 2) r = r + ens_dpp<0xB1>(r);    // quad_perm [1,0,3,2]
-  if constexpr (SPLIT >= 4) r = r + ens_dpp<0x4E>(r);    // quad_perm [2,3,0,1]
-  if constexpr (SPLIT >= 8) r = r + ens_dpp<0x141>(r);   // row_half_mirror
-  if constexpr (SPLIT >= 16) r = r + ens_dpp<0x128>(r);  // row_ror:8
-  if constexpr (SPLIT >= 32) r = ens_add_neighbour_row(r);
-  if constexpr (SPLIT >= 64) r = ens_add_other_half(r);
-  return r;
-}
-
-// main.rs:419-423, multiply then add, no contraction (TU flag); `row` is the body's row among all worlds.
-__device__ __forceinline__ void ens_integrate(const EnsembleArgs& a, size_t row, float px, float py, float ax, float ay) {
-  if (a.acc_out) a.acc_out[row] = make_float2(ax, ay);
-  if (a.vel) {
-    float2 v = a.vel[row];
-    v.x = v.x + ax * a.delta;
-    v.y = v.y + ay * a.delta;
-    const float sx = v.x * a.delta, sy = v.y * a.delta;
-    a.vel[row] = v;
-    a.pos_out[row] = make_float2(px + sx, py + sy);
-  }
 }
 
 template <int SPLIT>

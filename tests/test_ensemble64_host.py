@@ -101,6 +101,16 @@ def test_null_handle_calls(nb, which):
     assert not buf.any() and w.tolist() == [1, 1, 1, 1]
 
 
+@pytest.mark.parametrize("which", ["product", "lab"])
+def test_the_two_create_errors_are_kept_apart(nb, which):
+    C = nb._capi
+    lib = C._load(which)
+    assert lib.nbody_ensemble_create(None, 0) == C.ERR_INVALID
+    assert lib.nbody_ensemble64_create(None, 0) == C.ERR_INVALID
+    assert lib.nbody_ensemble_last_error(None).startswith(b"nbody_ensemble_create:")
+    assert lib.nbody_ensemble64_last_error(None).startswith(b"nbody_ensemble64_create:")
+
+
 def test_header_declares_the_f64_ensemble_and_both_libraries_export_it(nb):
     C = nb._capi
     declared = C.declared_symbols()
