@@ -462,7 +462,7 @@ int nbody_render_rgba_tracers(nbody_ctx* ctx, uint32_t height, uint32_t render_p
 int nbody_render_rgba_dev(void* stream, int64_t n, int is_f64, const void* pos_xy, const void* vel_xy, const void* weight_u32,
                           uint32_t height, uint32_t render_px, void* work_u32, void* rgba_dev);
 
-/* ---- self-test hooks (host only, no device needed) --------------------------------------------------- */
+/* ---- self-test hooks (host only unless they say otherwise) --------------------------------------------------- */
 /* The device BVH build reproduces the sequential f32 sum of bvh_tree.rs:58-61 with a parallel scan
  * (csrc/exact_sum.h).  This runs the same scan functions on the CPU, `tile` addends per scan and `seq_run` plain
  * adds after every restart, so the CPU tests can check them against the plain loop. */
@@ -480,6 +480,22 @@ int nbody_selftest_exact_sum_f64_segmented(const double* x, int64_t n, int seg, 
  * multiply-adds issued as packed instructions.  This runs it on device `device` over n host triples and hands the quotients
  * back, so that a test can compare them bit for bit with the host's IEEE division (needs a GPU). */
 int nbody_selftest_div_pair(int device, const float* nx, const float* ny, const float* den, int64_t n, float* qx, float* qy);
+/* The one-pass tree walk cuts its waves by an estimate: hist[ids[t]] >> shift terms for target t (t < n, ids distinct indices
+ * below hist_n).  This runs the walk's PREPARATION alone on device `device` — no walk kernel, no tree — by one of its routes:
+ * 0 the library scan, the wrap check and the total (a plain step); 1 the library scan and the check whose last work-group also
+ * concludes on the build (a step enqueued ahead, more than 2^24 targets); 2 the single-pass scan that does all of it (a step
+ * enqueued ahead; n <= 2^24).  Routes 1 and 2 judge a build described by the named values (the function lays them out as the
+ * 128-word flags block a step packs: level counters from word 32 on, every unused word a value of its own) and afterwards
+ * clear `clear_words` (128 .. 65536) words starting at that block.  hist_n <= 2^22.  keep_scratch != 0: the scratch block of
+ * this thread's previous such call is used again if it is large enough (the scan's state area is zeroed once per allocation
+ * only) and stays allocated for the next; keep_scratch == 0: a fresh block, freed (with any kept one) before returning.
+ * Out: off[n] (the exclusive scan), info[8], verdict[2], pack[2 + 128 + 8] (verdict | flags block | info), flags[128] (the
+ * block as built), clear[clear_words] (that region afterwards), used[4] = {extra waves, grid waves, 1 if the scratch was kept,
+ * 0}.  Route 0 leaves verdict and pack zero and the clear region as built.  Needs a GPU. */
+int nbody_selftest_walk_estimate(int device, const uint32_t* hist, int64_t hist_n, const uint32_t* ids, int64_t n, int shift, int route,
+                                 int nodes, int node_count, int fallback, int bad_index, int long_nodes_at_level_end, int level_end,
+                                 int node_cap, int keep_scratch, uint32_t* out_off, int32_t* out_info, int32_t* out_verdict,
+                                 int32_t* out_pack, int32_t* out_flags, int32_t* out_clear, int64_t clear_words, int64_t* out_used);
 /* Restarts of that scan during the last device BVH build of this context (diagnostic; 0 after a host build). */
 int nbody_bvh_build_restarts(const nbody_ctx* ctx);
 /* 1 if the last tree build of this context ran on the device, 0 if the host builder did it (the device builders

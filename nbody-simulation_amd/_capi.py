@@ -164,6 +164,7 @@ _SIGS = {
     "nbody_selftest_exact_sum_f64_segmented": (C.c_int, [_vp, C.c_int64, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "nbody_selftest_div_pair": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_int64, _vp, _vp]),
     "nbody_selftest_exact_sum_chunked": (C.c_int, [_vp, C.c_int64, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int64)]),
+    "nbody_selftest_walk_estimate": (C.c_int, [_i32, _vp, _i64, _vp, _i64, _i32, _i32] + [_i32] * 8 + [_vp] * 6 + [_i64, _vp]),
     "nbody_bvh_build_restarts": (C.c_int, [_vp]),
     "nbody_last_build_on_device": (C.c_int, [_vp]),
     "nbody_timer_create": (C.c_int, [C.POINTER(_vp)]),
@@ -336,6 +337,25 @@ def selftest_div_pair(nx, ny, den, device=0):
     if nx.size:
         check(None, load().nbody_selftest_div_pair(int(device), _ptr(nx), _ptr(ny), _ptr(den), nx.size, _ptr(qx), _ptr(qy)))
     return qx, qy
+
+
+def selftest_walk_estimate(hist, ids, shift=0, route=2, nodes=1, node_count=1, fallback=0, bad_index=0, long_nodes=0, level_end=0,
+                           node_cap=1, keep_scratch=False, clear_words=128, device=0):
+    """The one-pass walk's preparation alone on the device (nbody_selftest_walk_estimate) -> dict of off, info, verdict, pack,
+    flags, clear, extra, grid_waves, kept."""
+    hist = np.ascontiguousarray(hist, np.uint32)
+    ids = np.ascontiguousarray(ids, np.uint32)
+    assert hist.ndim == 1 and ids.ndim == 1
+    off = np.empty(ids.size, np.uint32)
+    info, verdict = np.zeros(8, np.int32), np.zeros(2, np.int32)
+    pack, flags = np.zeros(2 + 128 + 8, np.int32), np.zeros(128, np.int32)
+    clear, used = np.zeros(int(clear_words), np.int32), np.zeros(4, np.int64)
+    check(None, load().nbody_selftest_walk_estimate(int(device), _ptr(hist), hist.size, _ptr(ids), ids.size, int(shift), int(route), int(nodes),
+                                                    int(node_count), int(fallback), int(bad_index), int(long_nodes), int(level_end),
+                                                    int(node_cap), 1 if keep_scratch else 0, _ptr(off), _ptr(info), _ptr(verdict), _ptr(pack),
+                                                    _ptr(flags), _ptr(clear), int(clear_words), _ptr(used)))
+    return dict(off=off, info=info, verdict=verdict, pack=pack, flags=flags, clear=clear, extra=int(used[0]), grid_waves=int(used[1]),
+                kept=bool(used[2]))
 
 
 def selftest_exact_sum_chunked(x, chunk=2048):

@@ -13,9 +13,11 @@
 #include <cstring>
 #include <new>
 
+#include "bvh_build.h"
 #include "direct_kernels.h"
 #include "driver.h"
 #include "exact_sum_emulate.h"
+#include "walk_split.h"
 
 using namespace nbody;
 
@@ -387,6 +389,107 @@ NB_API int nbody_selftest_div_pair(int device, const float* nx, const float* ny,
   if (e == hipSuccess) e = hipMemcpy(qy, d + 4 * n, b, hipMemcpyDeviceToHost);
   (void)hipFree(d);
   return e == hipSuccess ? NBODY_OK : NBODY_ERR_HIP;
+}
+// The one-pass walk's preparation alone (launch_tree_walk_tile_prep: no walk kernel, no tree), over a history and target ids of
+// the caller's.  With `keep_scratch` the scratch block lives per thread from one call to the next: the estimate scan's state
+// area is zeroed when the block is allocated and never again, as ensure_walk_scratch does it for a step.  A call without it
+// takes a fresh block and leaves none behind.
+namespace {
+struct EstimateSelftestScratch {
+  char* block = nullptr;
+  size_t bytes = 0;
+  int device = -1;
+};
+thread_local EstimateSelftestScratch g_est_scratch;
+constexpr int kEstFlagWords = 128;    // the block a step packs: flags + level counters (tree_driver.hip, kSpecWords)
+constexpr int kEstBigcountAt = 32;    // where this self-test puts the level counters inside it (64 of them)
+}  // namespace
+NB_API int nbody_selftest_walk_estimate(int device, const uint32_t* hist, int64_t hist_n, const uint32_t* ids, int64_t n, int shift, int route,
+                                        int nodes, int node_count, int fallback, int bad_index, int long_nodes_at_level_end, int level_end,
+                                        int node_cap, int keep_scratch, uint32_t* out_off, int32_t* out_info, int32_t* out_verdict,
+                                        int32_t* out_pack, int32_t* out_flags, int32_t* out_clear, int64_t clear_words, int64_t* out_used) {
+  if (!hist || !ids || !out_off || !out_info || !out_verdict || !out_pack || !out_flags || !out_clear || !out_used) return NBODY_ERR_INVALID;
+  if (n < 1 || hist_n < n || hist_n > ((int64_t)1 << 22) || shift < 0 || shift > 31 || route < 0 || route > 2) return NBODY_ERR_INVALID;
+  if (route == 2 && n > kWalkFusedScanMaxTargets) return NBODY_ERR_INVALID;
+  if (level_end < 0 || level_end >= kBvhLevels || clear_words < kEstFlagWords || clear_words > 65536) return NBODY_ERR_INVALID;
+  for (int64_t i = 0; i < n; ++i)
+    if ((int64_t)ids[i] >= hist_n) return NBODY_ERR_INVALID;  // the kernels gather hist[ids[t]] unchecked
+  if (hipSetDevice(device) != hipSuccess) return NBODY_ERR_NO_DEVICE;
+  const WalkSplitLayout L = walk_split_layout(n);
+  EstimateSelftestScratch& sc = g_est_scratch;
+  const bool kept = keep_scratch != 0 && sc.block && sc.device == device && sc.bytes >= L.total;
+  uint32_t *hist_d = nullptr, *ids_d = nullptr;
+  int* aux = nullptr;  // verdict (2) | pack (2 + flag words + 8) | flags block and clear region (clear_words)
+  const size_t pack_words = 2 + kEstFlagWords + 8;
+  auto finish = [&](hipError_t e) {
+    (void)hipDeviceSynchronize();
+    (void)hipFree(hist_d);
+    (void)hipFree(ids_d);
+    (void)hipFree(aux);
+    if (keep_scratch == 0 || e != hipSuccess) {  // nothing stays allocated behind a call that did not ask for it
+      (void)hipFree(sc.block);
+      sc = EstimateSelftestScratch{};
+    }
+    if (e != hipSuccess) (void)hipGetLastError();
+    return e == hipSuccess ? NBODY_OK : NBODY_ERR_HIP;
+  };
+  hipError_t e = hipSuccess;
+  if (!kept) {
+    (void)hipFree(sc.block);
+    sc = EstimateSelftestScratch{};
+    if ((e = hipMalloc((void**)&sc.block, L.total)) != hipSuccess) { sc.block = nullptr; return finish(e); }
+    sc.bytes = L.total;
+    sc.device = device;
+    if ((e = hipMemset(sc.block + L.scan_state, 0, L.scan_state_bytes)) != hipSuccess) return finish(e);
+  }
+  if ((e = hipMalloc((void**)&hist_d, (size_t)hist_n * 4)) != hipSuccess) return finish(e);
+  if ((e = hipMalloc((void**)&ids_d, (size_t)n * 4)) != hipSuccess) return finish(e);
+  if ((e = hipMalloc((void**)&aux, (2 + pack_words + (size_t)clear_words) * sizeof(int))) != hipSuccess) return finish(e);
+  int* verdict_d = aux;
+  int* pack_d = aux + 2;
+  int* flags_d = aux + 2 + pack_words;
+  // the flags block: every word its own value, so that the packed copy is checked word by word; then the verdict's inputs
+  std::vector<int32_t> block((size_t)clear_words);
+  for (int64_t k = 0; k < clear_words; ++k) block[(size_t)k] = (int32_t)(0x5A000000 + k);
+  for (int k = 0; k < kBvhLevels; ++k) block[(size_t)(kEstBigcountAt + k)] = 0;
+  block[kBvhFallback] = fallback;
+  block[kBvhNodeCount] = node_count;
+  block[kBvhBadIndex] = bad_index;
+  block[kBvhNodes] = nodes;
+  block[(size_t)(kEstBigcountAt + level_end)] = long_nodes_at_level_end;
+  std::memcpy(out_flags, block.data(), kEstFlagWords * sizeof(int32_t));
+  if ((e = hipMemcpy(hist_d, hist, (size_t)hist_n * 4, hipMemcpyHostToDevice)) != hipSuccess) return finish(e);
+  if ((e = hipMemcpy(ids_d, ids, (size_t)n * 4, hipMemcpyHostToDevice)) != hipSuccess) return finish(e);
+  if ((e = hipMemcpy(flags_d, block.data(), (size_t)clear_words * sizeof(int), hipMemcpyHostToDevice)) != hipSuccess) return finish(e);
+  if ((e = hipMemset(aux, 0, (2 + pack_words) * sizeof(int))) != hipSuccess) return finish(e);
+  WalkArgs<float> w{};
+  w.n_tgt = n;
+  TileTail tail;
+  tail.flags = flags_d;
+  tail.flag_words = kEstFlagWords;
+  tail.bigcount = flags_d + kEstBigcountAt;
+  tail.level_end = level_end;
+  tail.node_cap = node_cap;
+  tail.verdict = verdict_d;
+  tail.pack = pack_d;
+  tail.clear = flags_d;
+  tail.clear_words = (int)clear_words;
+  tail.info_zeroed = false;
+  tail.fused_scan = route == 2;
+  int64_t waves = 0;
+  if ((e = launch_tree_walk_tile_prep<float>(nullptr, w, sc.block, L, ids_d, hist_d, 1, shift, &waves, route == 0 ? nullptr : &tail)) != hipSuccess)
+    return finish(e);
+  if ((e = hipDeviceSynchronize()) != hipSuccess) return finish(e);
+  if ((e = hipMemcpy(out_off, sc.block + L.off, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess) return finish(e);
+  if ((e = hipMemcpy(out_info, sc.block + L.info, 8 * sizeof(int), hipMemcpyDeviceToHost)) != hipSuccess) return finish(e);
+  if ((e = hipMemcpy(out_verdict, verdict_d, 2 * sizeof(int), hipMemcpyDeviceToHost)) != hipSuccess) return finish(e);
+  if ((e = hipMemcpy(out_pack, pack_d, pack_words * sizeof(int), hipMemcpyDeviceToHost)) != hipSuccess) return finish(e);
+  if ((e = hipMemcpy(out_clear, flags_d, (size_t)clear_words * sizeof(int), hipMemcpyDeviceToHost)) != hipSuccess) return finish(e);
+  out_used[0] = waves - n / 64 - 4;  // the `extra` waves of the budget rule (grid = extra + n / 64 + 4)
+  out_used[1] = waves;
+  out_used[2] = kept ? 1 : 0;
+  out_used[3] = 0;
+  return finish(hipSuccess);
 }
 NB_API int nbody_selftest_exact_sum_chunked(const float* x, int64_t n, int chunk, float* out_sum, int64_t* out_runs_used) {
   if ((!x && n > 0) || n < 0 || chunk < 1 || !out_sum) return NBODY_ERR_INVALID;

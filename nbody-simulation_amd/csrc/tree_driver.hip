@@ -105,6 +105,21 @@ int phase_drain(nbody_ctx* c) {
   return NBODY_OK;
 }
 
+// NBODY_TRACE: one line per launched walk that says WHICH walk it was.  Nearly every route computes the same bits by design,
+// so the result cannot tell them apart: tests that name a route read it here (tests/_routes.py).
+//   route: fused | small-leaves | per-thread (laboratory) | tile | three-pass (laboratory) | none
+//   tile only: arm exact | fast-registers | fast-rows (laboratory also fast-bfs, fast-registers-log); rows, srec, rec_mode:
+//   the kernel's template parameters (-1: that arm has none)
+//   prep: how a tile walk's estimate was prepared: plain (library scan, wrap check, total), scan-tail (a step enqueued
+//   ahead: walk_scan_est_tail) or check-tail (a step enqueued ahead: library scan + walk_check_est_tail); ahead: 0 / 1
+void trace_route(const char* route, const TileRoute* t, const char* prep, bool ahead, int64_t n_tgt, bool f64) {
+  if (env_int("NBODY_TRACE", 0) == 0) return;
+  const TileRoute none;
+  if (!t) t = &none;
+  std::fprintf(stderr, "[nbody] walk route: route=%s arm=%s rows=%d srec=%d rec_mode=%d prep=%s ahead=%d n_tgt=%lld f64=%d\n", route, t->arm,
+               t->rows, t->srec, t->rec_mode, prep, ahead ? 1 : 0, (long long)n_tgt, f64 ? 1 : 0);
+}
+
 // A walk in which the average target takes a sixteenth of all particles (small theta on the needle boxes) is nearly the
 // direct sum: every lane wants every leaf and the fused walk's lane = target is the cheaper arrangement.
 inline bool walk_near_direct(unsigned long long total, int64_t n_tgt, int64_t n) {
@@ -173,10 +188,11 @@ int tree_walk_phase(nbody_ctx* c, State<T>& s, int kind, const void* tgt_pos, in
       if (hist && (rc = estimate_shift(c, s.wt_total, s.wt_hist, s.n, &shift)) != NBODY_OK) return rc;
       int info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
       unsigned long long total = 0;
+      TileRoute tile_route;
       for (int estimate = hist ? 1 : 0; !done; estimate = 2) {
         {
           TimerScope ts(c->timer, c->stream);
-          HIPCHK(c, launch_tree_walk_tile(c->stream, w, s.ws_scratch, L, tgt_ids, self ? s.wt_hist : nullptr, estimate, shift));
+          HIPCHK(c, launch_tree_walk_tile(c->stream, w, s.ws_scratch, L, tgt_ids, self ? s.wt_hist : nullptr, estimate, shift, &tile_route));
         }
         HIPCHK(c, hipMemcpyAsync(info, s.ws_scratch + L.info, sizeof(info), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -184,6 +200,7 @@ int tree_walk_phase(nbody_ctx* c, State<T>& s, int kind, const void* tgt_pos, in
         if (env_int("NBODY_TRACE", 0) != 0)
           std::fprintf(stderr, "[nbody] tile walk: %llu terms, estimate %s (shift %d, total %d), %d per wave, overflow %d\n", total,
                        estimate == 1 ? "from the last walk" : (estimate == 0 ? "counted" : "none"), shift, info[0], info[3], info[1]);
+        trace_route("tile", &tile_route, "plain", false, w.n_tgt, sizeof(T) == 8);
         // an estimate whose scan does not fit (a counted one past 2^32 terms; counts of older walks under another theta
         // in a shard's new slice): walk without one (the counts it leaves behind are scaled next time)
         done = info[1] == 0;
@@ -211,6 +228,7 @@ int tree_walk_phase(nbody_ctx* c, State<T>& s, int kind, const void* tgt_pos, in
         if (env_int("NBODY_TRACE", 0) != 0)
           std::fprintf(stderr, "[nbody] split walk: %d terms, overflow %d, %d terms per term-pass wave; longest such wave %d us (leaf %d us, node %d us; timing builds)\n",
                        info[0], info[1], info[3], info[5] >> 20, (info[5] >> 10) & 1023, info[5] & 1023);
+        trace_route("three-pass", nullptr, "none", false, w.n_tgt, sizeof(T) == 8);
         if (info[1] == 0) {
           done = true;
         } else if (info[2] != 0 || info[0] > hard_cap) {
@@ -236,8 +254,12 @@ int tree_walk_phase(nbody_ctx* c, State<T>& s, int kind, const void* tgt_pos, in
     }
   }
   if (!done) {
-    TimerScope ts(c->timer, c->stream);
-    HIPCHK(c, launch_tree_walk<T>(c->stream, w, lab_int("NBODY_WALK_PER_THREAD", 0) == 0));
+    const char* route = "none";
+    {
+      TimerScope ts(c->timer, c->stream);
+      HIPCHK(c, launch_tree_walk<T>(c->stream, w, lab_int("NBODY_WALK_PER_THREAD", 0) == 0, &route));
+    }
+    trace_route(route, nullptr, "none", false, w.n_tgt, sizeof(T) == 8);
   }
   if (w.stats) {
     HIPCHK(c, hipMemcpyAsync(c->last_stats, c->stats_dev, sizeof(c->last_stats), hipMemcpyDeviceToHost, c->stream));
@@ -378,9 +400,10 @@ template <class T> int bvh_step_ahead(nbody_ctx* c, State<T>& s, T delta, PhaseE
     s.bb_flags_clean = true;
     int* h = c->spec_host;
     HIPCHK(c, hipEventRecord(c->spec_event, c->stream));  // (the tail kernel has written h[0 .. 2 + 128 + 8) by then)
+    TileRoute tile_route;
     {
       TimerScope ts(c->timer, c->stream);
-      HIPCHK(c, launch_tree_walk_tile_main<T>(c->stream, w, s.ws_scratch, WL, tgt_ids, s.wt_hist, waves));
+      HIPCHK(c, launch_tree_walk_tile_main<T>(c->stream, w, s.ws_scratch, WL, tgt_ids, s.wt_hist, waves, &tile_route));
     }
     if (!stamps) rc = phase_mark(c, ph, 2);
     if (rc) return rc;
@@ -396,6 +419,7 @@ template <class T> int bvh_step_ahead(nbody_ctx* c, State<T>& s, T delta, PhaseE
                    flags[kBvhMaxDepth], flags[kBvhFallback], lv_end);
       std::fprintf(stderr, "[nbody] tile walk (step ahead): estimate from the last walk (shift %d, total %d), %d per wave, overflow %d\n", shift,
                    info[0], info[3], info[1]);
+      trace_route("tile", &tile_route, fused_scan ? "scan-tail" : "check-tail", true, n, false);
     }
     if (h[1] == 0) {  // the build needs more levels or the host builder: nothing was integrated, `in` is intact
       s.wt_hist_n = -1;  // (the walk returned at once and left zeros in the history)

@@ -117,7 +117,9 @@ template <class T> __device__ __forceinline__ void gather_row(const GatherArgs<T
   if (a.mass_out) a.mass_out[i] = (T)a.weight_in[s];  // `weight as f32`, main.rs:360
 }
 
-template <class T> hipError_t launch_tree_walk(hipStream_t s, const WalkArgs<T>& a, bool wave_uniform);
+// *route (the NBODY_TRACE route line): which walk was launched — "fused" (tree_walk_wave), "small-leaves" (tree_walk_small),
+// "per-thread" (tree_walk, laboratory only), "none" (no targets).
+template <class T> hipError_t launch_tree_walk(hipStream_t s, const WalkArgs<T>& a, bool wave_uniform, const char** route = nullptr);
 hipError_t launch_div_pair_selftest(hipStream_t s, const float* nx, const float* ny, const float* den, int64_t n, float* qx, float* qy);
 template <class T> hipError_t launch_gather(hipStream_t s, const GatherArgs<T>& a);
 template <class T> hipError_t launch_integrate(hipStream_t s, void* pos, void* vel, const void* acc, int64_t n, T delta, Gate gate = Gate{});

@@ -440,11 +440,15 @@ NB_INST(float)
 NB_INST(double)
 #undef NB_INST
 
-template <class T> hipError_t launch_tree_walk(hipStream_t s, const WalkArgs<T>& a, bool wave_uniform) {
+template <class T> hipError_t launch_tree_walk(hipStream_t s, const WalkArgs<T>& a, bool wave_uniform, const char** route) {
+  const char* route_here;
+  const char*& rt = route ? *route : route_here;
+  rt = "none";
   if (a.n_tgt <= 0) return hipSuccess;
   const dim3 grid((unsigned)((a.n_tgt + 255) / 256));
 #ifdef NBODY_LAB
   if (!wave_uniform) {
+    rt = "per-thread";
     hipLaunchKernelGGL((tree_walk<T>), grid, dim3(256), 0, s, a);
     return hipGetLastError();
   }
@@ -455,6 +459,7 @@ template <class T> hipError_t launch_tree_walk(hipStream_t s, const WalkArgs<T>&
   // Laboratory: NBODY_WALK_COMPACT 0 off / 2, 3 other thresholds for dealing a leaf step's pairs to the lanes
   const int compact = lab_int("NBODY_WALK_COMPACT", 1);
   if (!a.big_leaves && !a.fast && !a.stats && a.n_nodes > 0 && compact != 0) {
+    rt = "small-leaves";
     hipLaunchKernelGGL((tree_walk_small<T>), grid, dim3(256), 0, s, a, compact);
     return hipGetLastError();
   }
@@ -464,6 +469,7 @@ template <class T> hipError_t launch_tree_walk(hipStream_t s, const WalkArgs<T>&
 #define NB_WS(L, P, F) do { if (a.stats) hipLaunchKernelGGL((tree_walk_wave<T, L, P, F, true>), grid, dim3(256), 0, s, a); \
                            else hipLaunchKernelGGL((tree_walk_wave<T, L, P, F, false>), grid, dim3(256), 0, s, a); } while (0)
 #define NB_W(L, P) do { if (a.fast) NB_WS(L, P, true); else NB_WS(L, P, false); } while (0)
+  rt = "fused";
 #ifdef NBODY_LAB
   const int env_lb = lab_int("NBODY_WALK_LB", 0);
   const int env_pf = lab_int("NBODY_WALK_PREFETCH", -1);
@@ -508,8 +514,8 @@ template <class T> hipError_t launch_integrate(hipStream_t s, void* pos, void* v
   return hipGetLastError();
 }
 
-template hipError_t launch_tree_walk<float>(hipStream_t, const WalkArgs<float>&, bool);
-template hipError_t launch_tree_walk<double>(hipStream_t, const WalkArgs<double>&, bool);
+template hipError_t launch_tree_walk<float>(hipStream_t, const WalkArgs<float>&, bool, const char**);
+template hipError_t launch_tree_walk<double>(hipStream_t, const WalkArgs<double>&, bool, const char**);
 template hipError_t launch_gather<float>(hipStream_t, const GatherArgs<float>&);
 template hipError_t launch_gather<double>(hipStream_t, const GatherArgs<double>&);
 template hipError_t launch_integrate<float>(hipStream_t, void*, void*, const void*, int64_t, float, Gate);

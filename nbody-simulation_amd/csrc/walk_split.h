@@ -24,6 +24,15 @@ constexpr int64_t kWalkFusedScanMaxTargets = (int64_t)1 << 24;  // TileTail::fus
 hipError_t launch_tree_walk_split(hipStream_t s, const WalkArgs<float>& a, char* scratch, const WalkSplitLayout& L, void* terms,
                                   int64_t term_capacity);
 
+// Which instantiation launch_tree_walk_tile_main launched (the NBODY_TRACE route line): the arm ("exact": walk_tile<T, false>,
+// "fast-registers": walk_tile_fast, "fast-rows": walk_tile<T, true>; laboratory only: "fast-bfs", "fast-registers-log"), and
+// the template parameters that arm has: the LDS tile's rows and whether node records come by scalar loads (exact, fast-rows),
+// the node-record mode (fast-registers).  -1: that arm has no such parameter.
+struct TileRoute {
+  const char* arm = "none";
+  int rows = -1, srec = -1, rec_mode = -1;
+};
+
 // The same walk in one pass, the terms handed from "lane = particle" to "lane = target" through LDS (walk_tile): no term
 // array.  The waves are cut by an estimate of each target's work.  estimate 1: hist[tgt_ids[t]] holds the term count of
 // target t's particle in the previous walk (scaled down by `shift` bits so that the sum stays below 2^31); 0: a counting
@@ -33,7 +42,7 @@ hipError_t launch_tree_walk_split(hipStream_t s, const WalkArgs<float>& a, char*
 // info[6..7]: this walk's total terms (unsigned long long).
 template <class T>
 hipError_t launch_tree_walk_tile(hipStream_t s, const WalkArgs<T>& a, char* scratch, const WalkSplitLayout& L, const uint32_t* tgt_ids,
-                                 uint32_t* hist, int estimate, int shift);
+                                 uint32_t* hist, int estimate, int shift, TileRoute* route = nullptr);
 
 // The same in two halves (preparation: estimate scan, wrap check, budget — info[0..3] final; then the walk kernel), for
 // a caller that enqueues a copy of info and an event in between.
@@ -62,6 +71,6 @@ hipError_t launch_tree_walk_tile_prep(hipStream_t s, const WalkArgs<T>& a, char*
                                       uint32_t* hist, int estimate, int shift, int64_t* grid_waves, const TileTail* tail = nullptr);
 template <class T>
 hipError_t launch_tree_walk_tile_main(hipStream_t s, const WalkArgs<T>& a, char* scratch, const WalkSplitLayout& L, const uint32_t* tgt_ids,
-                                      uint32_t* hist, int64_t grid_waves);
+                                      uint32_t* hist, int64_t grid_waves, TileRoute* route = nullptr);
 
 }  // namespace nbody

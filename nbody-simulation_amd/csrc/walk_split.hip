@@ -1837,7 +1837,10 @@ hipError_t launch_tree_walk_tile_prep(hipStream_t s, const WalkArgs<T>& a, char*
 
 template <class T>
 hipError_t launch_tree_walk_tile_main(hipStream_t s, const WalkArgs<T>& a_in, char* scratch, const WalkSplitLayout& L, const uint32_t* tgt_ids,
-                                      uint32_t* hist, int64_t grid_waves) {
+                                      uint32_t* hist, int64_t grid_waves, TileRoute* route) {
+  TileRoute route_here;
+  TileRoute& rt = route ? *route : route_here;
+  rt = TileRoute{};
   if (a_in.n_tgt <= 0 || grid_waves <= 0) return hipSuccess;
   const uint32_t* off = (const uint32_t*)(scratch + L.off);
   int* info = (int*)(scratch + L.info);
@@ -1875,21 +1878,22 @@ hipError_t launch_tree_walk_tile_main(hipStream_t s, const WalkArgs<T>& a_in, ch
   }
   // node records by scalar loads (scalar_node_rec): the exact walk always (62 instead of 72 VGPRs: eight waves per SIMD instead of seven;
   // reference scene 0.579 -> 0.567 ms, Plummer 1 M 6.07 -> 5.96); NBODY_WALK_SCALAR_REC=0: the vector loads of one address
-  static const bool srec = lab_int("NBODY_WALK_SCALAR_REC", 1) != 0;
+  const bool srec = lab_int("NBODY_WALK_SCALAR_REC", 1) != 0;
   // FAST: f32 takes walk_tile_fast (registers, lane-parallel sums); f64 the rows arm (walk_tile<double, true>: LDS rows + ordered adds with
   // the one-reciprocal term) — walk_tile_fast<double> moves every value as two 32-bit halves through the swaps and runs at half
   // the occupancy: Plummer 4 M f64 205 ms against 92 (the exact walk: 124).  Laboratory: NBODY_WALK_FAST_ROWS=0/1 forces one or the other.
-  static const int fast_rows_env = lab_int("NBODY_WALK_FAST_ROWS", -1);
+  const int fast_rows_env = lab_int("NBODY_WALK_FAST_ROWS", -1);
   const bool fast_rows = fast_rows_env >= 0 ? fast_rows_env != 0 : sizeof(T) == 8;
   // FAST: node records by scalar loads (round 3 took vector loads of one address below 400 000 targets: 0.298 against 0.322 ms on the
   // reference scene's FIRST steps; over the bench leg's 300 steps, with the waves in one residency round, scalar loads win there too:
   // 0.299 -> 0.277 ms, profiles/r04_walk_wave_target.txt).  Laboratory: NBODY_WALK_FAST_REC=0 / 1 the plain / pinned vector loads.
-  static const int rec_env = lab_int("NBODY_WALK_FAST_REC", -1);
+  const int rec_env = lab_int("NBODY_WALK_FAST_REC", -1);
   const int rec_mode = rec_env >= 0 ? rec_env : 3;
 #ifdef NBODY_LAB
   // every variant the A/B tools switch between: rows 4 / 8 / 16, node records by vector loads, the rows arm in f32, the register arm
   // in f64, the per-wave log
-#define NB_TILE(F, R) do { if (srec) walk_tile<T, F, R, true><<<grid_ordered, dim3(256), 0, s>>>(a, off, info, tgt_ids, hist, total_out); \
+#define NB_TILE(F, R) do { rt = TileRoute{F ? "fast-rows" : "exact", R, srec ? 1 : 0, -1};                                                      \
+                           if (srec) walk_tile<T, F, R, true><<<grid_ordered, dim3(256), 0, s>>>(a, off, info, tgt_ids, hist, total_out); \
                            else walk_tile<T, F, R, false><<<grid_ordered, dim3(256), 0, s>>>(a, off, info, tgt_ids, hist, total_out); } while (0)
   unsigned long long* wave_log = nullptr;
   WalkArgs<T> a_log = a_strided;
@@ -1904,8 +1908,11 @@ hipError_t launch_tree_walk_tile_main(hipStream_t s, const WalkArgs<T>& a_in, ch
   bool bfs = false;
   if constexpr (sizeof(T) == 4) bfs = a.fast && !fast_rows && !wave_log && lab_int("NBODY_WALK_FAST_BFS", 0) != 0;
   if (bfs) {
+    rt.arm = "fast-bfs";
     if constexpr (sizeof(T) == 4) walk_tile_fast_bfs<<<grid, dim3(256), 0, s>>>(a, off, info, tgt_ids, hist, total_out);
   } else if (a.fast && !fast_rows) {
+    rt.arm = wave_log ? "fast-registers-log" : "fast-registers";
+    rt.rec_mode = wave_log ? 0 : (rec_mode == 1 || rec_mode == 3 ? rec_mode : 0);
     if (wave_log) walk_tile_fast<T, 0, true><<<grid_ordered, dim3(256), 0, s>>>(a, off, info, tgt_ids, hist, total_out);
     else if (rec_mode == 1) walk_tile_fast<T, 1, false><<<grid_ordered, dim3(256), 0, s>>>(a, off, info, tgt_ids, hist, total_out);
     else if (rec_mode == 3) walk_tile_fast<T, 3, false><<<grid_ordered, dim3(256), 0, s>>>(a, off, info, tgt_ids, hist, total_out);
@@ -1934,11 +1941,14 @@ hipError_t launch_tree_walk_tile_main(hipStream_t s, const WalkArgs<T>& a_in, ch
   const WalkArgs<T>& a = a_strided;
   if constexpr (sizeof(T) == 4) {
     if (a.fast) {
+      rt = TileRoute{"fast-registers", -1, -1, 3};
       walk_tile_fast<T, 3, false><<<grid_ordered, dim3(256), 0, s>>>(a, off, info, tgt_ids, hist, total_out);
     } else {
+      rt = TileRoute{"exact", 8, 1, -1};
       walk_tile<T, false, 8, true><<<grid_ordered, dim3(256), 0, s>>>(a, off, info, tgt_ids, hist, total_out);
     }
   } else {
+    rt = TileRoute{a.fast ? "fast-rows" : "exact", 8, 1, -1};
     if (a.fast) walk_tile<T, true, 8, true><<<grid_ordered, dim3(256), 0, s>>>(a, off, info, tgt_ids, hist, total_out);
     else walk_tile<T, false, 8, true><<<grid_ordered, dim3(256), 0, s>>>(a, off, info, tgt_ids, hist, total_out);
   }
@@ -1948,20 +1958,20 @@ hipError_t launch_tree_walk_tile_main(hipStream_t s, const WalkArgs<T>& a_in, ch
 
 template <class T>
 hipError_t launch_tree_walk_tile(hipStream_t s, const WalkArgs<T>& a, char* scratch, const WalkSplitLayout& L, const uint32_t* tgt_ids,
-                                 uint32_t* hist, int estimate, int shift) {
+                                 uint32_t* hist, int estimate, int shift, TileRoute* route) {
   int64_t waves = 0;
   hipError_t e = launch_tree_walk_tile_prep<T>(s, a, scratch, L, tgt_ids, hist, estimate, shift, &waves, nullptr);
   if (e != hipSuccess) return e;
-  return launch_tree_walk_tile_main<T>(s, a, scratch, L, tgt_ids, hist, waves);
+  return launch_tree_walk_tile_main<T>(s, a, scratch, L, tgt_ids, hist, waves, route);
 }
 
-template hipError_t launch_tree_walk_tile<float>(hipStream_t, const WalkArgs<float>&, char*, const WalkSplitLayout&, const uint32_t*, uint32_t*, int, int);
-template hipError_t launch_tree_walk_tile<double>(hipStream_t, const WalkArgs<double>&, char*, const WalkSplitLayout&, const uint32_t*, uint32_t*, int, int);
+template hipError_t launch_tree_walk_tile<float>(hipStream_t, const WalkArgs<float>&, char*, const WalkSplitLayout&, const uint32_t*, uint32_t*, int, int, TileRoute*);
+template hipError_t launch_tree_walk_tile<double>(hipStream_t, const WalkArgs<double>&, char*, const WalkSplitLayout&, const uint32_t*, uint32_t*, int, int, TileRoute*);
 template hipError_t launch_tree_walk_tile_prep<float>(hipStream_t, const WalkArgs<float>&, char*, const WalkSplitLayout&, const uint32_t*, uint32_t*, int, int, int64_t*,
                                                       const TileTail*);
 template hipError_t launch_tree_walk_tile_prep<double>(hipStream_t, const WalkArgs<double>&, char*, const WalkSplitLayout&, const uint32_t*, uint32_t*, int, int, int64_t*,
                                                        const TileTail*);
-template hipError_t launch_tree_walk_tile_main<float>(hipStream_t, const WalkArgs<float>&, char*, const WalkSplitLayout&, const uint32_t*, uint32_t*, int64_t);
-template hipError_t launch_tree_walk_tile_main<double>(hipStream_t, const WalkArgs<double>&, char*, const WalkSplitLayout&, const uint32_t*, uint32_t*, int64_t);
+template hipError_t launch_tree_walk_tile_main<float>(hipStream_t, const WalkArgs<float>&, char*, const WalkSplitLayout&, const uint32_t*, uint32_t*, int64_t, TileRoute*);
+template hipError_t launch_tree_walk_tile_main<double>(hipStream_t, const WalkArgs<double>&, char*, const WalkSplitLayout&, const uint32_t*, uint32_t*, int64_t, TileRoute*);
 
 }  // namespace nbody

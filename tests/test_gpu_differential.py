@@ -4,6 +4,8 @@ coordinates on an axis), huge and zero masses (u32 sums wrap as in release Rust)
 import numpy as np
 import pytest
 
+from tests import _routes as routes
+
 pytestmark = pytest.mark.gpu
 F32 = np.float32
 
@@ -46,19 +48,26 @@ def test_direct_exact_differential(nb, orc, seed):
     assert np.array_equal(p, rp, equal_nan=True) and np.array_equal(v, rv, equal_nan=True)
 
 
-@pytest.mark.parametrize("walk", ["default", "one pass forced", "three passes forced"])
-@pytest.mark.parametrize("order", ["as_written", "consistent"])
-@pytest.mark.parametrize("seed", range(10))
-def test_bvh_step_differential(nb, orc, monkeypatch, seed, order, walk):
-    """`walk`: these inputs are too small for the lane = particle walks to be chosen by themselves; forcing them puts
-    duplicates, wrapped and zero masses, infinite and NaN terms through the LDS tile / the term array as well."""
-    if walk != "default":
-        monkeypatch.setenv("NBODY_WALK_SPLIT", "3" if walk.startswith("one") else "2")
+_SPLIT = {"default": "1", "one pass forced": "3", "three passes forced": "2"}
+
+
+def _bvh_step_case(nb, orc, request, monkeypatch, capfd, seed, order, walk, theta, leaf):
+    """Four BVH steps against the oracle, bit for bit, and — because every walk gives those bits — the walk that ran, from the
+    trace, against tree_walk_phase's rule (tests/_routes.py).  The three-pass walk exists in the laboratory library only (the
+    product reads NBODY_WALK_SPLIT=2 as 1), so that variant alone asks for the `lab` fixture."""
+    use_lab = walk.startswith("three")
+    if use_lab:
+        request.getfixturevalue("lab")
+    if walk == "default":
+        monkeypatch.delenv("NBODY_WALK_SPLIT", raising=False)     # the library's own default, which the rule knows as mode 1
+    else:
+        monkeypatch.setenv("NBODY_WALK_SPLIT", _SPLIT[walk])
+    monkeypatch.setenv("NBODY_TRACE", "1")
     n = 500 + 211 * seed
     pos, vel, w = _case(seed, n)
-    theta = [50.0, 0.5, 2.0][seed % 3]
-    leaf = [64, 16, 7][seed % 3]
+    want = routes.expected_bvh_route(n, leaf, _SPLIT[walk], lab=use_lab)
     mode = orc.AS_WRITTEN if order == "as_written" else orc.CONSISTENT
+    capfd.readouterr()
     try:
         rp, rv, rw, rids, _ = orc.update_bvh(pos, vel, w, delta=0.1, theta=theta, leaf_size=leaf, mode=mode, nsteps=4, nthreads=8)
     except RuntimeError:
@@ -66,13 +75,36 @@ def test_bvh_step_differential(nb, orc, monkeypatch, seed, order, walk):
         with pytest.raises(nb._capi.NBodyError):          # the same degenerate input must be an error on the device path too
             world.update(0.1, None, n_steps=4)
         world.close()
+        assert routes.routes(capfd.readouterr().err) <= {want}
         return
     world = nb.World(pos, vel, w, method="bvh", theta=theta, leaf_size=leaf, order=order)
     world.update(0.1, None, n_steps=4)
     p, v, w2, ids = world.particles()
     world.close()
+    err = capfd.readouterr().err
     assert np.array_equal(ids, rids) and np.array_equal(w2, rw)
     assert np.array_equal(p, rp, equal_nan=True) and np.array_equal(v, rv, equal_nan=True)
+    ran = routes.parse(err)
+    assert len(ran) >= 4 and {r.route for r in ran} == {want}, (want, [r.route for r in ran], err[-600:])
+
+
+@pytest.mark.parametrize("walk", ["default", "one pass forced", "three passes forced"])
+@pytest.mark.parametrize("order", ["as_written", "consistent"])
+@pytest.mark.parametrize("seed", range(10))
+def test_bvh_step_differential(nb, orc, request, monkeypatch, capfd, seed, order, walk):
+    """`walk`: these inputs are too small for the lane = particle walks to be chosen by themselves; forcing them puts
+    duplicates, wrapped and zero masses, infinite and NaN terms through the LDS tile / the term array as well.  Leaves of 7
+    (seed % 3 == 2) are small leaves: no lane = particle walk takes them, whatever is forced, and the case asserts the
+    small-leaves walk; test_bvh_step_differential_forced_leaf16 gives the forced walks those inputs too."""
+    _bvh_step_case(nb, orc, request, monkeypatch, capfd, seed, order, walk, [50.0, 0.5, 2.0][seed % 3], [64, 16, 7][seed % 3])
+
+
+@pytest.mark.parametrize("walk", ["one pass forced", "three passes forced"])
+@pytest.mark.parametrize("order", ["as_written", "consistent"])
+@pytest.mark.parametrize("seed", range(10))
+def test_bvh_step_differential_forced_leaf16(nb, orc, request, monkeypatch, capfd, seed, order, walk):
+    """All ten inputs through each forced walk: the same seeds and thetas with leaves of 16, the smallest big leaf."""
+    _bvh_step_case(nb, orc, request, monkeypatch, capfd, seed, order, walk, [50.0, 0.5, 2.0][seed % 3], 16)
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])

@@ -4,6 +4,9 @@ The walk uses the reference's operations in the reference's DFS order, so everyt
 import numpy as np
 import pytest
 
+from tests import _routes as routes
+from tests._tol import check_fast
+
 pytestmark = pytest.mark.gpu
 F32 = np.float32
 
@@ -405,15 +408,18 @@ def test_device_bvh_build_with_long_nodes_left_after_the_blind_levels(nb, orc, l
 
 
 # ------------------------------------------------------------------ split walk (walk_split.hip)
-@pytest.mark.parametrize("mode", ["0", "2", "3"])
-def test_split_and_fused_walks_are_the_same_walk(nb, orc, lab_ctx, monkeypatch, mode):
-    """count / emit / ordered-sum (NBODY_WALK_SPLIT=2), the one-pass walk with the terms through LDS (=3) and the fused
-    wave walk (=0) against the CPU recursion: the
+@pytest.mark.parametrize("mode", ["0", "2", "3", "1"])
+def test_split_and_fused_walks_are_the_same_walk(nb, orc, lab_ctx, monkeypatch, capfd, mode):
+    """count / emit / ordered-sum (NBODY_WALK_SPLIT=2), the one-pass walk with the terms through LDS (=3, and =1: chosen by
+    itself from 4 096 targets) and the fused wave walk (=0) against the CPU recursion: the
     same nodes, pairs, operations and order of additions, so the same bits — targets = the particles (tree order), a
-    strided subset of arbitrary targets, coincident and out-of-box targets, several thetas."""
+    strided subset of arbitrary targets, coincident and out-of-box targets, several thetas.  The same bits whichever walk
+    ran, so the walk that ran is read from the trace."""
     C = nb._capi
     ctx = lab_ctx                                          # laboratory library: the test forces a variant / a slow path
     monkeypatch.setenv("NBODY_WALK_SPLIT", mode)
+    monkeypatch.setenv("NBODY_TRACE", "1")
+    capfd.readouterr()
     pos, vel, w = nb.scenes.galaxy()
     pos, vel, w = pos[::3].copy(), vel[::3].copy(), w[::3].copy()
     pos[100] = pos[101]                                    # a pair the reference skips (sum == 0)
@@ -426,19 +432,30 @@ def test_split_and_fused_walks_are_the_same_walk(nb, orc, lab_ctx, monkeypatch, 
         tg = np.concatenate([pos[::7], extra])
         ctx.upload(pos, vel, w)                            # a build permutes the rows, and the tree depends on their order
         assert np.array_equal(ctx.accel_tree(C.TREE_BVH, tg), bvh.walk(tg, theta=theta, nthreads=8))
+    ran = routes.parse(capfd.readouterr().err)
+    want = routes.expected_bvh_route(pos.shape[0], 64, mode, lab=True)
+    assert want == {"0": routes.FUSED, "2": routes.THREE_PASS, "3": routes.TILE, "1": routes.TILE}[mode]
+    assert tg.shape[0] >= routes.TILE_MIN_TARGETS              # mode 1 takes the one-pass walk by itself for both target sets
+    assert len(ran) >= 4 and {r.route for r in ran} == {want}, [(r.route, r.n_tgt) for r in ran]
 
 
-def test_split_walk_steps_equal_fused_walk_steps(nb, lab, monkeypatch):
+def test_split_walk_steps_equal_fused_walk_steps(nb, lab, monkeypatch, capfd):
     pos, vel, w = nb.scenes.galaxy()
     res = []
+    monkeypatch.setenv("NBODY_TRACE", "1")
     for mode in ("0", "2", "3", "1"):
         monkeypatch.setenv("NBODY_WALK_SPLIT", mode)
+        capfd.readouterr()
         world = nb.World(pos, vel, w, method="bvh")
         cnt = nb.Counting()
         for _ in range(5):
             world.update(0.1, cnt)
         res.append(world.particles())
         world.close()
+        ran = routes.parse(capfd.readouterr().err)                    # same bits by design: which walk ran is in the trace
+        want = routes.expected_bvh_route(pos.shape[0], 64, mode, lab=True)
+        assert want == {"0": routes.FUSED, "2": routes.THREE_PASS, "3": routes.TILE, "1": routes.TILE}[mode]
+        assert len(ran) >= 5 and {r.route for r in ran} == {want}, (mode, [r.route for r in ran])
     for other in res[1:]:
         for a, b in zip(res[0], other):
             assert np.array_equal(a, b)
@@ -811,24 +828,54 @@ def test_phase_stamps_and_event_records_time_the_same_phases(nb, lab, monkeypatc
     assert all(np.array_equal(x, y) for x, y in zip(a[4], b[4]))
 
 
-def test_node_record_fetch_variants_walk_the_same_walk(nb, lab, monkeypatch):
-    """Node records arrive by scalar loads through the constant address space (exact walk: always; FAST: from 400 000 targets) or
-    by vector loads of one address; FAST can also pin / not pin them (NBODY_WALK_FAST_REC 0 / 1 / 3).  Where they come from
-    changes no bit."""
+def test_node_record_fetch_variants_walk_the_same_walk(nb, orc, lab, monkeypatch, capfd):
+    """Node records arrive by scalar loads through the constant address space (the default of the exact and the FAST walk) or
+    by vector loads of one address (NBODY_WALK_SCALAR_REC=0); FAST can also take plain or pinned vector loads
+    (NBODY_WALK_FAST_REC 0 / 1 instead of 3).  Where they come from changes no bit — so equal bits do not show that the
+    variants ran: the trace's route lines must name three different FAST kernels, and both `srec` settings of the exact one.
+    (The switches are read at every launch: latched by the first walk of the process, this test would compare one kernel
+    with itself.)  20 000 Plummer bodies: several waves and several tile rounds, the one-pass walk by itself (n >= 4096).
+    f32 FAST through LDS rows against through registers (NBODY_WALK_FAST_ROWS=1 / 0) differ in summation order: each
+    against the oracle's walk under the FAST tolerance (tests/_tol.py), not with each other."""
     C = nb._capi
-    pos, vel, w = nb.scenes.plummer(200000, seed=61)
+    n = 20000
+    pos, vel, w = nb.scenes.plummer(n, seed=61)
+    monkeypatch.setenv("NBODY_TRACE", "1")
     for arith in (C.ARITH_AUTO, C.ARITH_FAST):
-        got = []
+        got, ran = [], set()
         for srec, frec in (("1", "0"), ("0", "1"), ("1", "3")):
             monkeypatch.setenv("NBODY_WALK_SCALAR_REC", srec)
             monkeypatch.setenv("NBODY_WALK_FAST_REC", frec)
+            capfd.readouterr()
             with C.Context(0) as c:
                 c.set_params(theta=50.0, arith=arith, order=C.ORDER_AS_WRITTEN)
                 c.upload(pos, vel, w)
                 c.update_tree(C.TREE_BVH, 0.1, 3)
                 got.append(c.download())
+            err = capfd.readouterr().err
+            assert routes.routes(err) == {routes.TILE} and len(routes.parse(err)) >= 3, err[-600:]
+            here = routes.kernels(err)
+            assert len(here) == 1, here                        # one kernel per setting ...
+            ran |= here
         for other in got[1:]:
             assert all(np.array_equal(x, y) for x, y in zip(got[0], other))
+        if arith == C.ARITH_FAST:                              # ... and another one per setting: (arm, rows, srec, rec_mode)
+            assert ran == {("fast-registers", -1, -1, 0), ("fast-registers", -1, -1, 1), ("fast-registers", -1, -1, 3)}, ran
+        else:
+            assert ran == {("exact", 8, 1, -1), ("exact", 8, 0, -1)}, ran
+    monkeypatch.setenv("NBODY_WALK_SCALAR_REC", "1")
+    monkeypatch.setenv("NBODY_WALK_FAST_REC", "3")
+    bvh = orc.BVH(pos, w)
+    ref64, norm = bvh.walk_ref(bvh.flat().pos_perm, theta=50.0, nthreads=16)
+    for rows, kernel in (("0", ("fast-registers", -1, -1, 3)), ("1", ("fast-rows", 8, 1, -1))):
+        monkeypatch.setenv("NBODY_WALK_FAST_ROWS", rows)
+        capfd.readouterr()
+        with C.Context(0) as c:
+            c.set_params(theta=50.0, arith=C.ARITH_FAST, order=C.ORDER_CONSISTENT)
+            c.upload(pos, vel, w)
+            acc = c.accel_tree(C.TREE_BVH)                     # the bodies themselves, in tree order
+        assert routes.kernels(capfd.readouterr().err) == {kernel}
+        check_fast(acc, ref64, norm, label=f" FAST rows={rows}")
 
 
 def test_f64_walks_take_theta_as_the_f32_parameter_it_is(nb, orc, ctx):
