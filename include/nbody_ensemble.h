@@ -37,9 +37,10 @@
  *   Booking.  Force and integration are fused, so the whole call's seconds are booked under sum_gravity, as the direct step
  *     books them (`counter` may be NULL).
  *   Params.  nbody_default_params' values at creation; clamp and arith are used, the rest is kept and ignored.
- *   Not offered: f64 on this handle (nbody_ensemble64_* below is the double-precision sibling); worlds of different sizes; a
- *     per-world delta or clamp; tree methods; tracers; several devices; snapshots, delta streams and frames of an ensemble;
- *     hipGraph replay.  The library reads no environment variable for any of this.
+ *   Not offered: f64 on this handle (nbody_ensemble64_* below is the double-precision sibling); worlds of different sizes on
+ *     this handle (nbody_ragged_* at the end of this file steps them together); a per-world delta or clamp; tree methods;
+ *     tracers; several devices; snapshots, delta streams and frames of an ensemble; hipGraph replay.  The library reads no
+ *     environment variable for any of this.
  * Arrays are world-major, [n_worlds][n_bodies] rows, pos / vel interleaved x,y; weight may be NULL (all 1); an upload replaces
  * the previous ensemble, whatever its shape. */
 typedef struct nbody_ensemble nbody_ensemble;
@@ -85,5 +86,52 @@ int64_t nbody_ensemble64_num_worlds(const nbody_ensemble64* e);
 int64_t nbody_ensemble64_num_bodies(const nbody_ensemble64* e);                     /* per world */
 int nbody_ensemble64_update(nbody_ensemble64* e, double delta, int n_steps, nbody_counting* counter);
 int nbody_ensemble64_accel(nbody_ensemble64* e, double* acc_xy);                    /* force only, state untouched */
+
+/* ---- ragged ensembles: worlds of different sizes stepped together, a handle of its own (f32) ----------------------
+ * A sweep over N, clusters drawn from a mass function, halos cut out of a larger run: worlds that differ in size.  Padding them
+ * to one size is wrong (a padded body of weight 0 still moves EXACT's chain and FAST's order of additions: both are functions
+ * of n), and one nbody_ensemble per distinct size is one launch chain per size again.  A ragged ensemble holds n_worlds worlds
+ * of n_bodies[k] bodies each and steps all of them with at most NBODY_RAGGED_MAX_LAUNCHES launches per step.
+ *   Arrays.  The worlds' rows come one after another in world order, with no padding: world k's rows are [off_k, off_k + n_k)
+ *     with off_k the sum of the sizes before it; pos / vel interleaved x,y; weight may be NULL (all 1).  An upload replaces the
+ *     previous ragged ensemble, whatever its sizes.
+ *   Limits.  1 <= n_bodies[k] <= 4096 for every world, n_worlds >= 1, the sizes add up to at most 2^26 rows.  Anything outside
+ *     gives NBODY_ERR_INVALID before anything is allocated, and the message names "ragged".
+ *   Contract.  Step, EXACT, FAST, AUTO (per world, per step, on the device), booking, params, trivial calls and errors, no CPU
+ *     path (nbody_ragged_create fails with NBODY_ERR_NO_DEVICE without a gfx950 device), NULL handle (NBODY_ERR_INVALID; 0 from
+ *     nbody_ragged_num_worlds / _num_rows; nbody_ragged_last_error(NULL): the last failed nbody_ragged_create or
+ *     nbody_ragged_plan on this thread): as the ensemble above states them, word for word.
+ *   Independence.  A world's bits depend only on its own rows, its own size and the params.  They do not depend on the other
+ *     worlds' sizes, contents, routes or order.  They do not depend on which launch the world falls in.  They do not depend on
+ *     how steps are split over calls.
+ *   EXACT.  Every world is bit-identical to the CPU restatement's update_direct of that world alone.
+ *   FAST.  Every world is bit-identical to nbody_ensemble_* holding that world alone (the two kernels share one body; FAST's
+ *     order of additions is a fixed function of the world's n_bodies), hence within the ensemble's tolerance.
+ *   Launches.  Worlds are grouped by the LDS they need, in size order: n <= 128, <= 256, <= 512, <= 1024, <= 2048, <= 4096; every
+ *     class that has a world is one launch per step, under the LDS of its largest member, and within a launch one block is one
+ *     (world, tile) work item of a table built at upload.  An upload through this handle always takes the ragged kernel, also
+ *     when all sizes are equal.  nbody_ragged_plan shows the plan the handle uses: for every world its launch and the first of
+ *     its (contiguous) blocks in that launch, the number of launches, and per launch (arrays of NBODY_RAGGED_MAX_LAUNCHES, zero
+ *     past n_launches) the dynamic LDS and the number of blocks.  It is pure host code: no device, no handle, every output
+ *     pointer may be NULL; sizes outside the limits give NBODY_ERR_INVALID and nothing is written.
+ *   Not offered on this handle: f64 ragged ensembles, a per-world delta or clamp, tracers, tree methods, several devices, and
+ *     what the ensemble above does not offer either. */
+#define NBODY_RAGGED_MAX_LAUNCHES 6
+typedef struct nbody_ragged nbody_ragged;
+int nbody_ragged_create(nbody_ragged** out, int device_id);
+void nbody_ragged_destroy(nbody_ragged* e);
+const char* nbody_ragged_last_error(const nbody_ragged* e);
+int nbody_ragged_set_params(nbody_ragged* e, const nbody_params* p);
+int nbody_ragged_get_params(const nbody_ragged* e, nbody_params* out);
+int nbody_ragged_upload_f32(nbody_ragged* e, int64_t n_worlds, const int64_t* n_bodies /*[n_worlds]*/, const float* pos_xy,
+                            const float* vel_xy, const uint32_t* weight);
+int nbody_ragged_download_f32(nbody_ragged* e, float* pos_xy, float* vel_xy);     /* either may be NULL */
+int64_t nbody_ragged_num_worlds(const nbody_ragged* e);
+int64_t nbody_ragged_num_rows(const nbody_ragged* e);                             /* the sum of the sizes */
+int nbody_ragged_sizes(const nbody_ragged* e, int64_t* n_bodies_out /*[num_worlds]*/);
+int nbody_ragged_update_f32(nbody_ragged* e, float delta, int n_steps, nbody_counting* counter);
+int nbody_ragged_accel_f32(nbody_ragged* e, float* acc_xy);                       /* force only, state untouched */
+int nbody_ragged_plan(int64_t n_worlds, const int64_t* n_bodies, int32_t* launch_of_world, int64_t* first_block_of_world,
+                      int32_t* n_launches, int32_t* lds_bytes_of_launch, int64_t* blocks_of_launch);
 
 #endif /* NBODY_ENSEMBLE_H */

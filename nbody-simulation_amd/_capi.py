@@ -110,6 +110,19 @@ _SIGS = {
     "nbody_ensemble64_num_bodies": (_i64, [_vp]),
     "nbody_ensemble64_update": (C.c_int, [_vp, _f64, _i32, C.POINTER(Counting)]),
     "nbody_ensemble64_accel": (C.c_int, [_vp, _vp]),
+    "nbody_ragged_create": (C.c_int, [C.POINTER(_vp), _i32]),
+    "nbody_ragged_destroy": (None, [_vp]),
+    "nbody_ragged_last_error": (C.c_char_p, [_vp]),
+    "nbody_ragged_set_params": (C.c_int, [_vp, C.POINTER(Params)]),
+    "nbody_ragged_get_params": (C.c_int, [_vp, C.POINTER(Params)]),
+    "nbody_ragged_upload_f32": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "nbody_ragged_download_f32": (C.c_int, [_vp, _vp, _vp]),
+    "nbody_ragged_num_worlds": (_i64, [_vp]),
+    "nbody_ragged_num_rows": (_i64, [_vp]),
+    "nbody_ragged_sizes": (C.c_int, [_vp, _vp]),
+    "nbody_ragged_update_f32": (C.c_int, [_vp, _f32, _i32, C.POINTER(Counting)]),
+    "nbody_ragged_accel_f32": (C.c_int, [_vp, _vp]),
+    "nbody_ragged_plan": (C.c_int, [_i64, _vp, _vp, _vp, C.POINTER(_i32), _vp, _vp]),
     "nbody_accel_tree_f32": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_accel_tree_f64": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_tree_info": (C.c_int, [_vp, C.POINTER(TreeView)]),
@@ -873,6 +886,58 @@ class EnsembleHandle(_EnsembleHandleBase):
 class Ensemble64Handle(_EnsembleHandleBase):
     """nbody_ensemble64_*: float64 worlds, the sibling of EnsembleHandle."""
     _prefix, _suffix, _dtype = "nbody_ensemble64", "", np.float64
+
+
+class RaggedHandle(_EnsembleHandleBase):
+    """nbody_ragged_*: float32 worlds of different sizes, their rows one after another in world order."""
+    _prefix, _suffix, _dtype = "nbody_ragged", "_f32", np.float32
+
+    @property
+    def shape(self):
+        """(worlds, rows of all worlds together) of the current upload; (0, 0) before one."""
+        return int(self._call("_num_worlds")), int(self._call("_num_rows"))
+
+    @property
+    def sizes(self):
+        """The bodies of every world, int64[worlds]."""
+        out = np.zeros(self.shape[0], np.int64)
+        self._check(self._call("_sizes", _ptr(out)))
+        return out
+
+    def upload(self, sizes, pos, vel, weight):
+        """sizes int64[worlds]; pos, vel [rows, 2]; weight uint32[rows] or None."""
+        sizes = np.ascontiguousarray(sizes, dtype=np.int64)
+        self._check(self._call("_upload" + self._suffix, int(sizes.shape[0]), _ptr(sizes), _ptr(pos), _ptr(vel), _ptr(weight)))
+
+    def download(self):
+        rows = self.shape[1]
+        pos, vel = np.zeros((rows, 2), self._dtype), np.zeros((rows, 2), self._dtype)
+        self._check(self._call("_download" + self._suffix, _ptr(pos), _ptr(vel)))
+        return pos, vel
+
+    def accel(self):
+        acc = np.zeros((self.shape[1], 2), self._dtype)
+        self._check(self._call("_accel" + self._suffix, _ptr(acc)))
+        return acc
+
+
+RAGGED_MAX_LAUNCHES = 6
+
+
+def ragged_plan(sizes):
+    """nbody_ragged_plan of these sizes (pure host code) -> (launch_of_world int32[worlds], first_block_of_world int64[worlds],
+    lds_bytes int32[launches], blocks int64[launches]); NBodyError(ERR_INVALID) for sizes outside the limits."""
+    lib = load()
+    sizes = np.ascontiguousarray(sizes, dtype=np.int64)
+    b = int(sizes.shape[0])
+    launch, first = np.zeros(b, np.int32), np.zeros(b, np.int64)
+    lds, blocks = np.zeros(RAGGED_MAX_LAUNCHES, np.int32), np.zeros(RAGGED_MAX_LAUNCHES, np.int64)
+    n = _i32(0)
+    rc = lib.nbody_ragged_plan(b, _ptr(sizes), _ptr(launch), _ptr(first), C.byref(n), _ptr(lds), _ptr(blocks))
+    if rc != OK:
+        msg = lib.nbody_ragged_last_error(None)
+        raise NBodyError(rc, msg.decode() if msg else "")
+    return launch, first, lds[:n.value].copy(), blocks[:n.value].copy()
 
 
 def mass_hint(weight) -> float:

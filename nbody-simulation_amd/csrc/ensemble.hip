@@ -1,28 +1,9 @@
-// libnbody_hip — ensembles: the C entry points of nbody_ensemble_* (include/nbody_hip.h) over the driver of ensemble_driver.h,
-// and what is f32 about them: the masses uploaded as `weight as f32`, the arith rule of the f32 direct step, the kernel of
-// ensemble_kernels.hip.
-#include "ensemble_driver.h"
+// libnbody_hip — ensembles: the C entry points of nbody_ensemble_* (include/nbody_hip.h) over the driver of ensemble_driver.h
+// in the precision of ensemble_f32.h.
+#include "ensemble_f32.h"
 
 using namespace nbody;
 
-struct EnsF32 {
-  using Real = float;
-  using Vec2 = float2;
-  using Mass = float;
-  using Args = EnsembleArgs;
-  static constexpr const char* kCreate = "nbody_ensemble_create";
-  static const float* stage(const uint32_t* weight, size_t rows, std::vector<float>& tmp) {
-    tmp.resize(rows);
-    for (size_t i = 0; i < rows; ++i) tmp[i] = weight ? (float)weight[i] : 1.0f;  // `weight as f32`, main.rs:360
-    return tmp.data();
-  }
-  static void route(EnsembleArgs& a, const float* mass, const nbody_params& p) {
-    a.mass = mass;
-    a.clamp = p.clamp;
-    a.arith = direct_arith_f32(p.arith, p.clamp);  // a clamp below kFastClampFloor (or NaN): every world EXACT
-  }
-  static hipError_t launch(hipStream_t s, int64_t n_worlds, const EnsembleArgs& a) { return launch_ensemble_step(s, n_worlds, a); }
-};
 struct nbody_ensemble : EnsembleState<EnsF32> {};
 
 NB_API int nbody_ensemble_create(nbody_ensemble** out, int device_id) { return ens_create(out, device_id); }

@@ -12,6 +12,7 @@ struct EnsF64 {
   using Mass = uint32_t;
   using Args = Ensemble64Args;
   static constexpr const char* kCreate = "nbody_ensemble64_create";
+  static constexpr const char* kWho = "ensemble";
   static const uint32_t* stage(const uint32_t* weight, size_t rows, std::vector<uint32_t>& tmp) {
     if (weight) return weight;  // uploaded from where they are
     tmp.assign(rows, 1u);

@@ -5,10 +5,14 @@
 //
 // P supplies: Real, Vec2 (the element types), Mass (what the device keeps per body), Args (the kernel's arguments);
 //   kCreate                        the create call's name, the prefix of its messages;
+//   kWho                           the word that every other message of the handle begins with ("ensemble", "ragged");
 //   stage(weight, rows, tmp)       -> the rows Mass values to upload (tmp is theirs to fill);
 //   route(args, mass, params)      the masses and the arithmetic of a launch, from the handle's parameters;
 //   launch(stream, n_worlds, args) one step, or one force evaluation, of all worlds.
-// A handle is a struct of its own derived from EnsembleState<P>: the C header declares two distinct opaque types.
+// A handle is a struct of its own derived from EnsembleState<P>: the C header declares distinct opaque types.
+// The ragged handle (ragged_driver.h: worlds of different sizes, several launches per step) is built from the same parts: the
+// state, create / destroy, params and errors as they are, and upload, download, update and accel through the *_rows / *_with
+// functions below, which take the number of rows and the step's launches from their caller.
 #pragma once
 #include <cstring>
 #include <new>
@@ -27,7 +31,8 @@ template <class P> struct EnsembleState {
   std::string err;
   nbody_params params{};
   nbody_counting counting{};
-  int64_t n_worlds = 0, n_bodies = 0;  // 0: nothing uploaded
+  int64_t n_worlds = 0, n_bodies = 0;  // 0: nothing uploaded (n_bodies stays 0 where the worlds have sizes of their own)
+  int64_t rows = 0;                    // the rows of all worlds together
   typename P::Vec2* pos[2] = {nullptr, nullptr};
   int cur = 0;
   typename P::Vec2* vel = nullptr;
@@ -42,7 +47,7 @@ template <class P> int ens_fail(EnsembleState<P>* e, int code, const std::string
   return code;
 }
 template <class P> int ens_fail_hip(EnsembleState<P>* e, hipError_t h, const char* what) {
-  return ens_fail<P>(e, NBODY_ERR_HIP, std::string("ensemble: ") + what + ": " + hipGetErrorString(h));
+  return ens_fail<P>(e, NBODY_ERR_HIP, std::string(P::kWho) + ": " + what + ": " + hipGetErrorString(h));
 }
 #define ENS_HIPCHK(e, call)                                        \
   do {                                                             \
@@ -52,7 +57,7 @@ template <class P> int ens_fail_hip(EnsembleState<P>* e, hipError_t h, const cha
 
 template <class P> void ens_free(EnsembleState<P>* e) {
   free_dev(e->pos[0]); free_dev(e->pos[1]); free_dev(e->vel); free_dev(e->mass); free_dev(e->acc);
-  e->n_worlds = e->n_bodies = 0;
+  e->n_worlds = e->n_bodies = e->rows = 0;
   e->cur = 0;
 }
 
@@ -111,7 +116,7 @@ template <class P> const char* ens_last_error(const EnsembleState<P>* e) { retur
 
 template <class P> int ens_set_params(EnsembleState<P>* e, const nbody_params* p) {
   if (!e || !p) return NBODY_ERR_INVALID;
-  if (p->arith < NBODY_ARITH_AUTO || p->arith > NBODY_ARITH_EXACT) return ens_fail(e, NBODY_ERR_INVALID, "ensemble set_params: bad arith");
+  if (p->arith < NBODY_ARITH_AUTO || p->arith > NBODY_ARITH_EXACT) return ens_fail(e, NBODY_ERR_INVALID, std::string(P::kWho) + " set_params: bad arith");
   e->params = *p;
   return NBODY_OK;
 }
@@ -121,21 +126,16 @@ template <class P> int ens_get_params(const EnsembleState<P>* e, nbody_params* o
   return NBODY_OK;
 }
 
+// The handle's previous arrays freed and `rows` rows allocated and filled from the caller's (the stream is drained before and
+// after).  On failure nothing is left allocated.
 template <class P>
-int ens_upload(EnsembleState<P>* e, int64_t n_worlds, int64_t n_bodies, const typename P::Real* pos, const typename P::Real* vel,
-               const uint32_t* weight) {
+int ens_store_rows(EnsembleState<P>* e, int64_t n_rows, const typename P::Real* pos, const typename P::Real* vel, const uint32_t* weight) {
   using Vec2 = typename P::Vec2;
   using Mass = typename P::Mass;
-  if (!e) return NBODY_ERR_INVALID;
-  if (n_bodies < 1 || n_bodies > kEnsembleMaxBodies)
-    return ens_fail(e, NBODY_ERR_INVALID, "ensemble upload: n_bodies must be 1 .. 4096 (above that a context per world is the tool)");
-  if (n_worlds < 1 || n_worlds > kEnsembleMaxRows / n_bodies)
-    return ens_fail(e, NBODY_ERR_INVALID, "ensemble upload: n_worlds must be >= 1 and n_worlds * n_bodies <= 2^26");
-  if (!pos || !vel) return ens_fail(e, NBODY_ERR_INVALID, "ensemble upload: pos_xy or vel_xy is NULL");
   ENS_HIPCHK(e, hipSetDevice(e->device));
   ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
   ens_free(e);
-  const size_t rows = (size_t)(n_worlds * n_bodies);
+  const size_t rows = (size_t)n_rows;
   std::vector<Mass> tmp;
   const Mass* const mass = P::stage(weight, rows, tmp);
   hipError_t h = hipMalloc((void**)&e->pos[0], rows * sizeof(Vec2));
@@ -150,6 +150,20 @@ int ens_upload(EnsembleState<P>* e, int64_t n_worlds, int64_t n_bodies, const ty
     ens_free(e);
     return ens_fail_hip(e, h, "upload");
   }
+  e->rows = n_rows;
+  return NBODY_OK;
+}
+
+template <class P>
+int ens_upload(EnsembleState<P>* e, int64_t n_worlds, int64_t n_bodies, const typename P::Real* pos, const typename P::Real* vel,
+               const uint32_t* weight) {
+  if (!e) return NBODY_ERR_INVALID;
+  if (n_bodies < 1 || n_bodies > kEnsembleMaxBodies)
+    return ens_fail(e, NBODY_ERR_INVALID, "ensemble upload: n_bodies must be 1 .. 4096 (above that a context per world is the tool)");
+  if (n_worlds < 1 || n_worlds > kEnsembleMaxRows / n_bodies)
+    return ens_fail(e, NBODY_ERR_INVALID, "ensemble upload: n_worlds must be >= 1 and n_worlds * n_bodies <= 2^26");
+  if (!pos || !vel) return ens_fail(e, NBODY_ERR_INVALID, "ensemble upload: pos_xy or vel_xy is NULL");
+  if (int rc = ens_store_rows(e, n_worlds * n_bodies, pos, vel, weight)) return rc;
   e->n_worlds = n_worlds;
   e->n_bodies = n_bodies;
   return NBODY_OK;
@@ -157,19 +171,21 @@ int ens_upload(EnsembleState<P>* e, int64_t n_worlds, int64_t n_bodies, const ty
 
 template <class P> int ens_download(EnsembleState<P>* e, typename P::Real* pos, typename P::Real* vel) {
   if (!e) return NBODY_ERR_INVALID;
-  if (!e->n_worlds) return ens_fail(e, NBODY_ERR_INVALID, "ensemble download: nothing uploaded");
+  if (!e->n_worlds) return ens_fail(e, NBODY_ERR_INVALID, std::string(P::kWho) + " download: nothing uploaded");
   ENS_HIPCHK(e, hipSetDevice(e->device));
-  const size_t bytes = (size_t)(e->n_worlds * e->n_bodies) * sizeof(typename P::Vec2);
+  const size_t bytes = (size_t)e->rows * sizeof(typename P::Vec2);
   if (pos) ENS_HIPCHK(e, hipMemcpyAsync(pos, e->pos[e->cur], bytes, hipMemcpyDeviceToHost, e->stream));
   if (vel) ENS_HIPCHK(e, hipMemcpyAsync(vel, e->vel, bytes, hipMemcpyDeviceToHost, e->stream));
   ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
   return NBODY_OK;
 }
 
-template <class P> int ens_update(EnsembleState<P>* e, typename P::Real delta, int n_steps, nbody_counting* counter) {
+// n_steps steps; `launch(args)` enqueues one step (or one force evaluation) of every world on e->stream and returns a hipError_t.
+template <class P, class Launch>
+int ens_update_with(EnsembleState<P>* e, typename P::Real delta, int n_steps, nbody_counting* counter, Launch launch) {
   if (!e) return NBODY_ERR_INVALID;
-  if (!e->n_worlds) return ens_fail(e, NBODY_ERR_INVALID, "ensemble update: nothing uploaded");
-  if (n_steps < 0) return ens_fail(e, NBODY_ERR_INVALID, "ensemble update: n_steps < 0");
+  if (!e->n_worlds) return ens_fail(e, NBODY_ERR_INVALID, std::string(P::kWho) + " update: nothing uploaded");
+  if (n_steps < 0) return ens_fail(e, NBODY_ERR_INVALID, std::string(P::kWho) + " update: n_steps < 0");
   if (n_steps == 0) return NBODY_OK;
   ENS_HIPCHK(e, hipSetDevice(e->device));
   const double t_begin = now_s();
@@ -178,7 +194,7 @@ template <class P> int ens_update(EnsembleState<P>* e, typename P::Real delta, i
     a.pos_out = e->pos[1 - e->cur];
     a.vel = e->vel;
     a.delta = delta;
-    ENS_HIPCHK(e, P::launch(e->stream, e->n_worlds, a));
+    ENS_HIPCHK(e, launch(a));
     e->cur = 1 - e->cur;  // (the launches are in stream order: the next one reads what this one writes)
   }
   ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -189,19 +205,27 @@ template <class P> int ens_update(EnsembleState<P>* e, typename P::Real delta, i
   return NBODY_OK;
 }
 
-template <class P> int ens_accel(EnsembleState<P>* e, typename P::Real* acc_xy) {
+template <class P> int ens_update(EnsembleState<P>* e, typename P::Real delta, int n_steps, nbody_counting* counter) {
+  return ens_update_with(e, delta, n_steps, counter, [e](const typename P::Args& a) { return P::launch(e->stream, e->n_worlds, a); });
+}
+
+template <class P, class Launch> int ens_accel_with(EnsembleState<P>* e, typename P::Real* acc_xy, Launch launch) {
   if (!e) return NBODY_ERR_INVALID;
-  if (!e->n_worlds) return ens_fail(e, NBODY_ERR_INVALID, "ensemble accel: nothing uploaded");
-  if (!acc_xy) return ens_fail(e, NBODY_ERR_INVALID, "ensemble accel: acc_xy is NULL");
+  if (!e->n_worlds) return ens_fail(e, NBODY_ERR_INVALID, std::string(P::kWho) + " accel: nothing uploaded");
+  if (!acc_xy) return ens_fail(e, NBODY_ERR_INVALID, std::string(P::kWho) + " accel: acc_xy is NULL");
   ENS_HIPCHK(e, hipSetDevice(e->device));
-  const size_t bytes = (size_t)(e->n_worlds * e->n_bodies) * sizeof(typename P::Vec2);
+  const size_t bytes = (size_t)e->rows * sizeof(typename P::Vec2);
   if (!e->acc) ENS_HIPCHK(e, hipMalloc((void**)&e->acc, bytes));
   typename P::Args a = ens_args(e);
   a.acc_out = e->acc;
-  ENS_HIPCHK(e, P::launch(e->stream, e->n_worlds, a));
+  ENS_HIPCHK(e, launch(a));
   ENS_HIPCHK(e, hipMemcpyAsync(acc_xy, e->acc, bytes, hipMemcpyDeviceToHost, e->stream));
   ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
   return NBODY_OK;
+}
+
+template <class P> int ens_accel(EnsembleState<P>* e, typename P::Real* acc_xy) {
+  return ens_accel_with(e, acc_xy, [e](const typename P::Args& a) { return P::launch(e->stream, e->n_worlds, a); });
 }
 
 #undef ENS_HIPCHK

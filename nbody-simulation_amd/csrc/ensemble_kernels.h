@@ -8,15 +8,14 @@
 //                  (2 .. 64, at least 4 targets per block) and their partial sums meet in a butterfly of DPP adds inside a
 //                  row of 16 lanes, v_permlane16_swap across rows, v_permlane32_swap across the halves of the wave.
 // FAST's order of additions is a function of n alone (ensemble_kernels.hip), EXACT is one ascending-j chain per target.
+// Worlds of different sizes (nbody_ragged_*) run the same block body from a table of (world, tile) work items: below.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace nbody {
+#include "ensemble_shape.h"  // kEnsembleMaxBodies, kEnsembleMaxRows, kEnsembleBlock, ensemble_split, ensemble_lds_bytes
 
-constexpr int kEnsembleMaxBodies = 4096;
-constexpr int64_t kEnsembleMaxRows = 1ll << 26;  // n_worlds * n_bodies
-constexpr int kEnsembleBlock = 256;
+namespace nbody {
 
 struct EnsembleArgs {
   const float2* pos_in = nullptr;  // [n_worlds][n_bodies], read by every block of the world
@@ -30,16 +29,13 @@ struct EnsembleArgs {
   int arith = 0;                   // nbody_arith; AUTO decides per world in the kernel
 };
 
-// Lanes that share one target's sources.
-inline int ensemble_split(int n_bodies) {
-  if (n_bodies > 128) return 1;
-  int split = 2, targets = 128;
-  while (targets / 2 >= n_bodies && split < 64) { targets /= 2; split *= 2; }
-  return split;
-}
-inline size_t ensemble_lds_bytes(int n_bodies) { return (size_t)((n_bodies + 1) / 2) * 24; }  // couples {xA, xB, yA, yB} + {mA, mB}
-
 // One step (or, without vel / pos_out, one force evaluation) of all n_worlds worlds on `s`.
 hipError_t launch_ensemble_step(hipStream_t s, int64_t n_worlds, EnsembleArgs a);
+
+// Ragged ensembles (nbody_ragged_*): worlds of different sizes.  A block is one work item (world, tile) of the table that
+// ragged_plan.h lays out: {row0, n | tile << 16} — the world's first row among all rows, its size, the tile of its targets.  One
+// launch of the plan: `blocks` items from `items`, `lds_bytes` = ensemble_lds_bytes of the largest world among them; n_bodies and
+// tiles of `a` are not read.  Every world computes exactly what launch_ensemble_step computes for a world of its size.
+hipError_t launch_ensemble_step_ragged(hipStream_t s, int64_t blocks, size_t lds_bytes, const uint2* items, EnsembleArgs a);
 
 }  // namespace nbody

@@ -46,19 +46,18 @@ __device__ __forceinline__ float ens_abs_sum(float a, float b) {
   return r;
 }
 
+// What a block computes: one tile of the targets of the world whose rows are row0 .. row0 + n — its sources staged in LDS with
+// the AUTO decision taken on the way, then the EXACT or the FAST arm.  A function of the world through (n, row0, tile) alone: the
+// uniform kernel and the ragged one share it, and with it every bit.  Every thread of the block calls it (it holds a barrier).
 template <int SPLIT>
-__global__ __launch_bounds__(kEnsembleBlock) void ensemble_step(const EnsembleArgs a) {
+__device__ __forceinline__ void ens_world_tile(const EnsembleArgs& a, const int n, const size_t row0, const unsigned tile) {
   constexpr int TPB = kEnsembleBlock / SPLIT;  // targets per block
   extern __shared__ __attribute__((aligned(16))) unsigned char ens_lds[];
-  const int n = a.n_bodies;
   const int nc = (n + 1) >> 1;  // couples
   float* const cplf = reinterpret_cast<float*>(ens_lds);
   const ens_v4f* const cpl = reinterpret_cast<const ens_v4f*>(ens_lds);
   float* const massf = cplf + 4 * nc;
   const ens_v2f* const mass2 = reinterpret_cast<const ens_v2f*>(massf);
-
-  const unsigned world = blockIdx.x / a.tiles, tile = blockIdx.x - world * a.tiles;
-  const size_t row0 = (size_t)world * (size_t)n;
 
   // ---- the world's sources into LDS, and its AUTO decision on the way
   int bad = 0;
@@ -142,6 +141,32 @@ __global__ __launch_bounds__(kEnsembleBlock) void ensemble_step(const EnsembleAr
   if (live && part == 0) ens_integrate(a, row0 + t, px, py, ax, ay);
 }
 
+template <int SPLIT>
+__global__ __launch_bounds__(kEnsembleBlock) void ensemble_step(const EnsembleArgs a) {
+  const int n = a.n_bodies;
+  const unsigned world = blockIdx.x / a.tiles, tile = blockIdx.x - world * a.tiles;
+  ens_world_tile<SPLIT>(a, n, (size_t)world * (size_t)n, tile);
+}
+
+// Ragged: the block's work item {row0, n | tile << 16} is the same in every lane (a scalar load), so the switch on the
+// world's lane split is taken by the whole block — the barrier of the staging and the butterfly of FAST see every thread.
+__global__ __launch_bounds__(kEnsembleBlock) void ensemble_step_ragged(const EnsembleArgs a, const uint2* __restrict__ items) {
+  const uint2 item = items[blockIdx.x];
+  const size_t row0 = (size_t)(unsigned)__builtin_amdgcn_readfirstlane(item.x);
+  const unsigned packed = __builtin_amdgcn_readfirstlane(item.y);
+  const int n = (int)(packed & 0xffffu);
+  const unsigned tile = packed >> 16;
+  switch (ensemble_split(n)) {
+    case 1: ens_world_tile<1>(a, n, row0, tile); break;
+    case 2: ens_world_tile<2>(a, n, row0, tile); break;
+    case 4: ens_world_tile<4>(a, n, row0, tile); break;
+    case 8: ens_world_tile<8>(a, n, row0, tile); break;
+    case 16: ens_world_tile<16>(a, n, row0, tile); break;
+    case 32: ens_world_tile<32>(a, n, row0, tile); break;
+    default: ens_world_tile<64>(a, n, row0, tile); break;
+  }
+}
+
 }  // namespace
 
 hipError_t launch_ensemble_step(hipStream_t s, int64_t n_worlds, EnsembleArgs a) {
@@ -162,6 +187,12 @@ hipError_t launch_ensemble_step(hipStream_t s, int64_t n_worlds, EnsembleArgs a)
     default: NB_ENS_GO(64); break;
   }
 #undef NB_ENS_GO
+  return hipGetLastError();
+}
+
+hipError_t launch_ensemble_step_ragged(hipStream_t s, int64_t blocks, size_t lds_bytes, const uint2* items, EnsembleArgs a) {
+  if (blocks < 1 || blocks > kEnsembleMaxRows || !items || lds_bytes > ensemble_lds_bytes(kEnsembleMaxBodies)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ensemble_step_ragged, dim3((unsigned)blocks), dim3(kEnsembleBlock), lds_bytes, s, a, items);
   return hipGetLastError();
 }
 

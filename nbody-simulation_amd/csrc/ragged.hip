@@ -1,0 +1,53 @@
+// libnbody_hip — ragged ensembles: the C entry points of nbody_ragged_* (include/nbody_ensemble.h) over the driver of
+// ragged_driver.h in the precision of ensemble_f32.h, and nbody_ragged_plan, the plan of ragged_plan.h as the ABI shows it.
+#include "ensemble_f32.h"
+#include "ragged_driver.h"
+
+using namespace nbody;
+
+static_assert(NBODY_RAGGED_MAX_LAUNCHES == kRaggedMaxLaunches, "the header's constant is the plan's");
+static_assert(sizeof(RaggedItem) == sizeof(uint2), "a work item is the device's uint2");
+
+struct RagF32 : EnsF32 {
+  static constexpr const char* kCreate = "nbody_ragged_create";
+  static constexpr const char* kWho = "ragged";
+  static hipError_t launch_items(hipStream_t s, int64_t blocks, size_t lds_bytes, const uint2* items, const EnsembleArgs& a) {
+    return launch_ensemble_step_ragged(s, blocks, lds_bytes, items, a);
+  }
+};
+struct nbody_ragged : RaggedState<RagF32> {};
+
+NB_API int nbody_ragged_create(nbody_ragged** out, int device_id) { return ens_create(out, device_id); }
+NB_API void nbody_ragged_destroy(nbody_ragged* e) { ens_destroy(e); }
+NB_API const char* nbody_ragged_last_error(const nbody_ragged* e) { return ens_last_error<RagF32>(e); }
+NB_API int nbody_ragged_set_params(nbody_ragged* e, const nbody_params* p) { return ens_set_params<RagF32>(e, p); }
+NB_API int nbody_ragged_get_params(const nbody_ragged* e, nbody_params* out) { return ens_get_params<RagF32>(e, out); }
+NB_API int nbody_ragged_upload_f32(nbody_ragged* e, int64_t n_worlds, const int64_t* n_bodies, const float* pos, const float* vel,
+                                   const uint32_t* weight) {
+  return ragged_upload<RagF32>(e, n_worlds, n_bodies, pos, vel, weight);
+}
+NB_API int nbody_ragged_download_f32(nbody_ragged* e, float* pos, float* vel) { return ens_download<RagF32>(e, pos, vel); }
+NB_API int64_t nbody_ragged_num_worlds(const nbody_ragged* e) { return e ? e->n_worlds : 0; }
+NB_API int64_t nbody_ragged_num_rows(const nbody_ragged* e) { return e ? e->rows : 0; }
+NB_API int nbody_ragged_sizes(const nbody_ragged* e, int64_t* n_bodies_out) {
+  if (!e || !n_bodies_out) return NBODY_ERR_INVALID;
+  for (int64_t k = 0; k < e->n_worlds; ++k) n_bodies_out[k] = e->sizes[(size_t)k];
+  return NBODY_OK;
+}
+NB_API int nbody_ragged_update_f32(nbody_ragged* e, float delta, int n_steps, nbody_counting* counter) {
+  return ragged_update<RagF32>(e, delta, n_steps, counter);
+}
+NB_API int nbody_ragged_accel_f32(nbody_ragged* e, float* acc_xy) { return ragged_accel<RagF32>(e, acc_xy); }
+
+NB_API int nbody_ragged_plan(int64_t n_worlds, const int64_t* n_bodies, int32_t* launch_of_world, int64_t* first_block_of_world,
+                             int32_t* n_launches, int32_t* lds_bytes_of_launch, int64_t* blocks_of_launch) {
+  RaggedPlan plan;
+  if (const int rc = ragged_plan(n_worlds, n_bodies, &plan, launch_of_world, first_block_of_world))
+    return ens_fail<RagF32>(nullptr, NBODY_ERR_INVALID, ragged_plan_error(rc));  // (read with nbody_ragged_last_error(NULL))
+  if (n_launches) *n_launches = plan.n_launches;
+  for (int l = 0; l < kRaggedMaxLaunches; ++l) {
+    if (lds_bytes_of_launch) lds_bytes_of_launch[l] = plan.lds_bytes[l];
+    if (blocks_of_launch) blocks_of_launch[l] = plan.blocks[l];
+  }
+  return NBODY_OK;
+}

@@ -10,6 +10,11 @@ FAST within the tolerance of DESIGN.md, AUTO choosing between them per world and
 same constructor and methods, float64 arrays only: every world takes the step of an f64 `World(method="direct")` — EXACT and AUTO
 bit-identical to the oracle's update_direct on float64, FAST (opt-in, per world and per step on the device) within 1e-12 of
 sum |term|.  Shapes, dtypes and the size limits are checked here, with ValueError, before a handle exists.
+
+`RaggedEnsemble` (nbody_ragged_*) holds float32 worlds of DIFFERENT sizes — a sweep over N, clusters drawn from a mass function,
+halos cut out of a larger run — and steps them together with at most six launches per step (`ragged_plan` shows which).  Every
+world takes the same step: EXACT bit-identical to the oracle of that world alone, FAST bit-identical to an `Ensemble` holding
+that world alone, AUTO per world and per step on the device.
 """
 from __future__ import annotations
 
@@ -136,3 +141,112 @@ class Ensemble64(_EnsembleBase):
     @staticmethod
     def _new_handle(device):
         return _capi.Ensemble64Handle(device)
+
+
+def _checked_ragged(positions, velocities, weights):
+    """-> (sizes int64[B], position[rows,2], velocity[rows,2], weight uint32[rows] or None), the worlds' rows one after another;
+    ValueError for anything else.  Nothing is copied before every world has passed."""
+    who = "RaggedEnsemble"
+    for name, seq in (("positions", positions), ("velocities", velocities)) + ((("weights", weights),) if weights is not None else ()):
+        if not hasattr(seq, "__len__"):
+            raise ValueError(f"{who}: {name} must be a sequence of per-world arrays")
+    b = len(positions)
+    if b < 1:
+        raise ValueError(f"{who}: at least one world")
+    if len(velocities) != b or (weights is not None and len(weights) != b):
+        raise ValueError(f"{who}: positions, velocities and weights must be lists of equal length ({b} worlds)")
+    sizes, rows = [], 0
+    for k in range(b):
+        p, v = np.asarray(positions[k]), np.asarray(velocities[k])
+        for name, a in (("position", p), ("velocity", v)):
+            if a.dtype != np.float32:
+                raise ValueError(f"{who}: world {k}: {name} must be float32 (got {a.dtype})")
+        if p.ndim != 2 or p.shape[1] != 2:
+            raise ValueError(f"{who}: world {k}: position must be [n, 2], got {p.shape}")
+        if v.shape != p.shape:
+            raise ValueError(f"{who}: world {k}: velocity {v.shape} does not match position {p.shape}")
+        n = p.shape[0]
+        if not 1 <= n <= MAX_BODIES:
+            raise ValueError(f"{who}: world {k}: 1 .. {MAX_BODIES} bodies per world, got {n} (above that a World per world is the tool)")
+        if weights is not None:
+            w = np.asarray(weights[k])
+            if w.shape != (n,):
+                raise ValueError(f"{who}: world {k}: weight must be [n] = {(n,)}, got {w.shape}")
+            if w.dtype.kind not in "ui":
+                raise ValueError(f"{who}: world {k}: weight must be an integer array (u32 upstream), got {w.dtype}")
+        sizes.append(n)
+        rows += n
+        if rows > MAX_ROWS:
+            raise ValueError(f"{who}: the sizes add up to more than 2^26 rows")
+    position = np.ascontiguousarray(np.concatenate([np.asarray(p) for p in positions]))
+    velocity = np.ascontiguousarray(np.concatenate([np.asarray(v) for v in velocities]))
+    weight = None if weights is None else np.ascontiguousarray(np.concatenate([np.asarray(w) for w in weights]), dtype=np.uint32)
+    return np.asarray(sizes, np.int64), position, velocity, weight
+
+
+class RaggedEnsemble:
+    """Worlds of different sizes, stepped together: positions, velocities are sequences of [n_k, 2] float32 arrays, weights a
+    sequence of [n_k] integer arrays or None (all 1).  1 .. 4096 bodies per world, at most 2^26 bodies in all."""
+
+    def __init__(self, positions, velocities, weights=None, *, device=0, clamp=0.001, arith="auto"):
+        if arith not in _ARITH:
+            raise ValueError(f"arith must be one of {sorted(_ARITH)}")
+        self.h = None
+        args = _checked_ragged(positions, velocities, weights)
+        self.h = _capi.RaggedHandle(device)
+        self.h.set_params(clamp=float(clamp), arith=_ARITH[arith])
+        self._upload(*args)
+
+    def _upload(self, sizes, position, velocity, weight):
+        self.h.upload(sizes, position, velocity, weight)
+        self._sizes = sizes
+        self._cuts = np.cumsum(sizes)[:-1]
+        self._weight = np.ones(int(sizes.sum()), np.uint32) if weight is None else weight.copy()
+
+    def upload(self, positions, velocities, weights=None):
+        """Replaces the worlds by others, of any sizes."""
+        self._upload(*_checked_ragged(positions, velocities, weights))
+
+    def _per_world(self, a):
+        return [w.copy() for w in np.split(a, self._cuts)]
+
+    @property
+    def sizes(self):
+        """The bodies of every world, in world order."""
+        return [int(n) for n in self._sizes]
+
+    def update(self, delta: float, counter: Counting | None = None, n_steps: int = 1):
+        """n_steps direct steps of every world; the call's seconds go to counter.sum_gravity."""
+        self.h.update(delta, n_steps, counter)
+
+    def particles(self):
+        """-> (positions, velocities, weights): lists of per-world arrays [n_k, 2], [n_k, 2], [n_k]; rows never move."""
+        pos, vel = self.h.download()
+        return self._per_world(pos), self._per_world(vel), self._per_world(self._weight)
+
+    def accel(self):
+        """-> a list of acc[n_k, 2]: the accelerations at the current positions; the state is untouched."""
+        return self._per_world(self.h.accel())
+
+    def close(self):
+        if getattr(self, "h", None) is not None:
+            self.h.close()
+            self.h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def ragged_plan(sizes):
+    """The launches a RaggedEnsemble of these sizes takes per step (nbody_ragged_plan; host code, no GPU needed) -> dict:
+    launch_of_world, first_block_of_world (a world's blocks are contiguous in its launch), lds_bytes and blocks per launch."""
+    sizes = [int(n) for n in sizes]
+    if not sizes or min(sizes) < 1 or max(sizes) > MAX_BODIES or sum(sizes) > MAX_ROWS:
+        raise ValueError(f"ragged_plan: at least one world, 1 .. {MAX_BODIES} bodies per world, at most 2^26 in all")
+    launch, first, lds, blocks = _capi.ragged_plan(sizes)
+    return dict(launch_of_world=launch, first_block_of_world=first, lds_bytes=lds, blocks=blocks)
