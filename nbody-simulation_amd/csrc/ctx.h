@@ -71,7 +71,7 @@ template <class T> struct State {
   int bvh_levels_stable = 0;     // consecutive step-ahead builds that had exactly that many: after eight the spare blind level is dropped
   bool bb_flags_clean = false;   // the BVH build's flags and level counters are zero (the step enqueued ahead left them so)
   bool ahead_total_due = false;  // the last ahead-step's exact term count has not been read back yet
-  // split walk (walk_split.hip): counts/offsets scratch and the term array
+  // split walk (walk_prepare.hip, walk_lab.hip): counts/offsets scratch and the term array
   char* ws_scratch = nullptr;
   size_t ws_scratch_bytes = 0;
   void* ws_terms = nullptr;

@@ -21,7 +21,7 @@ template <int CTRL> __device__ __forceinline__ double ens_dpp(double v) {
   const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), CTRL, 0xf, 0xf, true);
   return ens_join((uint32_t)lo, (uint32_t)hi);
 }
-// v_permlane16_swap / v_permlane32_swap through inline asm, as walk_split.hip does (the s_nop covers "VALU writes a VGPR, a
+// v_permlane16_swap / v_permlane32_swap through inline asm, as walk_device.h does (the s_nop covers "VALU writes a VGPR, a
 // permlane swap reads it"): with both operands a copy of r, the sum of the two results is r of this row + r of its neighbour
 // row (rows 0|1, 2|3), resp. r of this half + r of the other half of the wave.
 __device__ __forceinline__ float ens_add_neighbour_row(float r) {

@@ -1,7 +1,7 @@
 // libnbody_hip — the Barnes-Hut step driver: phase timing, the walk phase (main.rs:406-416), the f32 BVH step enqueued whole
 // ahead of the host (bvh_step_ahead), the plain and the sharded step, the row exchange of a sharded step, and the tree entry
 // points of the C ABI (nbody_update_tree_*, nbody_wait, nbody_accel_tree_*, ...).  Builds: tree_build_driver.hip.
-// Kernels: walk_split.hip, tree_kernels.hip, bvh_build.hip.
+// Kernels: walk_prepare.hip, walk_tile.hip, walk_tile_fast.hip, walk_lab.hip (launched through walk_launch.hip), tree_kernels.hip, bvh_build.hip.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -163,7 +163,7 @@ int tree_walk_phase(nbody_ctx* c, State<T>& s, int kind, const void* tgt_pos, in
   } else { w.tgt_pos = s.set[s.cur].pos; w.n_tgt = slice_count >= 0 ? slice_count : s.n; w.tgt_index = s.order_dev + first; }
   bool done = false;
   {
-    // Big leaves: a leaf's terms are evaluated lane = particle (walk_split.hip): in one pass with the terms handed over
+    // Big leaves: a leaf's terms are evaluated lane = particle (walk_tile.hip, walk_tile_fast.hip): in one pass with the terms handed over
     // through LDS (walk_tile), or in three passes through a term array.  NBODY_WALK_SPLIT: 0 never (fused walk), 1 one pass
     // when it pays (default), 3 one pass whenever possible; laboratory build only: 4 / 2 three passes when it pays / whenever
     // possible (the round-1 design the one-pass walk replaced; the product treats them as 1).

@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void tree_walk_wave(const WalkArgs<T> a) {
   const T theta = a.theta, clamp = a.clamp;
   const int n_nodes = a.n_nodes;
   T ax = 0, ay = 0;
-  // FAST in f32: two-level summation (walk_split.hip, walk_tile_fast) — the terms go to a block sum that joins the running total
+  // FAST in f32: two-level summation (walk_tile_fast.hip) — the terms go to a block sum that joins the running total
   // every 32nd leaf step, so that a long list (theta near 0: the direct sum in disguise) stays inside the 2e-5 contract.  The
   // as-written arithmetic keeps the reference's one chain.
   constexpr bool TWO = FAST && sizeof(T) == 4;

@@ -1,10 +1,13 @@
-// Barnes-Hut walk in three parallel passes (walk_split.hip), f32, bit-identical to the fused walk.  Internal.
+// The Barnes-Hut walk for trees with big leaves (the BVH), f32 and f64: the one-pass walk — its preparation (walk_prepare.hip),
+// its kernels (walk_tile.hip, walk_tile_fast.hip) and its launch (walk_launch.hip, walk_route.h) — and the laboratory's three-pass
+// walk (walk_lab.hip).  Internal.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
 #include "tree_kernels.h"
+#include "walk_route.h"
 
 namespace nbody {
 
@@ -23,15 +26,6 @@ constexpr int64_t kWalkFusedScanMaxTargets = (int64_t)1 << 24;  // TileTail::fus
 // overflow flag is set: the caller grows the buffer (or uses the fused walk) and calls again.
 hipError_t launch_tree_walk_split(hipStream_t s, const WalkArgs<float>& a, char* scratch, const WalkSplitLayout& L, void* terms,
                                   int64_t term_capacity);
-
-// Which instantiation launch_tree_walk_tile_main launched (the NBODY_TRACE route line): the arm ("exact": walk_tile<T, false>,
-// "fast-registers": walk_tile_fast, "fast-rows": walk_tile<T, true>; laboratory only: "fast-bfs", "fast-registers-log"), and
-// the template parameters that arm has: the LDS tile's rows and whether node records come by scalar loads (exact, fast-rows),
-// the node-record mode (fast-registers).  -1: that arm has no such parameter.
-struct TileRoute {
-  const char* arm = "none";
-  int rows = -1, srec = -1, rec_mode = -1;
-};
 
 // The same walk in one pass, the terms handed from "lane = particle" to "lane = target" through LDS (walk_tile): no term
 // array.  The waves are cut by an estimate of each target's work.  estimate 1: hist[tgt_ids[t]] holds the term count of

@@ -45,3 +45,19 @@ def expected_bvh_route(n, leaf, mode, lab, fast=False):
     if mode == 2 or (mode == 4 and n >= TILE_MIN_TARGETS):
         return THREE_PASS
     return FUSED
+
+
+def expected_tile_kernel(f64, fast, rows=8, srec=1, fast_rows=-1, rec_mode=3, wave_log=0, bfs=0):
+    """choose_tile_route's rule (csrc/walk_route.h) for the one-pass walk's kernel, as kernels() reports it: (arm, rows, srec,
+    rec_mode).  The defaults are the product's knobs; the laboratory library reads NBODY_WALK_TILE_TARGETS, _SCALAR_REC,
+    _FAST_ROWS, _FAST_REC, _WAVE_LOG and _FAST_BFS into them.  Exact walks take the LDS rows; FAST takes them in f64 or where
+    fast_rows says so, else the registers (breadth first: f32 only, never with the log; the log has one kernel, record mode 0)."""
+    rows = rows if rows in (4, 16) else 8
+    through_rows = bool(fast_rows) if fast_rows >= 0 else bool(f64)
+    if not fast or through_rows:
+        return ("fast-rows" if fast else "exact", rows, 1 if srec else 0, -1)
+    if wave_log:
+        return ("fast-registers-log", -1, -1, 0)
+    if bfs and not f64:
+        return ("fast-bfs", -1, -1, -1)
+    return ("fast-registers", -1, -1, rec_mode if rec_mode in (1, 3) else 0)

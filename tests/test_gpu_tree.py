@@ -407,7 +407,7 @@ def test_device_bvh_build_with_long_nodes_left_after_the_blind_levels(nb, orc, l
         assert np.array_equal(t["order"], o.ids), name
 
 
-# ------------------------------------------------------------------ split walk (walk_split.hip)
+# ------------------------------------------------------------------ split walk (walk_tile.hip, walk_tile_fast.hip, walk_lab.hip)
 @pytest.mark.parametrize("mode", ["0", "2", "3", "1"])
 def test_split_and_fused_walks_are_the_same_walk(nb, orc, lab_ctx, monkeypatch, capfd, mode):
     """count / emit / ordered-sum (NBODY_WALK_SPLIT=2), the one-pass walk with the terms through LDS (=3, and =1: chosen by
@@ -876,6 +876,65 @@ def test_node_record_fetch_variants_walk_the_same_walk(nb, orc, lab, monkeypatch
             acc = c.accel_tree(C.TREE_BVH)                     # the bodies themselves, in tree order
         assert routes.kernels(capfd.readouterr().err) == {kernel}
         check_fast(acc, ref64, norm, label=f" FAST rows={rows}")
+
+
+def _two_bvh_steps(nb, capfd, dtype, arith):
+    """4 097 Plummer bodies (the smallest count that takes the one-pass walk by itself and leaves a partial last wave), leaves of
+    16, two BVH steps: what download() gives, and the kernels the trace names.  theta 8: about 160 terms per target (the oracle's
+    count), so many leaves are wanted by a few lanes of a wave only and their terms go through the LDS rows in batches — and
+    fewer than the n / 16 = 256 per target from which the driver takes the fused walk for the steps that follow."""
+    C = nb._capi
+    pos, vel, w = nb.scenes.plummer(4097, seed=67)
+    capfd.readouterr()
+    with C.Context(0) as c:
+        c.set_params(theta=8.0, leaf_size=16, arith=arith, order=C.ORDER_AS_WRITTEN)
+        c.upload(pos.astype(dtype), vel.astype(dtype), w)
+        c.update_tree(C.TREE_BVH, 0.1, 2)
+        got = c.download()
+    err = capfd.readouterr().err
+    assert routes.routes(err) == {routes.TILE} and len(routes.parse(err)) >= 2, err[-600:]
+    return got, routes.kernels(err)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_product_library_ignores_the_laboratory_switches_of_the_walk(nb, monkeypatch, capfd, dtype):
+    """The product and the laboratory library choose the one-pass walk's kernel by the same code (walk_launch.hip); the product
+    reads its knobs as their defaults.  So with every kernel switch set to something the laboratory would honour, the product
+    library launches the same four kernels as with nothing set, and the same bits come back."""
+    C = nb._capi
+    f64 = dtype == np.float64
+    monkeypatch.setenv("NBODY_TRACE", "1")
+    for arith in (C.ARITH_AUTO, C.ARITH_FAST):
+        want = {routes.expected_tile_kernel(f64, arith == C.ARITH_FAST)}
+        assert want == {{(False, False): ("exact", 8, 1, -1), (False, True): ("fast-registers", -1, -1, 3),
+                         (True, False): ("exact", 8, 1, -1), (True, True): ("fast-rows", 8, 1, -1)}[(f64, arith == C.ARITH_FAST)]}
+        for name in ("NBODY_WALK_SCALAR_REC", "NBODY_WALK_FAST_REC", "NBODY_WALK_FAST_ROWS", "NBODY_WALK_TILE_TARGETS"):
+            monkeypatch.delenv(name, raising=False)
+        plain, ran = _two_bvh_steps(nb, capfd, dtype, arith)
+        assert ran == want, ran
+        monkeypatch.setenv("NBODY_WALK_SCALAR_REC", "0")
+        monkeypatch.setenv("NBODY_WALK_FAST_REC", "1")
+        monkeypatch.setenv("NBODY_WALK_FAST_ROWS", "0" if f64 else "1")
+        monkeypatch.setenv("NBODY_WALK_TILE_TARGETS", "16")
+        switched, ran = _two_bvh_steps(nb, capfd, dtype, arith)
+        assert ran == want, ran
+        assert all(np.array_equal(x, y) for x, y in zip(plain, switched))
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_tile_rows_4_8_16_dispatch_and_walk_the_same_walk(nb, lab, monkeypatch, capfd, dtype):
+    """NBODY_WALK_TILE_TARGETS (laboratory): 4, 8 or 16 rows of the LDS tile.  A row holds one acting target's terms, a target adds
+    its own row in slice order: the row count changes the batches, not one addition — equal bits, so the trace must name the
+    three kernels."""
+    monkeypatch.setenv("NBODY_TRACE", "1")
+    got = []
+    for rows in (4, 8, 16):
+        monkeypatch.setenv("NBODY_WALK_TILE_TARGETS", str(rows))
+        here, ran = _two_bvh_steps(nb, capfd, dtype, lab.ARITH_AUTO)
+        assert ran == {("exact", rows, 1, -1)} == {routes.expected_tile_kernel(dtype == np.float64, False, rows=rows)}, ran
+        got.append(here)
+    for other in got[1:]:
+        assert all(np.array_equal(x, y) for x, y in zip(got[0], other))
 
 
 def test_f64_walks_take_theta_as_the_f32_parameter_it_is(nb, orc, ctx):

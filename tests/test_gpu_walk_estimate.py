@@ -11,7 +11,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 U32, U64 = np.uint32, np.uint64
 LIMIT = 2 ** 31 - 1            # the largest total the budget arithmetic takes (31 bits)
-K_TILE_BUDGET = 8192           # walk_split.hip, kTileBudget
+K_TILE_BUDGET = 8192           # walk_device.h, kTileBudget
 ROUTES = (0, 1, 2)
 ACCEPT = dict(nodes=5, node_count=7, fallback=0, bad_index=0, long_nodes=0, level_end=3, node_cap=10)
 

@@ -45,6 +45,13 @@ def test_exact_sum_scan_asan_ubsan(tmp_path):
                    src=os.path.join(ROOT, "tests", "native", "exact_sum_check.cpp"))
 
 
+def test_tile_route_chooser_asan_ubsan(tmp_path):
+    """csrc/walk_route.h: choose_tile_route over every combination of precision, arithmetic and laboratory knobs against a table,
+    the product's four routes from the default knobs, and a product build's knobs with every switch set in the environment."""
+    _build_and_run(tmp_path, ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"],
+                   src=os.path.join(ROOT, "tests", "native", "tile_route_check.cpp"))
+
+
 def test_multi_device_barrier_and_pool_tsan(tmp_path):
     """csrc/multi_sync.hpp (the barrier in front of every collective, the one-worker-per-device pool) under TSan: votes,
     a rank failing before a barrier, and a rank failing right after the final barrier while the others still wake from it

@@ -29,3 +29,15 @@ def test_the_rule_of_the_walk_phase_restated():
     assert r(500, 16, 2, lab=True) == routes.THREE_PASS and r(500, 16, 2, lab=False) == routes.FUSED   # the product reads 2 as 1
     assert r(5000, 16, 2, lab=False) == routes.TILE and r(500, 7, 2, lab=True) == routes.SMALL
     assert r(500, 64, 0, lab=True) == routes.FUSED and r(10 ** 6, 64, 0, lab=False) == routes.FUSED
+
+
+def test_the_rule_of_the_tile_kernel_restated():
+    """Against the tuples test_node_record_fetch_variants_walk_the_same_walk (tests/test_gpu_tree.py) asserts from the trace."""
+    k = routes.expected_tile_kernel
+    for srec, frec in ((1, 0), (0, 1), (1, 3)):
+        assert k(False, True, srec=srec, rec_mode=frec) == ("fast-registers", -1, -1, frec)
+        assert k(False, False, srec=srec, rec_mode=frec) == ("exact", 8, srec, -1)
+    assert k(False, True, fast_rows=0) == ("fast-registers", -1, -1, 3) and k(False, True, fast_rows=1) == ("fast-rows", 8, 1, -1)
+    # the product's four: nothing set
+    assert k(False, False) == k(True, False) == ("exact", 8, 1, -1)
+    assert k(False, True) == ("fast-registers", -1, -1, 3) and k(True, True) == ("fast-rows", 8, 1, -1)

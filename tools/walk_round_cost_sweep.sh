@@ -4,7 +4,7 @@ cd nbody-simulation_amd/csrc
 export NBODY_HIP_LIBRARY=lab
 BASE="-O3 -std=c++17 -fPIC -ffp-contract=off -fvisibility=hidden"
 for cfg in "" "-DNB_TILE_ROUND_COST=40 -DNB_FAST_ROUND_COST=12" "-DNB_TILE_ROUND_COST=52 -DNB_FAST_ROUND_COST=16" "-DNB_TILE_ROUND_COST=85 -DNB_FAST_ROUND_COST=24" "-DNB_TILE_ROUND_COST=110 -DNB_FAST_ROUND_COST=32"; do
-  rm -f walk_split.lab.o
+  rm -f walk_tile.lab.o walk_tile_fast.lab.o walk_lab.lab.o  # the units that read the two constants (walk_device.h)
   make lab CXXFLAGS="$BASE $cfg" > /dev/null 2>&1 || { echo "build failed: $cfg"; continue; }
   for leg in reference_scene_bvh plummer1m_bvh; do
   (cd ../.. && timeout -k 10 150 python bench.py --leg $leg --no-cpu-baseline > gpurun_out/r04_rc.json 2> gpurun_out/r04_rc.err && python -c "

@@ -1,6 +1,6 @@
 """Round 4: how many waves should the one-pass BVH walk aim at?  Whole World::update steps (BVH, theta 50, AS_WRITTEN) on the
 reference scene and on Plummer spheres of three sizes, for several NBODY_WALK_TILE_WAVES (laboratory library) and the product's
-size-aware default (tile_waves_target, csrc/walk_split.hip).  python tools/walk_wave_target.py"""
+size-aware default (tile_waves_target, csrc/walk_prepare.hip).  python tools/walk_wave_target.py"""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
