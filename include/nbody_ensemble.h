@@ -114,8 +114,8 @@ int nbody_ensemble64_accel(nbody_ensemble64* e, double* acc_xy);                
  *     its (contiguous) blocks in that launch, the number of launches, and per launch (arrays of NBODY_RAGGED_MAX_LAUNCHES, zero
  *     past n_launches) the dynamic LDS and the number of blocks.  It is pure host code: no device, no handle, every output
  *     pointer may be NULL; sizes outside the limits give NBODY_ERR_INVALID and nothing is written.
- *   Not offered on this handle: f64 ragged ensembles, a per-world delta or clamp, tracers, tree methods, several devices, and
- *     what the ensemble above does not offer either. */
+ *   Not offered on this handle: f64 (nbody_ragged64_* below is the double-precision sibling), a per-world delta or clamp,
+ *     tracers, tree methods, several devices, and what the ensemble above does not offer either. */
 #define NBODY_RAGGED_MAX_LAUNCHES 6
 typedef struct nbody_ragged nbody_ragged;
 int nbody_ragged_create(nbody_ragged** out, int device_id);
@@ -133,5 +133,43 @@ int nbody_ragged_update_f32(nbody_ragged* e, float delta, int n_steps, nbody_cou
 int nbody_ragged_accel_f32(nbody_ragged* e, float* acc_xy);                       /* force only, state untouched */
 int nbody_ragged_plan(int64_t n_worlds, const int64_t* n_bodies, int32_t* launch_of_world, int64_t* first_block_of_world,
                       int32_t* n_launches, int32_t* lds_bytes_of_launch, int64_t* blocks_of_launch);
+
+/* ---- ragged ensembles in f64: double-precision worlds of different sizes, a handle of its own ---------------------
+ * The ragged ensemble above in double precision: arrays, limits, launches (the same six classes, at most
+ * NBODY_RAGGED_MAX_LAUNCHES per step), independence, booking, params, trivial calls and errors as stated there, with the message
+ * naming "ragged"; no CPU path (nbody_ragged64_create fails with NBODY_ERR_NO_DEVICE without a gfx950 device); NULL handle
+ * (NBODY_ERR_INVALID; 0 from nbody_ragged64_num_worlds / _num_rows; nbody_ragged64_last_error(NULL): the last failed
+ * nbody_ragged64_create or nbody_ragged64_plan on this thread — a slot of its own, apart from nbody_ragged_*'s and
+ * nbody_ensemble64_*'s).  The arithmetic is nbody_ensemble64_*'s, word for word:
+ *   Step.  Every world takes the step of nbody_update_direct_f64: the pair of main.rs:234-253 in T = double (two correctly
+ *     rounded divisions, no contraction, the is_normal skip), mass `weight as f64`, the clamp params.clamp widened to double,
+ *     then main.rs:419-423, multiply then add.
+ *   EXACT and AUTO.  One ascending-j chain of IEEE additions per target: every world is bit-identical to the CPU restatement's
+ *     update_direct of that world alone on float64 arrays.  AUTO is EXACT, as it is for an f64 context.
+ *   FAST (opt-in).  |a - a_ref|_1 <= 1e-12 * sum_j |term_ij|_1 per body: v_rcp_f64 plus one Newton step, fused
+ *     multiply-adds, the 2^-700 biased denominator.  Gated per world, per step, on the device: a world with a position outside
+ *     the f64 FAST domain (non-finite, >= 2^100 in magnitude, or non-zero below 2^-300) at the start of a step takes EXACT for
+ *     that step; with a clamp that is not > 0, or NaN, every world takes EXACT.  Every world is bit-identical to
+ *     nbody_ensemble64_* holding that world alone (the two kernels share one body; FAST's order of additions is a fixed
+ *     function of the world's n_bodies).
+ *   Launches.  Per launch the dynamic LDS is that of its largest member at 20 bytes a body, rows padded to a multiple of 8:
+ *     at most 2 560, 5 120, 10 240, 20 480, 40 960 and 81 920 B for the six classes (the kernel uses no other LDS).
+ *     nbody_ragged64_plan is nbody_ragged_plan under these sizes. */
+typedef struct nbody_ragged64 nbody_ragged64;
+int nbody_ragged64_create(nbody_ragged64** out, int device_id);
+void nbody_ragged64_destroy(nbody_ragged64* e);
+const char* nbody_ragged64_last_error(const nbody_ragged64* e);
+int nbody_ragged64_set_params(nbody_ragged64* e, const nbody_params* p);
+int nbody_ragged64_get_params(const nbody_ragged64* e, nbody_params* out);
+int nbody_ragged64_upload(nbody_ragged64* e, int64_t n_worlds, const int64_t* n_bodies /*[n_worlds]*/, const double* pos_xy,
+                          const double* vel_xy, const uint32_t* weight);
+int nbody_ragged64_download(nbody_ragged64* e, double* pos_xy, double* vel_xy);   /* either may be NULL */
+int64_t nbody_ragged64_num_worlds(const nbody_ragged64* e);
+int64_t nbody_ragged64_num_rows(const nbody_ragged64* e);                         /* the sum of the sizes */
+int nbody_ragged64_sizes(const nbody_ragged64* e, int64_t* n_bodies_out /*[num_worlds]*/);
+int nbody_ragged64_update(nbody_ragged64* e, double delta, int n_steps, nbody_counting* counter);
+int nbody_ragged64_accel(nbody_ragged64* e, double* acc_xy);                      /* force only, state untouched */
+int nbody_ragged64_plan(int64_t n_worlds, const int64_t* n_bodies, int32_t* launch_of_world, int64_t* first_block_of_world,
+                        int32_t* n_launches, int32_t* lds_bytes_of_launch, int64_t* blocks_of_launch);
 
 #endif /* NBODY_ENSEMBLE_H */

@@ -123,6 +123,19 @@ _SIGS = {
     "nbody_ragged_update_f32": (C.c_int, [_vp, _f32, _i32, C.POINTER(Counting)]),
     "nbody_ragged_accel_f32": (C.c_int, [_vp, _vp]),
     "nbody_ragged_plan": (C.c_int, [_i64, _vp, _vp, _vp, C.POINTER(_i32), _vp, _vp]),
+    "nbody_ragged64_create": (C.c_int, [C.POINTER(_vp), _i32]),
+    "nbody_ragged64_destroy": (None, [_vp]),
+    "nbody_ragged64_last_error": (C.c_char_p, [_vp]),
+    "nbody_ragged64_set_params": (C.c_int, [_vp, C.POINTER(Params)]),
+    "nbody_ragged64_get_params": (C.c_int, [_vp, C.POINTER(Params)]),
+    "nbody_ragged64_upload": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "nbody_ragged64_download": (C.c_int, [_vp, _vp, _vp]),
+    "nbody_ragged64_num_worlds": (_i64, [_vp]),
+    "nbody_ragged64_num_rows": (_i64, [_vp]),
+    "nbody_ragged64_sizes": (C.c_int, [_vp, _vp]),
+    "nbody_ragged64_update": (C.c_int, [_vp, _f64, _i32, C.POINTER(Counting)]),
+    "nbody_ragged64_accel": (C.c_int, [_vp, _vp]),
+    "nbody_ragged64_plan": (C.c_int, [_i64, _vp, _vp, _vp, C.POINTER(_i32), _vp, _vp]),
     "nbody_accel_tree_f32": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_accel_tree_f64": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_tree_info": (C.c_int, [_vp, C.POINTER(TreeView)]),
@@ -921,21 +934,28 @@ class RaggedHandle(_EnsembleHandleBase):
         return acc
 
 
+class Ragged64Handle(RaggedHandle):
+    """nbody_ragged64_*: float64 worlds of different sizes, the sibling of RaggedHandle."""
+    _prefix, _suffix, _dtype = "nbody_ragged64", "", np.float64
+
+
 RAGGED_MAX_LAUNCHES = 6
 
 
-def ragged_plan(sizes):
-    """nbody_ragged_plan of these sizes (pure host code) -> (launch_of_world int32[worlds], first_block_of_world int64[worlds],
-    lds_bytes int32[launches], blocks int64[launches]); NBodyError(ERR_INVALID) for sizes outside the limits."""
+def ragged_plan(sizes, f64=False):
+    """nbody_ragged_plan (f64: nbody_ragged64_plan) of these sizes (pure host code) -> (launch_of_world int32[worlds],
+    first_block_of_world int64[worlds], lds_bytes int32[launches], blocks int64[launches]); NBodyError(ERR_INVALID) for sizes
+    outside the limits."""
     lib = load()
+    prefix = "nbody_ragged64" if f64 else "nbody_ragged"
     sizes = np.ascontiguousarray(sizes, dtype=np.int64)
     b = int(sizes.shape[0])
     launch, first = np.zeros(b, np.int32), np.zeros(b, np.int64)
     lds, blocks = np.zeros(RAGGED_MAX_LAUNCHES, np.int32), np.zeros(RAGGED_MAX_LAUNCHES, np.int64)
     n = _i32(0)
-    rc = lib.nbody_ragged_plan(b, _ptr(sizes), _ptr(launch), _ptr(first), C.byref(n), _ptr(lds), _ptr(blocks))
+    rc = getattr(lib, prefix + "_plan")(b, _ptr(sizes), _ptr(launch), _ptr(first), C.byref(n), _ptr(lds), _ptr(blocks))
     if rc != OK:
-        msg = lib.nbody_ragged_last_error(None)
+        msg = getattr(lib, prefix + "_last_error")(None)
         raise NBodyError(rc, msg.decode() if msg else "")
     return launch, first, lds[:n.value].copy(), blocks[:n.value].copy()
 

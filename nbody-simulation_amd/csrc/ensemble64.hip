@@ -1,30 +1,9 @@
 // libnbody_hip — ensembles in f64: the C entry points of nbody_ensemble64_* (include/nbody_ensemble.h) over the driver of
-// ensemble_driver.h, and what is f64 about them: the masses kept as the caller's u32 weights (the kernel converts on use,
-// `weight as f64` is exact), the opt-in FAST rule of the f64 direct step, the kernel of ensemble64_kernels.hip.
-#include "ensemble64_kernels.h"
-#include "ensemble_driver.h"
+// ensemble_driver.h in the precision of ensemble_f64.h.
+#include "ensemble_f64.h"
 
 using namespace nbody;
 
-struct EnsF64 {
-  using Real = double;
-  using Vec2 = double2;
-  using Mass = uint32_t;
-  using Args = Ensemble64Args;
-  static constexpr const char* kCreate = "nbody_ensemble64_create";
-  static constexpr const char* kWho = "ensemble";
-  static const uint32_t* stage(const uint32_t* weight, size_t rows, std::vector<uint32_t>& tmp) {
-    if (weight) return weight;  // uploaded from where they are
-    tmp.assign(rows, 1u);
-    return tmp.data();
-  }
-  static void route(Ensemble64Args& a, const uint32_t* weight, const nbody_params& p) {
-    a.weight = weight;
-    a.clamp = (double)p.clamp;  // the f32 parameter widened, as the f64 context's direct step does
-    a.fast = direct_fast_f64(p.arith, a.clamp) ? 1 : 0;  // opt-in, and a clamp that is not > 0 (or NaN): every world EXACT
-  }
-  static hipError_t launch(hipStream_t s, int64_t n_worlds, const Ensemble64Args& a) { return launch_ensemble64_step(s, n_worlds, a); }
-};
 struct nbody_ensemble64 : EnsembleState<EnsF64> {};
 
 NB_API int nbody_ensemble64_create(nbody_ensemble64** out, int device_id) { return ens_create(out, device_id); }

@@ -1,4 +1,5 @@
-// Ensembles in f64 (nbody_ensemble64_*): many small double-precision worlds of equal size stepped by ONE launch per step.
+// Ensembles in f64 (nbody_ensemble64_*): many small double-precision worlds of equal size stepped by ONE launch per step;
+// worlds of different sizes (nbody_ragged64_*) run the same block body from a table of work items: at the end.
 // Internal.  The launch shape is that of ensemble_kernels.h — worlds x target tiles, every block stages its world's sources
 // whole in LDS and takes FAST's per-world decision while it loads them — with these differences:
 //   LDS      double2 positions and the u32 WEIGHTS (converted on use: `weight as f64` is exact, so the bits are those of a
@@ -20,8 +21,6 @@
 
 namespace nbody {
 
-constexpr int kEns64TermBlock = 8;  // EXACT: pairs evaluated together before their terms are added in ascending j
-
 struct Ensemble64Args {
   const double2* pos_in = nullptr;   // [n_worlds][n_bodies], read by every block of the world
   const uint32_t* weight = nullptr;  // the mass is `weight as f64`
@@ -34,11 +33,18 @@ struct Ensemble64Args {
   int fast = 0;                      // FAST where the world's positions allow it; 0: every world EXACT
 };
 
-inline int ensemble64_padded(int n_bodies) { return (n_bodies + kEns64TermBlock - 1) / kEns64TermBlock * kEns64TermBlock; }
-inline size_t ensemble64_lds_bytes(int n_bodies) { return (size_t)ensemble64_padded(n_bodies) * (sizeof(double2) + sizeof(uint32_t)); }
+// kEns64TermBlock, ensemble64_padded and ensemble64_lds_bytes come from ensemble_shape.h (plain C++: the ragged plan uses them).
+static_assert(sizeof(double2) + sizeof(uint32_t) == 2 * sizeof(double) + sizeof(uint32_t), "a staged body is a double2 and a u32");
 
 // One step (or, without vel / pos_out, one force evaluation) of all n_worlds worlds on `s`.  The limits are the f32 ensemble's
 // (kEnsembleMaxBodies, kEnsembleMaxRows); a launch that cannot be made comes back as an error, never as an unlaunched step.
 hipError_t launch_ensemble64_step(hipStream_t s, int64_t n_worlds, Ensemble64Args a);
+
+// Ragged ensembles in f64 (nbody_ragged64_*): worlds of different sizes.  A block is one work item (world, tile) of the table
+// that ragged_plan.h lays out, {row0, n | tile << 16}, as in launch_ensemble_step_ragged.  One launch of the plan: `blocks` items
+// from `items`, `lds_bytes` = ensemble64_lds_bytes of the largest world among them (above 64 KB the ragged kernel's own
+// dynamic-LDS limit is raised, once per device); n_bodies and tiles of `a` are not read.  Every world computes exactly what
+// launch_ensemble64_step computes for a world of its size.
+hipError_t launch_ensemble64_step_ragged(hipStream_t s, int64_t blocks, size_t lds_bytes, const uint2* items, Ensemble64Args a);
 
 }  // namespace nbody

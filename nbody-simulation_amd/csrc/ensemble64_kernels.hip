@@ -47,18 +47,17 @@ namespace {
 
 constexpr int kEns64Run = 64;  // sources of one lane summed on their own before they join its total
 
+// What a block computes: one tile of the targets of the world whose rows are row0 .. row0 + n — its sources staged in LDS with
+// FAST's decision taken on the way, then the EXACT or the FAST arm.  A function of the world through (n, row0, tile) alone: the
+// uniform kernel and the ragged one share it, and with it every bit.  Every thread of the block calls it (it holds barriers).
 template <int SPLIT>
-__global__ __launch_bounds__(kEnsembleBlock) void ensemble64_step(const Ensemble64Args a) {
+__device__ __forceinline__ void ens64_world_tile(const Ensemble64Args& a, const int n, const size_t row0, const unsigned tile) {
   constexpr int TPB = kEnsembleBlock / SPLIT;  // targets per block
   constexpr int TB = kEns64TermBlock;
   extern __shared__ __attribute__((aligned(16))) unsigned char ens64_lds[];
-  const int n = a.n_bodies;
   const int npad = (n + TB - 1) / TB * TB;
   double2* const spos = reinterpret_cast<double2*>(ens64_lds);
   uint32_t* const sw = reinterpret_cast<uint32_t*>(spos + npad);
-
-  const unsigned world = blockIdx.x / a.tiles, tile = blockIdx.x - world * a.tiles;
-  const size_t row0 = (size_t)world * (size_t)n;
 
   // ---- the world's sources into LDS, and FAST's decision on the way
   int bad = 0;
@@ -148,15 +147,41 @@ __global__ __launch_bounds__(kEnsembleBlock) void ensemble64_step(const Ensemble
   if (live && part == 0) ens_integrate(a, row0 + t, p.x, p.y, ax, ay);
 }
 
-// Dynamic LDS above 64 KB (n > 3272: rows are padded to 8 and 3280 x 20 B = 65 600; the one-target-per-lane layout only) needs the function's limit raised: once per device.
-hipError_t ens64_raise_lds_limit() {
-  static std::atomic<bool> raised[64];  // (zero-initialised: false)
+template <int SPLIT>
+__global__ __launch_bounds__(kEnsembleBlock) void ensemble64_step(const Ensemble64Args a) {
+  const int n = a.n_bodies;
+  const unsigned world = blockIdx.x / a.tiles, tile = blockIdx.x - world * a.tiles;
+  ens64_world_tile<SPLIT>(a, n, (size_t)world * (size_t)n, tile);
+}
+
+// Ragged: the block's work item {row0, n | tile << 16} is the same in every lane (its address is a function of blockIdx.x
+// alone, and readfirstlane says so to the compiler), so the switch on the world's lane split is taken by the whole block — the
+// barriers of the staging and the butterfly of FAST see every thread.  No static LDS here either.
+__global__ __launch_bounds__(kEnsembleBlock) void ensemble64_step_ragged(const Ensemble64Args a, const uint2* __restrict__ items) {
+  const uint2 item = items[blockIdx.x];
+  const size_t row0 = (size_t)(unsigned)__builtin_amdgcn_readfirstlane(item.x);
+  const unsigned packed = __builtin_amdgcn_readfirstlane(item.y);
+  const int n = (int)(packed & 0xffffu);
+  const unsigned tile = packed >> 16;
+  switch (ensemble_split(n)) {
+    case 1: ens64_world_tile<1>(a, n, row0, tile); break;
+    case 2: ens64_world_tile<2>(a, n, row0, tile); break;
+    case 4: ens64_world_tile<4>(a, n, row0, tile); break;
+    case 8: ens64_world_tile<8>(a, n, row0, tile); break;
+    case 16: ens64_world_tile<16>(a, n, row0, tile); break;
+    case 32: ens64_world_tile<32>(a, n, row0, tile); break;
+    default: ens64_world_tile<64>(a, n, row0, tile); break;
+  }
+}
+
+// Dynamic LDS above 64 KB (n > 3272: rows are padded to 8 and 3280 x 20 B = 65 600; the one-target-per-lane layout only) needs
+// the function's limit raised: once per device and per function (`raised` is that function's own table, zero-initialised).
+hipError_t ens64_raise_lds_limit(const void* kernel, std::atomic<bool>* raised) {
   int dev = 0;
   hipError_t h = hipGetDevice(&dev);
   if (h != hipSuccess) return h;
   if (dev >= 0 && dev < 64 && raised[dev]) return hipSuccess;
-  h = hipFuncSetAttribute(reinterpret_cast<const void*>(&ensemble64_step<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)ensemble64_lds_bytes(kEnsembleMaxBodies));
+  h = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ensemble64_lds_bytes(kEnsembleMaxBodies));
   if (h == hipSuccess && dev >= 0 && dev < 64) raised[dev] = true;
   return h;
 }
@@ -171,7 +196,8 @@ hipError_t launch_ensemble64_step(hipStream_t s, int64_t n_worlds, Ensemble64Arg
   const dim3 grid((unsigned)(n_worlds * a.tiles));  // <= 2^26 blocks
   const size_t lds = ensemble64_lds_bytes(a.n_bodies);
   if (lds > 65536) {
-    const hipError_t h = ens64_raise_lds_limit();
+    static std::atomic<bool> raised[64];
+    const hipError_t h = ens64_raise_lds_limit(reinterpret_cast<const void*>(&ensemble64_step<1>), raised);
     if (h != hipSuccess) return h;
   }
 #define NB_ENS64_GO(S) hipLaunchKernelGGL(ensemble64_step<S>, grid, dim3(kEnsembleBlock), lds, s, a)
@@ -185,6 +211,17 @@ hipError_t launch_ensemble64_step(hipStream_t s, int64_t n_worlds, Ensemble64Arg
     default: NB_ENS64_GO(64); break;
   }
 #undef NB_ENS64_GO
+  return hipGetLastError();
+}
+
+hipError_t launch_ensemble64_step_ragged(hipStream_t s, int64_t blocks, size_t lds_bytes, const uint2* items, Ensemble64Args a) {
+  if (blocks < 1 || blocks > kEnsembleMaxRows || !items || lds_bytes > ensemble64_lds_bytes(kEnsembleMaxBodies)) return hipErrorInvalidValue;
+  if (lds_bytes > 65536) {  // its own function, so its own limit: the uniform kernel's raised one does not cover it
+    static std::atomic<bool> raised[64];
+    const hipError_t h = ens64_raise_lds_limit(reinterpret_cast<const void*>(&ensemble64_step_ragged), raised);
+    if (h != hipSuccess) return h;
+  }
+  hipLaunchKernelGGL(ensemble64_step_ragged, dim3((unsigned)blocks), dim3(kEnsembleBlock), lds_bytes, s, a, items);
   return hipGetLastError();
 }
 

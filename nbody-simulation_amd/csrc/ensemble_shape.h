@@ -1,5 +1,5 @@
-// Ensembles: the limits and the two functions of a world's size that decide its launch — how many lanes share a target and
-// how much LDS its sources take.  Internal.  Plain C++ (no HIP include), so that the host-only plan of ragged_plan.h and a
+// Ensembles: the limits and the functions of a world's size that decide its launch — how many lanes share a target and
+// how much LDS its sources take, in f32 and in f64.  Internal.  Plain C++ (no HIP include), so that the host-only plan of ragged_plan.h and a
 // stand-alone host program can use them; the kernels see the same definitions through ensemble_kernels.h.
 #pragma once
 #include <stddef.h>
@@ -25,5 +25,10 @@ NB_ENS_HD inline int ensemble_split(int n_bodies) {
   return split;
 }
 inline size_t ensemble_lds_bytes(int n_bodies) { return (size_t)((n_bodies + 1) / 2) * 24; }  // couples {xA, xB, yA, yB} + {mA, mB}
+
+// In f64 (ensemble64_kernels.h): rows padded to a multiple of the EXACT term block, a double2 position and a u32 weight each.
+constexpr int kEns64TermBlock = 8;  // EXACT: pairs evaluated together before their terms are added in ascending j
+inline int ensemble64_padded(int n_bodies) { return (n_bodies + kEns64TermBlock - 1) / kEns64TermBlock * kEns64TermBlock; }
+inline size_t ensemble64_lds_bytes(int n_bodies) { return (size_t)ensemble64_padded(n_bodies) * (2 * sizeof(double) + sizeof(uint32_t)); }
 
 }  // namespace nbody

@@ -14,6 +14,7 @@ struct RagF32 : EnsF32 {
   static hipError_t launch_items(hipStream_t s, int64_t blocks, size_t lds_bytes, const uint2* items, const EnsembleArgs& a) {
     return launch_ensemble_step_ragged(s, blocks, lds_bytes, items, a);
   }
+  static size_t lds_bytes(int n_bodies) { return ensemble_lds_bytes(n_bodies); }
 };
 struct nbody_ragged : RaggedState<RagF32> {};
 
@@ -29,11 +30,7 @@ NB_API int nbody_ragged_upload_f32(nbody_ragged* e, int64_t n_worlds, const int6
 NB_API int nbody_ragged_download_f32(nbody_ragged* e, float* pos, float* vel) { return ens_download<RagF32>(e, pos, vel); }
 NB_API int64_t nbody_ragged_num_worlds(const nbody_ragged* e) { return e ? e->n_worlds : 0; }
 NB_API int64_t nbody_ragged_num_rows(const nbody_ragged* e) { return e ? e->rows : 0; }
-NB_API int nbody_ragged_sizes(const nbody_ragged* e, int64_t* n_bodies_out) {
-  if (!e || !n_bodies_out) return NBODY_ERR_INVALID;
-  for (int64_t k = 0; k < e->n_worlds; ++k) n_bodies_out[k] = e->sizes[(size_t)k];
-  return NBODY_OK;
-}
+NB_API int nbody_ragged_sizes(const nbody_ragged* e, int64_t* n_bodies_out) { return ragged_sizes<RagF32>(e, n_bodies_out); }
 NB_API int nbody_ragged_update_f32(nbody_ragged* e, float delta, int n_steps, nbody_counting* counter) {
   return ragged_update<RagF32>(e, delta, n_steps, counter);
 }
@@ -41,13 +38,6 @@ NB_API int nbody_ragged_accel_f32(nbody_ragged* e, float* acc_xy) { return ragge
 
 NB_API int nbody_ragged_plan(int64_t n_worlds, const int64_t* n_bodies, int32_t* launch_of_world, int64_t* first_block_of_world,
                              int32_t* n_launches, int32_t* lds_bytes_of_launch, int64_t* blocks_of_launch) {
-  RaggedPlan plan;
-  if (const int rc = ragged_plan(n_worlds, n_bodies, &plan, launch_of_world, first_block_of_world))
-    return ens_fail<RagF32>(nullptr, NBODY_ERR_INVALID, ragged_plan_error(rc));  // (read with nbody_ragged_last_error(NULL))
-  if (n_launches) *n_launches = plan.n_launches;
-  for (int l = 0; l < kRaggedMaxLaunches; ++l) {
-    if (lds_bytes_of_launch) lds_bytes_of_launch[l] = plan.lds_bytes[l];
-    if (blocks_of_launch) blocks_of_launch[l] = plan.blocks[l];
-  }
-  return NBODY_OK;
+  // (a refusal is read with nbody_ragged_last_error(NULL))
+  return ragged_show_plan<RagF32>(n_worlds, n_bodies, launch_of_world, first_block_of_world, n_launches, lds_bytes_of_launch, blocks_of_launch);
 }

@@ -1,11 +1,12 @@
-// libnbody_hip — ragged ensembles: the host driver behind nbody_ragged_* (ragged.hip), written once over a precision P as
+// libnbody_hip — ragged ensembles: the host driver behind nbody_ragged_* (ragged.hip) and nbody_ragged64_* (ragged64.hip), written once over a precision P as
 // ensemble_driver.h is, and out of its parts: the state with its double-buffered positions, in-place velocities and lazily
 // allocated accelerations, create / destroy, params and errors are the ensemble's.  Internal.  What differs: the worlds have
 // sizes of their own, so an upload keeps the sizes, lays out the plan of ragged_plan.h and uploads its work-item table, and one
 // step is one launch per launch of that plan, back to back on the handle's stream, with one synchronise at the end of a call.
 //
 // P supplies what ensemble_driver.h asks for (kWho "ragged") and, in place of launch:
-//   launch_items(stream, blocks, lds_bytes, items, args)   one launch of the plan: `blocks` work items from `items`.
+//   launch_items(stream, blocks, lds_bytes, items, args)   one launch of the plan: `blocks` work items from `items`;
+//   lds_bytes(n_bodies)                                    the dynamic LDS of a world, which the plan sizes its launches by.
 #pragma once
 #include "ensemble_driver.h"
 #include "ragged_plan.h"
@@ -43,7 +44,7 @@ int ragged_upload(RaggedState<P>* e, int64_t n_worlds, const int64_t* n_bodies, 
                   const uint32_t* weight) {
   if (!e) return NBODY_ERR_INVALID;
   RaggedPlan plan;
-  if (const int rc = ragged_plan(n_worlds, n_bodies, &plan, nullptr, nullptr)) return ens_fail<P>(e, NBODY_ERR_INVALID, ragged_plan_error(rc));
+  if (const int rc = ragged_plan(n_worlds, n_bodies, &plan, nullptr, nullptr, P::lds_bytes)) return ens_fail<P>(e, NBODY_ERR_INVALID, ragged_plan_error(rc));
   if (!pos || !vel) return ens_fail<P>(e, NBODY_ERR_INVALID, "ragged upload: pos_xy or vel_xy is NULL");
   std::vector<RaggedItem> items((size_t)plan.total_blocks);
   int64_t first_item[kRaggedMaxLaunches];
@@ -70,6 +71,27 @@ template <class P> int ragged_update(RaggedState<P>* e, typename P::Real delta, 
 }
 template <class P> int ragged_accel(RaggedState<P>* e, typename P::Real* acc_xy) {
   return ens_accel_with<P>(e, acc_xy, [e](const typename P::Args& a) { return ragged_launch_all<P>(e, a); });
+}
+
+template <class P> int ragged_sizes(const RaggedState<P>* e, int64_t* n_bodies_out) {
+  if (!e || !n_bodies_out) return NBODY_ERR_INVALID;
+  for (int64_t k = 0; k < e->n_worlds; ++k) n_bodies_out[k] = e->sizes[(size_t)k];
+  return NBODY_OK;
+}
+
+// The plan as the ABI shows it (nbody_ragged_plan, nbody_ragged64_plan): pure host code; a refusal goes to P's create-error slot.
+template <class P>
+int ragged_show_plan(int64_t n_worlds, const int64_t* n_bodies, int32_t* launch_of_world, int64_t* first_block_of_world, int32_t* n_launches,
+                     int32_t* lds_bytes_of_launch, int64_t* blocks_of_launch) {
+  RaggedPlan plan;
+  if (const int rc = ragged_plan(n_worlds, n_bodies, &plan, launch_of_world, first_block_of_world, P::lds_bytes))
+    return ens_fail<P>(nullptr, NBODY_ERR_INVALID, ragged_plan_error(rc));
+  if (n_launches) *n_launches = plan.n_launches;
+  for (int l = 0; l < kRaggedMaxLaunches; ++l) {
+    if (lds_bytes_of_launch) lds_bytes_of_launch[l] = plan.lds_bytes[l];
+    if (blocks_of_launch) blocks_of_launch[l] = plan.blocks[l];
+  }
+  return NBODY_OK;
 }
 
 }  // namespace nbody

@@ -1,11 +1,14 @@
-// Ragged ensembles (nbody_ragged_*): the launch plan of worlds of different sizes.  Internal, host only, plain C++ (no HIP
-// include): nbody_ragged_plan, the handle's upload and the stand-alone check of tools/ragged_plan_check.cpp use this one header.
+// Ragged ensembles (nbody_ragged_*, nbody_ragged64_*): the launch plan of worlds of different sizes.  Internal, host only, plain
+// C++ (no HIP include): nbody_ragged_plan / nbody_ragged64_plan, the handles' upload and the stand-alone check of
+// tools/ragged_plan_check.cpp use this one header.  The plan is written over the precision's LDS function: ensemble_lds_bytes
+// (f32, the default) or ensemble64_lds_bytes; classes, tiles and work items are the same in both.
 //
 // Launch classes.  Worlds are grouped by the LDS they need, in size order: n <= 128, <= 256, <= 512, <= 1024, <= 2048, <= 4096.
 //   Every class that has a world is one launch per step (at most kRaggedMaxLaunches), in class order; its dynamic LDS is
-//   ensemble_lds_bytes of its LARGEST member, not of the class cap: equal sizes get exactly the uniform ensemble's LDS, and no
+//   the LDS function of its LARGEST member, not of the class cap: equal sizes get exactly the uniform ensemble's LDS, and no
 //   world above 128 bodies sits under more than twice its own need.  The first class holds every lane split (ensemble_split:
-//   2 .. 64 lanes per target) under at most 1.5 KB.
+//   2 .. 64 lanes per target) under at most 1.5 KB (f32; 2.5 KB in f64).  The class caps in f64: 2 560, 5 120, 10 240, 20 480,
+//   40 960 and 81 920 B.  The boundaries are the six doublings in both precisions: reasoned, not measured.
 // Work items.  Within a launch a block is one (world, tile) item; a world's blocks are contiguous, tile ascending, and the
 //   worlds of a launch follow one another in world order.  tiles = ceil(n / (256 / ensemble_split(n))), as in the uniform launch.
 //   The device table holds one 8-byte item per block, {row0, n | tile << 16}: row0 < 2^26, n <= 4096, tile <= 15.
@@ -46,9 +49,12 @@ struct RaggedPlan {
 
 enum { kRaggedOk = 0, kRaggedNoWorld = 1, kRaggedBadSize = 2, kRaggedTooManyRows = 3 };
 
+typedef size_t (*RaggedLdsFn)(int n_bodies);  // the dynamic LDS of a world of n_bodies: ensemble_lds_bytes or ensemble64_lds_bytes
+
 // The plan of `n_worlds` worlds of the sizes n_bodies[]: per launch its LDS and its blocks; per world (either array may be NULL)
 // its launch and the first of its blocks in that launch.  Nothing is written unless the sizes are valid.
-inline int ragged_plan(int64_t n_worlds, const int64_t* n_bodies, RaggedPlan* plan, int32_t* launch_of_world, int64_t* first_block_of_world) {
+inline int ragged_plan(int64_t n_worlds, const int64_t* n_bodies, RaggedPlan* plan, int32_t* launch_of_world, int64_t* first_block_of_world,
+                       RaggedLdsFn lds_bytes_of = ensemble_lds_bytes) {
   if (n_worlds < 1 || !n_bodies) return kRaggedNoWorld;
   if (n_worlds > kEnsembleMaxRows) return kRaggedTooManyRows;  // (every world has a row)
   RaggedPlan p;
@@ -66,7 +72,7 @@ inline int ragged_plan(int64_t n_worlds, const int64_t* n_bodies, RaggedPlan* pl
   for (int cls = 0; cls < kRaggedMaxLaunches; ++cls) {
     if (!max_n[cls]) continue;  // an empty class launches nothing
     p.launch_of_class[cls] = p.n_launches;
-    p.lds_bytes[p.n_launches] = (int32_t)ensemble_lds_bytes(max_n[cls]);
+    p.lds_bytes[p.n_launches] = (int32_t)lds_bytes_of(max_n[cls]);
     p.blocks[p.n_launches] = class_blocks[cls];
     p.total_blocks += class_blocks[cls];
     ++p.n_launches;

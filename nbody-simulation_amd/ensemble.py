@@ -14,7 +14,9 @@ sum |term|.  Shapes, dtypes and the size limits are checked here, with ValueErro
 `RaggedEnsemble` (nbody_ragged_*) holds float32 worlds of DIFFERENT sizes — a sweep over N, clusters drawn from a mass function,
 halos cut out of a larger run — and steps them together with at most six launches per step (`ragged_plan` shows which).  Every
 world takes the same step: EXACT bit-identical to the oracle of that world alone, FAST bit-identical to an `Ensemble` holding
-that world alone, AUTO per world and per step on the device.
+that world alone, AUTO per world and per step on the device.  `RaggedEnsemble64` (nbody_ragged64_*) is its double-precision
+sibling, float64 arrays only: EXACT and AUTO bit-identical to the oracle's update_direct of that world alone on float64, FAST
+(opt-in) bit-identical to an `Ensemble64` holding that world alone.
 """
 from __future__ import annotations
 
@@ -143,10 +145,13 @@ class Ensemble64(_EnsembleBase):
         return _capi.Ensemble64Handle(device)
 
 
-def _checked_ragged(positions, velocities, weights):
+def _checked_ragged(positions, velocities, weights, dtype=np.float32):
     """-> (sizes int64[B], position[rows,2], velocity[rows,2], weight uint32[rows] or None), the worlds' rows one after another;
-    ValueError for anything else.  Nothing is copied before every world has passed."""
-    who = "RaggedEnsemble"
+    ValueError for anything else.  Nothing is copied before every world has passed.  The messages name the class of that dtype:
+    RaggedEnsemble (float32) or RaggedEnsemble64 (float64)."""
+    dtype = np.dtype(dtype)
+    who, other = (("RaggedEnsemble", "RaggedEnsemble64 takes float64") if dtype == np.float32
+                  else ("RaggedEnsemble64", "RaggedEnsemble takes float32"))
     for name, seq in (("positions", positions), ("velocities", velocities)) + ((("weights", weights),) if weights is not None else ()):
         if not hasattr(seq, "__len__"):
             raise ValueError(f"{who}: {name} must be a sequence of per-world arrays")
@@ -159,8 +164,8 @@ def _checked_ragged(positions, velocities, weights):
     for k in range(b):
         p, v = np.asarray(positions[k]), np.asarray(velocities[k])
         for name, a in (("position", p), ("velocity", v)):
-            if a.dtype != np.float32:
-                raise ValueError(f"{who}: world {k}: {name} must be float32 (got {a.dtype})")
+            if a.dtype != dtype:
+                raise ValueError(f"{who}: world {k}: {name} must be {dtype} (got {a.dtype}); {other}")
         if p.ndim != 2 or p.shape[1] != 2:
             raise ValueError(f"{who}: world {k}: position must be [n, 2], got {p.shape}")
         if v.shape != p.shape:
@@ -184,16 +189,21 @@ def _checked_ragged(positions, velocities, weights):
     return np.asarray(sizes, np.int64), position, velocity, weight
 
 
-class RaggedEnsemble:
-    """Worlds of different sizes, stepped together: positions, velocities are sequences of [n_k, 2] float32 arrays, weights a
-    sequence of [n_k] integer arrays or None (all 1).  1 .. 4096 bodies per world, at most 2^26 bodies in all."""
+class _RaggedBase:
+    """What RaggedEnsemble and RaggedEnsemble64 share; each names its dtype, makes its own kind of handle and has its own
+    constructor."""
+    _dtype = None
 
-    def __init__(self, positions, velocities, weights=None, *, device=0, clamp=0.001, arith="auto"):
+    @staticmethod
+    def _new_handle(device):
+        raise NotImplementedError
+
+    def _create(self, positions, velocities, weights, device, clamp, arith):
         if arith not in _ARITH:
             raise ValueError(f"arith must be one of {sorted(_ARITH)}")
         self.h = None
-        args = _checked_ragged(positions, velocities, weights)
-        self.h = _capi.RaggedHandle(device)
+        args = _checked_ragged(positions, velocities, weights, self._dtype)
+        self.h = self._new_handle(device)
         self.h.set_params(clamp=float(clamp), arith=_ARITH[arith])
         self._upload(*args)
 
@@ -205,7 +215,7 @@ class RaggedEnsemble:
 
     def upload(self, positions, velocities, weights=None):
         """Replaces the worlds by others, of any sizes."""
-        self._upload(*_checked_ragged(positions, velocities, weights))
+        self._upload(*_checked_ragged(positions, velocities, weights, self._dtype))
 
     def _per_world(self, a):
         return [w.copy() for w in np.split(a, self._cuts)]
@@ -242,11 +252,42 @@ class RaggedEnsemble:
         self.close()
 
 
-def ragged_plan(sizes):
-    """The launches a RaggedEnsemble of these sizes takes per step (nbody_ragged_plan; host code, no GPU needed) -> dict:
-    launch_of_world, first_block_of_world (a world's blocks are contiguous in its launch), lds_bytes and blocks per launch."""
+class RaggedEnsemble(_RaggedBase):
+    """Worlds of different sizes, stepped together: positions, velocities are sequences of [n_k, 2] float32 arrays, weights a
+    sequence of [n_k] integer arrays or None (all 1).  1 .. 4096 bodies per world, at most 2^26 bodies in all."""
+    _dtype = np.float32
+
+    @staticmethod
+    def _new_handle(device):
+        return _capi.RaggedHandle(device)
+
+    def __init__(self, positions, velocities, weights=None, *, device=0, clamp=0.001, arith="auto"):
+        self._create(positions, velocities, weights, device, clamp, arith)
+
+
+class RaggedEnsemble64(_RaggedBase):
+    """The ragged ensemble in double precision: positions, velocities are sequences of [n_k, 2] float64 arrays.  arith "exact"
+    and "auto" are the exact chain; "fast" is opt-in and gated per world and per step on the device; clamp is a float, widened
+    to double by the library."""
+    _dtype = np.float64
+
+    @staticmethod
+    def _new_handle(device):
+        return _capi.Ragged64Handle(device)
+
+    def __init__(self, positions, velocities, weights=None, arith="exact", clamp=0.001, device=0):
+        self._create(positions, velocities, weights, device, clamp, arith)
+
+
+def ragged_plan(sizes, dtype=np.float32):
+    """The launches a RaggedEnsemble (dtype float64: a RaggedEnsemble64) of these sizes takes per step (nbody_ragged_plan /
+    nbody_ragged64_plan; host code, no GPU needed) -> dict: launch_of_world, first_block_of_world (a world's blocks are
+    contiguous in its launch), lds_bytes and blocks per launch."""
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError(f"ragged_plan: dtype must be float32 or float64, got {dtype}")
     sizes = [int(n) for n in sizes]
     if not sizes or min(sizes) < 1 or max(sizes) > MAX_BODIES or sum(sizes) > MAX_ROWS:
         raise ValueError(f"ragged_plan: at least one world, 1 .. {MAX_BODIES} bodies per world, at most 2^26 in all")
-    launch, first, lds, blocks = _capi.ragged_plan(sizes)
+    launch, first, lds, blocks = _capi.ragged_plan(sizes, f64=dtype == np.float64)
     return dict(launch_of_world=launch, first_block_of_world=first, lds_bytes=lds, blocks=blocks)

@@ -8,7 +8,9 @@
 // times over in a seeded shuffle, (b) 10^5 worlds of seeded random sizes, (c) one world of 1 body, one of 4096, and equal sizes,
 // and checks that every (world, tile) is exactly one item, that a world's items are contiguous in its launch with the right row0
 // and size, that a launch holds one class under the LDS of its largest member, and that invalid sizes are refused with nothing
-// written.  Exit status 0 and "ok" when all of it holds.  A tool, not a test: nothing here touches a device.
+// written — all of it once under the f32 LDS function (ensemble_lds_bytes, the plan's default) and once under the f64 one
+// (ensemble64_lds_bytes), whose six class caps must come out as 2 560 .. 81 920 B.  Exit status 0 and "ok" when all of it holds.
+// A tool, not a test: nothing here touches a device.
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -27,12 +29,20 @@ static int g_failed = 0;
     }                                                                     \
   } while (0)
 
+static RaggedLdsFn g_lds = ensemble_lds_bytes;  // the precision under check
+static const char* g_precision = "f32";
+
 static void check(const std::vector<int64_t>& sizes, const char* what) {
   const int64_t b = (int64_t)sizes.size();
   RaggedPlan plan;
   std::vector<int32_t> launch((size_t)b, -1);
   std::vector<int64_t> first((size_t)b, -1);
-  EXPECT(ragged_plan(b, sizes.data(), &plan, launch.data(), first.data()) == kRaggedOk);
+  EXPECT(ragged_plan(b, sizes.data(), &plan, launch.data(), first.data(), g_lds) == kRaggedOk);
+  if (g_lds == ensemble_lds_bytes) {  // the default is the f32 plan, field for field
+    RaggedPlan dflt;
+    EXPECT(ragged_plan(b, sizes.data(), &dflt, nullptr, nullptr) == kRaggedOk && dflt.n_launches == plan.n_launches);
+    for (int l = 0; l < kRaggedMaxLaunches; ++l) EXPECT(dflt.lds_bytes[l] == plan.lds_bytes[l] && dflt.blocks[l] == plan.blocks[l]);
+  }
   EXPECT(plan.n_launches >= 1 && plan.n_launches <= kRaggedMaxLaunches);
   std::vector<RaggedItem> items((size_t)plan.total_blocks);
   int64_t first_item[kRaggedMaxLaunches];
@@ -65,7 +75,8 @@ static void check(const std::vector<int64_t>& sizes, const char* what) {
   int64_t sum = 0;
   for (int l = 0; l < kRaggedMaxLaunches; ++l) {
     if (l < plan.n_launches) {
-      EXPECT(plan.lds_bytes[l] == (int32_t)ensemble_lds_bytes(max_n[l]) && first_item[l] == sum);
+      EXPECT(plan.lds_bytes[l] == (int32_t)g_lds(max_n[l]) && first_item[l] == sum);
+      for (int64_t k = 0; k < b; ++k) EXPECT(launch[(size_t)k] != l || (size_t)plan.lds_bytes[l] >= g_lds((int)sizes[(size_t)k]));
       EXPECT(l == 0 || cls_of[l] > cls_of[l - 1]);
       sum += plan.blocks[l];
     } else {
@@ -73,10 +84,28 @@ static void check(const std::vector<int64_t>& sizes, const char* what) {
     }
   }
   EXPECT(sum == plan.total_blocks);
-  std::printf("%-28s %8lld worlds %10lld rows %9lld blocks %d launches\n", what, (long long)b, (long long)rows, (long long)blocks, plan.n_launches);
+  std::printf("%-28s %s %8lld worlds %10lld rows %9lld blocks %d launches\n", what, g_precision, (long long)b, (long long)rows, (long long)blocks, plan.n_launches);
 }
 
+static void check_all();
+
 int main() {
+  check_all();
+  g_lds = ensemble64_lds_bytes;
+  g_precision = "f64";
+  check_all();
+  // the f64 class caps, and either side of the 64 KiB dynamic-LDS limit
+  const int64_t caps[] = {128, 256, 512, 1024, 2048, 4096};
+  const int32_t want[] = {2560, 5120, 10240, 20480, 40960, 81920};
+  RaggedPlan plan;
+  EXPECT(ragged_plan(6, caps, &plan, nullptr, nullptr, ensemble64_lds_bytes) == kRaggedOk && plan.n_launches == 6);
+  for (int l = 0; l < 6; ++l) EXPECT(plan.lds_bytes[l] == want[l]);
+  EXPECT(ensemble64_lds_bytes(3272) == 65440 && ensemble64_lds_bytes(3273) == 65600 && ensemble64_lds_bytes(1) == 160);
+  std::puts(g_failed ? "FAILED" : "ok");
+  return g_failed ? 1 : 0;
+}
+
+static void check_all() {
   const int64_t edge[] = {1, 2, 3, 7, 12, 24, 50, 100, 128, 129, 256, 257, 300, 512, 513, 1000, 1024, 1025, 2048, 2049, 4096};
   std::mt19937_64 rng(20261019);
   std::vector<int64_t> sizes;
@@ -92,7 +121,7 @@ int main() {
   {
     RaggedPlan untouched;
     std::vector<int32_t> launch(sizes.size(), -7);
-    EXPECT(keep == sizes.size() || ragged_plan((int64_t)sizes.size(), sizes.data(), &untouched, launch.data(), nullptr) == kRaggedTooManyRows);
+    EXPECT(keep == sizes.size() || ragged_plan((int64_t)sizes.size(), sizes.data(), &untouched, launch.data(), nullptr, g_lds) == kRaggedTooManyRows);
     EXPECT(untouched.n_launches == 0 && launch[0] == -7);
   }
   sizes.resize(keep);  // the longest prefix within 2^26 rows
@@ -108,14 +137,11 @@ int main() {
 
   RaggedPlan plan;
   const int64_t zero[] = {5, 0}, big[] = {4097}, neg[] = {-3};
-  EXPECT(ragged_plan(2, zero, &plan, nullptr, nullptr) == kRaggedBadSize);
-  EXPECT(ragged_plan(1, big, &plan, nullptr, nullptr) == kRaggedBadSize);
-  EXPECT(ragged_plan(1, neg, &plan, nullptr, nullptr) == kRaggedBadSize);
-  EXPECT(ragged_plan(0, zero, &plan, nullptr, nullptr) == kRaggedNoWorld);
-  EXPECT(ragged_plan(1, nullptr, &plan, nullptr, nullptr) == kRaggedNoWorld);
+  EXPECT(ragged_plan(2, zero, &plan, nullptr, nullptr, g_lds) == kRaggedBadSize);
+  EXPECT(ragged_plan(1, big, &plan, nullptr, nullptr, g_lds) == kRaggedBadSize);
+  EXPECT(ragged_plan(1, neg, &plan, nullptr, nullptr, g_lds) == kRaggedBadSize);
+  EXPECT(ragged_plan(0, zero, &plan, nullptr, nullptr, g_lds) == kRaggedNoWorld);
+  EXPECT(ragged_plan(1, nullptr, &plan, nullptr, nullptr, g_lds) == kRaggedNoWorld);
   EXPECT(plan.n_launches == 0 && plan.rows == 0);
-  EXPECT(ragged_plan(1, big + 0, nullptr, nullptr, nullptr) == kRaggedBadSize && ragged_plan(2, edge, nullptr, nullptr, nullptr) == kRaggedOk);
-
-  std::puts(g_failed ? "FAILED" : "ok");
-  return g_failed ? 1 : 0;
+  EXPECT(ragged_plan(1, big + 0, nullptr, nullptr, nullptr, g_lds) == kRaggedBadSize && ragged_plan(2, edge, nullptr, nullptr, nullptr, g_lds) == kRaggedOk);
 }
