@@ -1,4 +1,4 @@
-// Device-side BVH build (bvh_build.hip), f32.  Internal to the library.
+// Device-side BVH build (bvh_build.hip and the units it launches, bvh_units.h), f32.  Internal to the library.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -2,7 +2,7 @@
 // as the oracle, node for node — BVHTree::from + make_leaf + calculate_gravity of /root/reference src/bvh_tree.rs:40-158
 // carried over to f64 (the reference itself is f32: this is the extension BASELINE's f64 configurations use).
 //
-// bvh_build.hip (f32) is tuned to the last microsecond for the reference's own scene; this one is the same mathematics
+// bvh_build.hip and its units (f32) are tuned to the last microsecond for the reference's own scene; this one is the same mathematics
 // written plainly, level by level over ALL open nodes at once, because what it replaces is a 50-65 ms host build at
 // N = 4 M (HISTORY.md §4.3c), not a 0.7 ms device one:
 //   per level   fold64      one work-group per (open node, coordinate): min / max and the sum EXACTLY as the sequential chain
@@ -776,7 +776,7 @@ Bvh64Layout bvh64_layout(int64_t n, int leaf_size) {
   Bvh64Layout L{};
   const size_t N = (size_t)(n > 0 ? n : 1);
   const size_t lf = (size_t)(leaf_size > 0 ? leaf_size : 1);
-  const size_t C = (4 * N / lf < 2 * N ? 4 * N / lf : 2 * N) + 4096;  // as bvh_build.hip: more nodes than this -> host builder
+  const size_t C = (4 * N / lf < 2 * N ? 4 * N / lf : 2 * N) + 4096;  // as bvh_build.hip (bvh_build_layout): more nodes than this -> host builder
   const size_t OC = N / (lf + 1) + 2;                                   // open nodes of one level hold > leaf_size points each
   const size_t CC = N / (size_t)kChunk + OC + 2;                        // their chunks
   L.node_cap = (int)C;

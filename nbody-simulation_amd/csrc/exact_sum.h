@@ -17,7 +17,7 @@
 // The f64 BVH (an extension: the reference is f32) folds the same chain with 53-bit significands (M = 52).  Increments
 // are 64-bit: that is all it takes.  Traits<T> holds every constant in which the two precisions differ.
 //
-// Host + device: the device folds (bvh_build.hip, bvh_build64.hip) and the CPU emulations the tests run
+// Host + device: the device folds (bvh_fold.hip, bvh_build64.hip) and the CPU emulations the tests run
 // (exact_sum_emulate.h, through `nbody_selftest_exact_sum*` of capi.hip) run the very same functions.
 #pragma once
 #include <stdint.h>
@@ -166,7 +166,7 @@ template <class T> NB_HD bool run_fits(Word<T> S, const Run<T>& r) {
 }
 
 // ---- what only one of the builds uses --------------------------------------------------------------------------------
-// f32 only (bvh_chunk_runs of bvh_build.hip): how close (relatively) to a power of two a predicted prefix may come and still
+// f32 only (bvh_chunk_runs of bvh_fold.hip): how close (relatively) to a power of two a predicted prefix may come and still
 // be trusted.  The f32 chain drifts from the exact prefix by ~sqrt(n) half-ulps (worst case n): 2^-13 covers millions of
 // addends; if it is ever too tight, the run's own bounds fail when it is applied and the scan takes over.  The addends inside
 // the margin are added for real, so the margin also is 2 * margin * (addends so far) of serial work per crossing.

@@ -46,7 +46,7 @@ template <class T> inline T emulate_fold(const T* x, int64_t n, int tile, int se
   return s;
 }
 
-// f32, the chunked fold (bvh_build.hip: bvh_chunk_sums / bvh_chunk_runs / the chunk walk of bvh_big_fold): every chunk's runs
+// f32, the chunked fold (bvh_fold.hip: bvh_chunk_sums / bvh_chunk_runs / the chunk walk of bvh_big_fold): every chunk's runs
 // are prepared for the binades its start and end are PREDICTED to be in (from exact f64 partial sums); the walk uses a run
 // only if the prediction and the bounds hold for the true state, and adds for real otherwise.  A chunk that contains a
 // crossing is split three ways (bvh_chunk_runs' second form): thread segments of `seg` addends whose predicted prefix stays

@@ -1,6 +1,6 @@
 // libnbody_hip — phase 1 of a tree step (main.rs:398-401): the device builds (BVH in f32 and f64, quad tree), the host
 // builders' fallback and the installation of a linearised tree (the host builders', or a caller's: caller_tree.hip), and the
-// host image of a device-built tree for the export API.  Kernels: bvh_build.hip, bvh_build64.hip, quad_build.hip, tree_kernels.hip.
+// host image of a device-built tree for the export API.  Kernels: bvh_build.hip (with bvh_fold / bvh_partition / bvh_subtrees / bvh_finish.hip), bvh_build64.hip, quad_build.hip, tree_kernels.hip.
 #include <algorithm>
 #include <cstdio>
 #include <type_traits>
@@ -57,7 +57,7 @@ template <class T> int ensure_node_aux(nbody_ctx* c, State<T>& s, size_t m) {
   return NBODY_OK;
 }
 
-// BVH built on the device (bvh_build.hip, f32 only).  Returns NBODY_OK, an error, or 1 when the device build declines.
+// BVH built on the device (bvh_build.hip and its units, f32 only).  Returns NBODY_OK, an error, or 1 when the device build declines.
 // The same for f64 rows (bvh_build64.hip): every level enqueued blind, one question at the end.
 int bvh_build_device64(nbody_ctx* c, State<double>& s) {
   const int n = (int)s.n;

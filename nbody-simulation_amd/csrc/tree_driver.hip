@@ -1,7 +1,7 @@
 // libnbody_hip — the Barnes-Hut step driver: phase timing, the walk phase (main.rs:406-416), the f32 BVH step enqueued whole
 // ahead of the host (bvh_step_ahead), the plain and the sharded step, the row exchange of a sharded step, and the tree entry
 // points of the C ABI (nbody_update_tree_*, nbody_wait, nbody_accel_tree_*, ...).  Builds: tree_build_driver.hip.
-// Kernels: walk_prepare.hip, walk_tile.hip, walk_tile_fast.hip, walk_lab.hip (launched through walk_launch.hip), tree_kernels.hip, bvh_build.hip.
+// Kernels: walk_prepare.hip, walk_tile.hip, walk_tile_fast.hip, walk_lab.hip (launched through walk_launch.hip), tree_kernels.hip, bvh_build.hip and its units (bvh_units.h).
 #include <algorithm>
 #include <cstdio>
 #include <cstring>

@@ -7,7 +7,7 @@ namespace nbody {
 
 // LDS written by some lanes of a wave and read by other lanes of the same wave: wave_barrier alone is a scheduling
 // barrier (IntrNoMem), not a memory fence, so the hand-off is release -> barrier -> acquire at wavefront scope
-// (the form bvh_build.hip's group_sync<1> uses).  Costs nothing at run time: a wave's LDS accesses complete in order.
+// (the form bvh_subtrees.hip's group_sync<1> uses).  Costs nothing at run time: a wave's LDS accesses complete in order.
 __device__ __forceinline__ void wave_lds_handoff() {
 #if defined(__HIP_DEVICE_COMPILE__)
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

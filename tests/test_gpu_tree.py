@@ -254,7 +254,7 @@ def test_fast_walk_is_within_tolerance_of_the_exact_walk(nb, orc, ctx, dtype, ki
     assert np.all(err <= tol * norm), float((err / norm).max())
 
 
-# ------------------------------------------------------------------ device-side BVH build (bvh_build.hip)
+# ------------------------------------------------------------------ device-side BVH build (bvh_build.hip + bvh_fold / bvh_partition / bvh_subtrees / bvh_finish.hip)
 def _bvh_export_equal(a, b):
     for k in ("mass", "is_leaf", "first", "count", "skip", "order"):
         assert np.array_equal(a[k], b[k]), k
@@ -313,7 +313,7 @@ def test_device_bvh_build_equals_oracle_tree(nb, orc, ctx, leaf):
 @pytest.mark.parametrize("scene", ["plummer_1m", "centred_1m5", "negative_700k"])
 def test_device_bvh_build_equals_the_host_builder_on_long_chains(nb, ctx, scene):
     """The same at sizes where the chain is folded out of LDS windows over many rounds, with prepared chunk runs, crossings
-    seen coming and same-sign rounds proven by their end (bvh_build.hip exact_fold): against the host builder, which adds one
+    seen coming and same-sign rounds proven by their end (bvh_fold.hip exact_fold): against the host builder, which adds one
     point after the other (tree_build.hpp; itself checked against the oracle at the smaller sizes above)."""
     C = nb._capi
     rng = np.random.default_rng(23)

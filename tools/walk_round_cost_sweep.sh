@@ -1,11 +1,15 @@
 # Round 4: the leaf-step arm thresholds of the one-pass walks (lane = particle rounds vs lane = target) swept on the bench's BVH legs:
 # the laboratory library rebuilt on the GPU box with -DNB_TILE_ROUND_COST / -DNB_FAST_ROUND_COST.   bash tools/walk_round_cost_sweep.sh
-cd nbody-simulation_amd/csrc
+# On the way out, however it ends, the laboratory library is rebuilt with the default constants.
+set -o pipefail
+cd nbody-simulation_amd/csrc || exit 1
 export NBODY_HIP_LIBRARY=lab
-BASE="-O3 -std=c++17 -fPIC -ffp-contract=off -fvisibility=hidden"
+UNITS="walk_tile walk_tile_fast walk_lab"  # the units that read the two constants (walk_device.h)
+drop_objects() { for u in $UNITS; do rm -f "$u.lab.o"; done; }
+trap 'drop_objects; make lab > /dev/null' EXIT
 for cfg in "" "-DNB_TILE_ROUND_COST=40 -DNB_FAST_ROUND_COST=12" "-DNB_TILE_ROUND_COST=52 -DNB_FAST_ROUND_COST=16" "-DNB_TILE_ROUND_COST=85 -DNB_FAST_ROUND_COST=24" "-DNB_TILE_ROUND_COST=110 -DNB_FAST_ROUND_COST=32"; do
-  rm -f walk_tile.lab.o walk_tile_fast.lab.o walk_lab.lab.o  # the units that read the two constants (walk_device.h)
-  make lab CXXFLAGS="$BASE $cfg" > /dev/null 2>&1 || { echo "build failed: $cfg"; continue; }
+  drop_objects
+  make lab DEFS="$cfg" > /dev/null 2>&1 || { echo "build failed: $cfg"; continue; }
   for leg in reference_scene_bvh plummer1m_bvh; do
   (cd ../.. && timeout -k 10 150 python bench.py --leg $leg --no-cpu-baseline > gpurun_out/r04_rc.json 2> gpurun_out/r04_rc.err && python -c "
 import json,sys; d=json.load(open('gpurun_out/r04_rc.json'))
