@@ -39,7 +39,7 @@
  *   Params.  nbody_default_params' values at creation; clamp and arith are used, the rest is kept and ignored.
  *   Not offered: f64 on this handle (nbody_ensemble64_* below is the double-precision sibling); worlds of different sizes on
  *     this handle (nbody_ragged_* at the end of this file steps them together); a per-world delta or clamp; tree methods;
- *     tracers; several devices; snapshots, delta streams and frames of an ensemble; hipGraph replay.  The library reads no
+ *     tracers on this handle (nbody_restricted_* at the end of this file); several devices; snapshots, delta streams and frames of an ensemble; hipGraph replay.  The library reads no
  *     environment variable for any of this.
  * Arrays are world-major, [n_worlds][n_bodies] rows, pos / vel interleaved x,y; weight may be NULL (all 1); an upload replaces
  * the previous ensemble, whatever its shape. */
@@ -171,5 +171,70 @@ int nbody_ragged64_update(nbody_ragged64* e, double delta, int n_steps, nbody_co
 int nbody_ragged64_accel(nbody_ragged64* e, double* acc_xy);                      /* force only, state untouched */
 int nbody_ragged64_plan(int64_t n_worlds, const int64_t* n_bodies, int32_t* launch_of_world, int64_t* first_block_of_world,
                         int32_t* n_launches, int32_t* lds_bytes_of_launch, int64_t* blocks_of_launch);
+
+/* ---- restricted ensembles: tracers that step with each world, a handle of its own (f32) ---------------------------
+ * The restricted problem under many seeds or parameters: a few massive bodies and thousands of test particles per world — ring
+ * and belt stability maps, capture cross-sections, scattering sweeps.  A restricted ensemble holds n_worlds worlds of n_bodies
+ * bodies each, as nbody_ensemble_* does (1 <= n_bodies <= 4096, n_worlds * n_bodies <= 2^26), and beside them n_tracers massless
+ * points per world (n_tracers >= 0, the same for every world, n_worlds * n_tracers <= 2^26).  All arrays are world-major:
+ * [n_worlds][n_bodies] and [n_worlds][n_tracers] rows, pos / vel interleaved x,y.  Every step advances the bodies and the
+ * tracers of all worlds in at most two launches (one for the bodies, one for the tracers); there is no host synchronisation
+ * between the steps of a call and nothing is read back.
+ *   Bodies.  Every world's bodies take the step of nbody_ensemble_update_f32, from the same kernel and launch: they are
+ *     bit-identical to an nbody_ensemble holding the same worlds, under EXACT, FAST and AUTO, with or without tracers.  With
+ *     n_tracers == 0 the handle is an nbody_ensemble under another name.
+ *   Tracers.  A tracer's acceleration is the field of its own world's bodies at their pre-step positions (the buffer that
+ *     step's launch of the bodies reads): a_t = sum_j calculate_gravity(p_t, p_j, w_j), j ascending.  It has no mass and no self
+ *     term (a tracer on a body meets that body's pair like any other).  It integrates as main.rs:419-423 in f32: v += a*dt;
+ *     x += v*dt, multiply then add, no contraction.  Tracer rows never move.
+ *   EXACT.  One ascending-row chain of the pair as written (IEEE divisions, the is_normal skip, no contraction) per tracer:
+ *     bit-identical to the CPU restatement's direct_accel at the tracers (native accumulation) followed by that Euler step, and
+ *     to a context of that world alone with the tracers of nbody_tracers_* under EXACT.
+ *   FAST.  One lane per tracer, whatever n_bodies is.  The order of additions is the one the ensemble's bodies have for
+ *     n_bodies > 128: source couples ascending, even and odd sources summed apart in a packed accumulator, every run of 64
+ *     couples folded and added to the running total — a function of n_bodies alone, with the ensemble's pair (one v_rcp_f32,
+ *     the 2^-90 biased denominator, s = m * rcp).  Hence every tracer is within the tolerance of DESIGN.md (2e-5 of
+ *     sum_j |term|; worst case 6e-6 at n_bodies = 4096, as for the bodies), and for n_bodies > 128 a tracer that sits exactly
+ *     on a body gets that body's FAST acceleration bit for bit (the self pair adds exactly 0 on both sides).
+ *   AUTO.  Decided per world and per step on the device, without a flag buffer: a tracer block stages its whole world as a
+ *     body block does, and a world whose bodies take EXACT for a step (a position outside FAST's domain: non-finite, >= 2^60 in
+ *     magnitude, or non-zero below 2^-22) has all its tracers take EXACT for that step.  In a FAST world a tracer whose own
+ *     pre-step position is outside that domain takes its EXACT value for that step; its neighbours keep their FAST bits.  With
+ *     a clamp below 2^-19, or NaN, everything takes EXACT (FAST asked for by name, too).
+ *   Independence.  A tracer's bits depend on its own state, its world's bodies, n_bodies and the params.  They do not depend on
+ *     n_tracers, on its slot among the tracers, on n_worlds, on its world's index, on the other worlds' contents or routes, or
+ *     on how the steps are split over calls.  For this the sources are never split over lanes, however few tracers a world has:
+ *     a shape with few tracers per world leaves lanes idle (a block is 512 tracers of one world).
+ *   Lifetime.  nbody_restricted_upload_f32 replaces the bodies and removes the tracers (a new world);
+ *     nbody_restricted_tracers_upload_f32 replaces the tracers, n_tracers == 0 removes them (pos_xy / vel_xy may then be NULL);
+ *     its n_worlds must be the bodies'.  Without tracers the tracer downloads and nbody_restricted_tracers_accel_f32 write
+ *     nothing and return NBODY_OK.
+ *   Booking, params, trivial calls.  As the ensemble's: the whole call goes under sum_gravity; clamp and arith are used;
+ *     n_steps == 0 is a no-op; an update, accel or download before an upload is NBODY_ERR_INVALID.
+ *   Errors.  Anything outside the limits gives NBODY_ERR_INVALID before anything is allocated, and the message names
+ *     "restricted".  There is no CPU path: nbody_restricted_create fails with NBODY_ERR_NO_DEVICE without a gfx950 device.  A
+ *     NULL handle gives NBODY_ERR_INVALID (0 from nbody_restricted_num_worlds / _num_bodies / _num_tracers);
+ *     nbody_restricted_last_error(NULL): the last failed nbody_restricted_create on this thread, in a slot of its own.
+ *   Not offered on this handle: f64, worlds of different sizes or a per-world n_tracers (follow-ups of their own, as f64 and
+ *     ragged were for bodies); tree methods; several devices; snapshots, delta streams and frames; hipGraph replay.  The
+ *     library reads no environment variable for any of this. */
+typedef struct nbody_restricted nbody_restricted;
+int nbody_restricted_create(nbody_restricted** out, int device_id);
+void nbody_restricted_destroy(nbody_restricted* e);
+const char* nbody_restricted_last_error(const nbody_restricted* e);
+int nbody_restricted_set_params(nbody_restricted* e, const nbody_params* p);
+int nbody_restricted_get_params(const nbody_restricted* e, nbody_params* out);
+int nbody_restricted_upload_f32(nbody_restricted* e, int64_t n_worlds, int64_t n_bodies, const float* pos_xy, const float* vel_xy,
+                                const uint32_t* weight);
+int nbody_restricted_download_f32(nbody_restricted* e, float* pos_xy, float* vel_xy);         /* the bodies; either may be NULL */
+int nbody_restricted_tracers_upload_f32(nbody_restricted* e, int64_t n_worlds, int64_t n_tracers, const float* pos_xy,
+                                        const float* vel_xy);
+int nbody_restricted_tracers_download_f32(nbody_restricted* e, float* pos_xy, float* vel_xy); /* either may be NULL */
+int64_t nbody_restricted_num_worlds(const nbody_restricted* e);
+int64_t nbody_restricted_num_bodies(const nbody_restricted* e);                               /* per world */
+int64_t nbody_restricted_num_tracers(const nbody_restricted* e);                              /* per world */
+int nbody_restricted_update_f32(nbody_restricted* e, float delta, int n_steps, nbody_counting* counter);
+int nbody_restricted_accel_f32(nbody_restricted* e, float* acc_xy);                           /* the bodies; state untouched */
+int nbody_restricted_tracers_accel_f32(nbody_restricted* e, float* acc_xy);                   /* the tracers; state untouched */
 
 #endif /* NBODY_ENSEMBLE_H */

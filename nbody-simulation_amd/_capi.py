@@ -136,6 +136,21 @@ _SIGS = {
     "nbody_ragged64_update": (C.c_int, [_vp, _f64, _i32, C.POINTER(Counting)]),
     "nbody_ragged64_accel": (C.c_int, [_vp, _vp]),
     "nbody_ragged64_plan": (C.c_int, [_i64, _vp, _vp, _vp, C.POINTER(_i32), _vp, _vp]),
+    "nbody_restricted_create": (C.c_int, [C.POINTER(_vp), _i32]),
+    "nbody_restricted_destroy": (None, [_vp]),
+    "nbody_restricted_last_error": (C.c_char_p, [_vp]),
+    "nbody_restricted_set_params": (C.c_int, [_vp, C.POINTER(Params)]),
+    "nbody_restricted_get_params": (C.c_int, [_vp, C.POINTER(Params)]),
+    "nbody_restricted_upload_f32": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    "nbody_restricted_download_f32": (C.c_int, [_vp, _vp, _vp]),
+    "nbody_restricted_tracers_upload_f32": (C.c_int, [_vp, _i64, _i64, _vp, _vp]),
+    "nbody_restricted_tracers_download_f32": (C.c_int, [_vp, _vp, _vp]),
+    "nbody_restricted_num_worlds": (_i64, [_vp]),
+    "nbody_restricted_num_bodies": (_i64, [_vp]),
+    "nbody_restricted_num_tracers": (_i64, [_vp]),
+    "nbody_restricted_update_f32": (C.c_int, [_vp, _f32, _i32, C.POINTER(Counting)]),
+    "nbody_restricted_accel_f32": (C.c_int, [_vp, _vp]),
+    "nbody_restricted_tracers_accel_f32": (C.c_int, [_vp, _vp]),
     "nbody_accel_tree_f32": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_accel_tree_f64": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_tree_info": (C.c_int, [_vp, C.POINTER(TreeView)]),
@@ -937,6 +952,31 @@ class RaggedHandle(_EnsembleHandleBase):
 class Ragged64Handle(RaggedHandle):
     """nbody_ragged64_*: float64 worlds of different sizes, the sibling of RaggedHandle."""
     _prefix, _suffix, _dtype = "nbody_ragged64", "", np.float64
+
+
+class RestrictedHandle(EnsembleHandle):
+    """nbody_restricted_*: float32 worlds of one size with m tracers each; the bodies' calls are EnsembleHandle's."""
+    _prefix = "nbody_restricted"
+
+    @property
+    def n_tracers(self):
+        """Tracers per world; 0 without any."""
+        return int(self._call("_num_tracers"))
+
+    def upload_tracers(self, n_worlds, n_tracers, pos, vel):
+        """pos, vel [n_worlds, n_tracers, 2] float32, contiguous; n_tracers == 0 removes the tracers."""
+        self._check(self._call("_tracers_upload_f32", int(n_worlds), int(n_tracers), _ptr(pos), _ptr(vel)))
+
+    def download_tracers(self):
+        b, m = self.shape[0], self.n_tracers
+        pos, vel = np.zeros((b, m, 2), np.float32), np.zeros((b, m, 2), np.float32)
+        self._check(self._call("_tracers_download_f32", _ptr(pos), _ptr(vel)))
+        return pos, vel
+
+    def tracers_accel(self):
+        acc = np.zeros((self.shape[0], self.n_tracers, 2), np.float32)
+        self._check(self._call("_tracers_accel_f32", _ptr(acc)))
+        return acc
 
 
 RAGGED_MAX_LAUNCHES = 6

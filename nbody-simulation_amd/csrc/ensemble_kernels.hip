@@ -27,75 +27,35 @@
 #include "../../include/nbody_hip.h"
 #include "ensemble_device.h"
 #include "ensemble_kernels.h"
-#include "fast_domain.h"
-#include "pair.h"
+#include "ensemble_world.h"
 
 namespace nbody {
 namespace {
 
-typedef float ens_v2f __attribute__((ext_vector_type(2)));
-typedef float ens_v4f __attribute__((ext_vector_type(4)));
-
-constexpr float kEnsDenBias = 8.0779356694631609e-28f;  // 2^-90, as direct_kernels.hip
-constexpr int kEnsRun = 64;                              // couples of one lane summed on their own before they join its total
-
-// |a| + |b| as ONE v_add_f32 with abs modifiers (left to itself the compiler packs the add and pays four v_and for the moduli)
-__device__ __forceinline__ float ens_abs_sum(float a, float b) {
-  float r;
-  asm("v_add_f32 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-
 // What a block computes: one tile of the targets of the world whose rows are row0 .. row0 + n — its sources staged in LDS with
-// the AUTO decision taken on the way, then the EXACT or the FAST arm.  A function of the world through (n, row0, tile) alone: the
-// uniform kernel and the ragged one share it, and with it every bit.  Every thread of the block calls it (it holds a barrier).
+// the AUTO decision taken on the way, then the EXACT or the FAST arm (ensemble_world.h has the staging and both sums).  A
+// function of the world through (n, row0, tile) alone: the uniform kernel and the ragged one share it, and with it every bit.
+// Every thread of the block calls it (it holds a barrier).
 template <int SPLIT>
 __device__ __forceinline__ void ens_world_tile(const EnsembleArgs& a, const int n, const size_t row0, const unsigned tile) {
   constexpr int TPB = kEnsembleBlock / SPLIT;  // targets per block
   extern __shared__ __attribute__((aligned(16))) unsigned char ens_lds[];
-  const int nc = (n + 1) >> 1;  // couples
-  float* const cplf = reinterpret_cast<float*>(ens_lds);
-  const ens_v4f* const cpl = reinterpret_cast<const ens_v4f*>(ens_lds);
-  float* const massf = cplf + 4 * nc;
-  const ens_v2f* const mass2 = reinterpret_cast<const ens_v2f*>(massf);
+  const EnsWorldLds w(ens_lds, n);
 
   // ---- the world's sources into LDS, and its AUTO decision on the way
-  int bad = 0;
-  for (int s = (int)threadIdx.x; s < 2 * nc; s += kEnsembleBlock) {
-    float2 p = make_float2(0.f, 0.f);
-    float m = 0.f;
-    if (s < n) {
-      p = a.pos_in[row0 + s];
-      m = a.mass[row0 + s];
-      bad |= (int)outside_fast(p.x) | (int)outside_fast(p.y);
-    }
-    const int o = 4 * (s >> 1) + (s & 1);
-    cplf[o] = p.x;
-    cplf[o + 2] = p.y;
-    massf[s] = m;
-  }
-  const int hazard = __syncthreads_or(a.arith == NBODY_ARITH_AUTO ? bad : 0);
+  const int hazard = ens_stage_world(w, a.pos_in, a.mass, row0, a.arith == NBODY_ARITH_AUTO);
   const float clamp = a.clamp;
+  float px[1], py[1], ax[1], ay[1];
 
   if (a.arith == NBODY_ARITH_EXACT || hazard) {
     // ---- EXACT: thread = target, j ascending (no barrier follows: threads without a target leave)
     if ((int)threadIdx.x >= TPB) return;
     const int t = (int)tile * TPB + (int)threadIdx.x;
     if (t >= n) return;
-    const int ot = 4 * (t >> 1) + (t & 1);
-    const float px = cplf[ot], py = cplf[ot + 2];
-    float ax = 0.f, ay = 0.f;
-    for (int c = 0; c < (n >> 1); ++c) {
-      const ens_v4f s = cpl[c];
-      const ens_v2f m = mass2[c];
-      pair_as_written<float>(px, py, s.x, s.z, m.x, clamp, ax, ay);
-      pair_as_written<float>(px, py, s.y, s.w, m.y, clamp, ax, ay);
-    }
-    if (n & 1) {
-      const ens_v4f s = cpl[nc - 1];
-      pair_as_written<float>(px, py, s.x, s.z, massf[n - 1], clamp, ax, ay);
-    }
-    ens_integrate(a, row0 + t, px, py, ax, ay);
+    const float2 p = w.body(t);
+    px[0] = p.x, py[0] = p.y;
+    ens_exact_sum<1>(w, px, py, clamp, ax, ay);
+    ens_integrate(a, row0 + t, px[0], py[0], ax[0], ay[0]);
     return;
   }
 
@@ -103,42 +63,12 @@ __device__ __forceinline__ void ens_world_tile(const EnsembleArgs& a, const int 
   const int part = (int)threadIdx.x % SPLIT;
   const int t = (int)tile * TPB + (int)threadIdx.x / SPLIT;
   const bool live = t < n;
-  const int ot = live ? 4 * (t >> 1) + (t & 1) : 0;
-  const float px = cplf[ot], py = cplf[ot + 2];
-  const ens_v2f tx = {px, px}, ty = {py, py};
-  const ens_v2f bias = {kEnsDenBias, kEnsDenBias};
-  float ax = 0.f, ay = 0.f;
-  for (int c0 = part; c0 < nc; c0 += SPLIT * kEnsRun) {
-    const int c1 = c0 + SPLIT * kEnsRun < nc ? c0 + SPLIT * kEnsRun : nc;
-    ens_v2f accx = {0.f, 0.f}, accy = {0.f, 0.f};
-    auto couple = [&](int c) {
-      const ens_v4f s = cpl[c];
-      const ens_v2f m = mass2[c];
-      const ens_v2f dx = s.xy - tx, dy = s.zw - ty;
-      ens_v2f d2 = __builtin_elementwise_fma(dy, dy, dx * dx);
-      const ens_v2f sum = {ens_abs_sum(dx.x, dy.x), ens_abs_sum(dx.y, dy.y)};
-      d2.x = __builtin_fmaxf(d2.x, clamp);
-      d2.y = __builtin_fmaxf(d2.y, clamp);
-      const ens_v2f den = __builtin_elementwise_fma(sum, d2, bias);
-      const ens_v2f r = {__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
-      const ens_v2f sc = m * r;
-      accx = __builtin_elementwise_fma(dx, sc, accx);
-      accy = __builtin_elementwise_fma(dy, sc, accy);
-    };
-    int c = c0;
-    for (; c + 3 * SPLIT < c1; c += 4 * SPLIT) {  // (unrolled by hand: a loop with an asm statement in it is not unrolled for us)
-      couple(c);
-      couple(c + SPLIT);
-      couple(c + 2 * SPLIT);
-      couple(c + 3 * SPLIT);
-    }
-    for (; c < c1; c += SPLIT) couple(c);
-    ax = ax + (accx.x + accx.y);
-    ay = ay + (accy.x + accy.y);
-  }
-  ax = ens_group_sum<SPLIT>(ax);
-  ay = ens_group_sum<SPLIT>(ay);
-  if (live && part == 0) ens_integrate(a, row0 + t, px, py, ax, ay);
+  const float2 p = w.body(live ? t : 0);
+  px[0] = p.x, py[0] = p.y;
+  ens_fast_sum<SPLIT, 1>(w, part, px, py, clamp, ax, ay);
+  const float sx = ens_group_sum<SPLIT>(ax[0]);
+  const float sy = ens_group_sum<SPLIT>(ay[0]);
+  if (live && part == 0) ens_integrate(a, row0 + t, px[0], py[0], sx, sy);
 }
 
 template <int SPLIT>

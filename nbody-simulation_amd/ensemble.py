@@ -17,6 +17,11 @@ world takes the same step: EXACT bit-identical to the oracle of that world alone
 that world alone, AUTO per world and per step on the device.  `RaggedEnsemble64` (nbody_ragged64_*) is its double-precision
 sibling, float64 arrays only: EXACT and AUTO bit-identical to the oracle's update_direct of that world alone on float64, FAST
 (opt-in) bit-identical to an `Ensemble64` holding that world alone.
+
+`RestrictedEnsemble` (nbody_restricted_*) is an `Ensemble` whose worlds carry m tracers each — massless points that feel their
+own world's bodies and nothing else: the restricted problem under many seeds.  The bodies are bit-identical to an `Ensemble` of
+the same worlds; a tracer is EXACT bit-identical to the oracle's direct_accel at it + Euler, FAST within the tolerance of
+DESIGN.md, AUTO per world and per step on the device with a per-tracer exception for a tracer outside FAST's domain.
 """
 from __future__ import annotations
 
@@ -31,12 +36,13 @@ MAX_ROWS = 1 << 26         # worlds * bodies
 _ARITH = {"auto": _capi.ARITH_AUTO, "fast": _capi.ARITH_FAST, "exact": _capi.ARITH_EXACT}
 
 
-def _checked(position, velocity, weight, dtype=np.float32):
+def _checked(position, velocity, weight, dtype=np.float32, who=None):
     """-> (B, n, position[B,n,2], velocity[B,n,2], weight[B,n] or None), contiguous; ValueError for anything else.  The
-    messages name the class of that dtype: Ensemble (float32) or Ensemble64 (float64)."""
+    messages name `who`, or the class of that dtype: Ensemble (float32) or Ensemble64 (float64)."""
     position, velocity = np.asarray(position), np.asarray(velocity)
     dtype = np.dtype(dtype)
-    who, other = ("Ensemble", "Ensemble64 takes float64") if dtype == np.float32 else ("Ensemble64", "Ensemble takes float32")
+    name, other = ("Ensemble", "Ensemble64 takes float64") if dtype == np.float32 else ("Ensemble64", "Ensemble takes float32")
+    who = who or name
     for name, a in (("position", position), ("velocity", velocity)):
         if a.dtype != dtype:
             raise ValueError(f"{who}: {name} must be {dtype} (got {a.dtype}); {other}")
@@ -68,7 +74,7 @@ def _checked(position, velocity, weight, dtype=np.float32):
 
 
 class _EnsembleBase:
-    """What Ensemble and Ensemble64 share; each names its dtype and makes its own kind of handle."""
+    """What Ensemble, Ensemble64 and RestrictedEnsemble share; each names its dtype and makes its own kind of handle."""
     _dtype = None
 
     @staticmethod
@@ -143,6 +149,82 @@ class Ensemble64(_EnsembleBase):
     @staticmethod
     def _new_handle(device):
         return _capi.Ensemble64Handle(device)
+
+
+def _checked_tracers(tracers, b, who="RestrictedEnsemble"):
+    """tracers: None or (position[B,m,2], velocity[B,m,2]) float32 ([m,2] for one world) -> (m, position, velocity), contiguous
+    (m == 0: no tracers); ValueError for anything else."""
+    if tracers is None:
+        return 0, None, None
+    if not isinstance(tracers, (tuple, list)) or len(tracers) != 2:
+        raise ValueError(f"{who}: tracers must be a pair (position[B, m, 2], velocity[B, m, 2])")
+    tp, tv = np.asarray(tracers[0]), np.asarray(tracers[1])
+    for name, a in (("tracer position", tp), ("tracer velocity", tv)):
+        if a.dtype != np.float32:
+            raise ValueError(f"{who}: {name} must be float32 (got {a.dtype})")
+    if tp.ndim == 2 and b == 1:
+        tp = tp[None]
+        if tv.ndim == 2:
+            tv = tv[None]
+    if tp.ndim != 3 or tp.shape[2] != 2:
+        raise ValueError(f"{who}: tracer position must be [B, m, 2] (or [m, 2] for one world), got {tp.shape}")
+    if tv.shape != tp.shape:
+        raise ValueError(f"{who}: tracer velocity {tv.shape} does not match tracer position {tp.shape}")
+    if tp.shape[0] != b:
+        raise ValueError(f"{who}: tracers of {tp.shape[0]} worlds beside bodies of {b} worlds")
+    m = tp.shape[1]
+    if b * m > MAX_ROWS:
+        raise ValueError(f"{who}: worlds * tracers = {b * m} exceeds 2^26")
+    return m, np.ascontiguousarray(tp), np.ascontiguousarray(tv)
+
+
+class RestrictedEnsemble(_EnsembleBase):
+    """B worlds of n bodies and m tracers each, float32: position, velocity [B, n, 2], weight [B, n] integers or None (all 1),
+    tracers None or (position[B, m, 2], velocity[B, m, 2]).  Every update steps the bodies as `Ensemble` does, bit for bit, and
+    the tracers in the field of their own world's bodies at the pre-step positions."""
+    _dtype = np.float32
+
+    @staticmethod
+    def _new_handle(device):
+        return _capi.RestrictedHandle(device)
+
+    def __init__(self, position, velocity, weight=None, tracers=None, *, device=0, clamp=0.001, arith="auto"):
+        if arith not in _ARITH:
+            raise ValueError(f"arith must be one of {sorted(_ARITH)}")
+        self.h = None
+        args = _checked(position, velocity, weight, who="RestrictedEnsemble")
+        tr = _checked_tracers(tracers, args[0])
+        self.h = self._new_handle(device)
+        self.h.set_params(clamp=float(clamp), arith=_ARITH[arith])
+        self._upload(*args)
+        self._upload_tracers(*tr)
+
+    def _upload_tracers(self, m, tp, tv):
+        self.h.upload_tracers(self.h.shape[0], m, tp, tv)
+
+    def upload(self, position, velocity, weight=None, tracers=None):
+        """Replaces the worlds by others, of any shape; the previous tracers go with them."""
+        args = _checked(position, velocity, weight, who="RestrictedEnsemble")
+        tr = _checked_tracers(tracers, args[0])
+        self._upload(*args)
+        self._upload_tracers(*tr)
+
+    def set_tracers(self, tracers):
+        """Replaces the tracers: (position[B, m, 2], velocity[B, m, 2]); None, or m == 0, removes them."""
+        self._upload_tracers(*_checked_tracers(tracers, self.h.shape[0]))
+
+    @property
+    def shape(self):
+        """(worlds, bodies per world, tracers per world)."""
+        return (*self.h.shape, self.h.n_tracers)
+
+    def tracers(self):
+        """-> (position[B,m,2], velocity[B,m,2]) in upload order; rows never move."""
+        return self.h.download_tracers()
+
+    def tracers_accel(self):
+        """-> acc[B,m,2]: the accelerations at the tracers' current positions; the state is untouched."""
+        return self.h.tracers_accel()
 
 
 def _checked_ragged(positions, velocities, weights, dtype=np.float32):
