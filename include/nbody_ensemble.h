@@ -215,8 +215,8 @@ int nbody_ragged64_plan(int64_t n_worlds, const int64_t* n_bodies, int32_t* laun
  *     "restricted".  There is no CPU path: nbody_restricted_create fails with NBODY_ERR_NO_DEVICE without a gfx950 device.  A
  *     NULL handle gives NBODY_ERR_INVALID (0 from nbody_restricted_num_worlds / _num_bodies / _num_tracers);
  *     nbody_restricted_last_error(NULL): the last failed nbody_restricted_create on this thread, in a slot of its own.
- *   Not offered on this handle: f64, worlds of different sizes or a per-world n_tracers (follow-ups of their own, as f64 and
- *     ragged were for bodies); tree methods; several devices; snapshots, delta streams and frames; hipGraph replay.  The
+ *   Not offered on this handle: f64 (nbody_restricted64_* below is the double-precision sibling); worlds of different sizes
+ *     or a per-world n_tracers (a follow-up of its own, as ragged was for bodies); tree methods; several devices; snapshots, delta streams and frames; hipGraph replay.  The
  *     library reads no environment variable for any of this. */
 typedef struct nbody_restricted nbody_restricted;
 int nbody_restricted_create(nbody_restricted** out, int device_id);
@@ -236,5 +236,55 @@ int64_t nbody_restricted_num_tracers(const nbody_restricted* e);                
 int nbody_restricted_update_f32(nbody_restricted* e, float delta, int n_steps, nbody_counting* counter);
 int nbody_restricted_accel_f32(nbody_restricted* e, float* acc_xy);                           /* the bodies; state untouched */
 int nbody_restricted_tracers_accel_f32(nbody_restricted* e, float* acc_xy);                   /* the tracers; state untouched */
+
+/* ---- restricted ensembles in f64: double-precision tracers that step with each world, a handle of its own --------
+ * The restricted ensemble above in double precision — test particles that run for many orbits around a few massive bodies, where
+ * f32's 2^-24 per step is the error budget, not the force law.  Arrays, limits (1 <= n_bodies <= 4096, n_worlds * n_bodies <=
+ * 2^26, n_tracers >= 0 and the same for every world, n_worlds * n_tracers <= 2^26), the two launches per step, lifetime, booking,
+ * params, trivial calls and errors are as stated there, the messages naming "restricted"; no CPU path
+ * (nbody_restricted64_create fails with NBODY_ERR_NO_DEVICE without a gfx950 device); NULL handle (NBODY_ERR_INVALID; 0 from
+ * nbody_restricted64_num_worlds / _num_bodies / _num_tracers; nbody_restricted64_last_error(NULL): the last failed
+ * nbody_restricted64_create on this thread — a slot of its own, apart from nbody_restricted_*'s and nbody_ensemble64_*'s).
+ *   Bodies.  Every world's bodies take the step of nbody_ensemble64_update, from the same kernel and launch: they are
+ *     bit-identical to an nbody_ensemble64 holding the same worlds, under every arith, with or without tracers.
+ *   Tracers.  a_t = sum_j calculate_gravity(p_t, p_j, w_j as f64) over the bodies of the tracer's own world at their pre-step
+ *     positions, j ascending, the pair of main.rs:234-253 in T = double with the clamp params.clamp widened to double; no mass
+ *     and no self term; then main.rs:419-423 in double, multiply then add, no contraction.  Tracer rows never move.
+ *   EXACT and AUTO.  One ascending-row chain of IEEE additions per tracer (two correctly rounded divisions per pair, the
+ *     is_normal skip): bit-identical to the CPU restatement's direct_accel at the tracers (native accumulation) on float64
+ *     followed by that Euler step, and to an f64 context of that world alone with the tracers of nbody_tracers_upload_f64 under
+ *     EXACT.  AUTO is EXACT, as it is for nbody_ensemble64_* and for an f64 context.
+ *   FAST (opt-in).  |a - a_ref|_1 <= 1e-12 * sum_j |term_j|_1 per tracer: v_rcp_f64 plus one Newton step, fused
+ *     multiply-adds, the 2^-700 biased denominator.  One lane per tracer, whatever n_bodies is: the order of additions is the
+ *     one nbody_ensemble64_*'s bodies have for n_bodies > 128 (runs of 64 sources, two fma chains per run, the runs added in
+ *     order) — a function of n_bodies alone; for n_bodies > 128 a tracer that sits exactly on a body gets that body's FAST
+ *     acceleration bit for bit.  Routed per world and per step on the device, without a flag buffer: a world with a body
+ *     position outside the f64 FAST domain (non-finite, >= 2^100 in magnitude, or non-zero below 2^-300) at the start of a step
+ *     has its bodies and all its tracers take EXACT for that step.  In a FAST world a tracer whose own pre-step position is
+ *     outside that domain takes its EXACT value for that step; its neighbours keep their FAST bits.  With a clamp that is not
+ *     > 0, or NaN, everything takes EXACT.
+ *   Independence.  A tracer's bits depend on its own state, its world's bodies, n_bodies and the params — not on n_tracers, its
+ *     slot, n_worlds, its world's index, the other worlds, or how the steps are split over calls.
+ *   Staging.  A tracer block stages its world as a body block does: 80 KB of LDS at n_bodies = 4096 and no other LDS.
+ *   Not offered on this handle: worlds of different sizes or a per-world n_tracers, tracers on several devices, and what the
+ *     restricted ensemble above does not offer either. */
+typedef struct nbody_restricted64 nbody_restricted64;
+int nbody_restricted64_create(nbody_restricted64** out, int device_id);
+void nbody_restricted64_destroy(nbody_restricted64* e);
+const char* nbody_restricted64_last_error(const nbody_restricted64* e);
+int nbody_restricted64_set_params(nbody_restricted64* e, const nbody_params* p);
+int nbody_restricted64_get_params(const nbody_restricted64* e, nbody_params* out);
+int nbody_restricted64_upload(nbody_restricted64* e, int64_t n_worlds, int64_t n_bodies, const double* pos_xy, const double* vel_xy,
+                              const uint32_t* weight);
+int nbody_restricted64_download(nbody_restricted64* e, double* pos_xy, double* vel_xy);         /* the bodies; either may be NULL */
+int nbody_restricted64_tracers_upload(nbody_restricted64* e, int64_t n_worlds, int64_t n_tracers, const double* pos_xy,
+                                      const double* vel_xy);
+int nbody_restricted64_tracers_download(nbody_restricted64* e, double* pos_xy, double* vel_xy); /* either may be NULL */
+int64_t nbody_restricted64_num_worlds(const nbody_restricted64* e);
+int64_t nbody_restricted64_num_bodies(const nbody_restricted64* e);                             /* per world */
+int64_t nbody_restricted64_num_tracers(const nbody_restricted64* e);                            /* per world */
+int nbody_restricted64_update(nbody_restricted64* e, double delta, int n_steps, nbody_counting* counter);
+int nbody_restricted64_accel(nbody_restricted64* e, double* acc_xy);                            /* the bodies; state untouched */
+int nbody_restricted64_tracers_accel(nbody_restricted64* e, double* acc_xy);                    /* the tracers; state untouched */
 
 #endif /* NBODY_ENSEMBLE_H */

@@ -151,6 +151,21 @@ _SIGS = {
     "nbody_restricted_update_f32": (C.c_int, [_vp, _f32, _i32, C.POINTER(Counting)]),
     "nbody_restricted_accel_f32": (C.c_int, [_vp, _vp]),
     "nbody_restricted_tracers_accel_f32": (C.c_int, [_vp, _vp]),
+    "nbody_restricted64_create": (C.c_int, [C.POINTER(_vp), _i32]),
+    "nbody_restricted64_destroy": (None, [_vp]),
+    "nbody_restricted64_last_error": (C.c_char_p, [_vp]),
+    "nbody_restricted64_set_params": (C.c_int, [_vp, C.POINTER(Params)]),
+    "nbody_restricted64_get_params": (C.c_int, [_vp, C.POINTER(Params)]),
+    "nbody_restricted64_upload": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    "nbody_restricted64_download": (C.c_int, [_vp, _vp, _vp]),
+    "nbody_restricted64_tracers_upload": (C.c_int, [_vp, _i64, _i64, _vp, _vp]),
+    "nbody_restricted64_tracers_download": (C.c_int, [_vp, _vp, _vp]),
+    "nbody_restricted64_num_worlds": (_i64, [_vp]),
+    "nbody_restricted64_num_bodies": (_i64, [_vp]),
+    "nbody_restricted64_num_tracers": (_i64, [_vp]),
+    "nbody_restricted64_update": (C.c_int, [_vp, _f64, _i32, C.POINTER(Counting)]),
+    "nbody_restricted64_accel": (C.c_int, [_vp, _vp]),
+    "nbody_restricted64_tracers_accel": (C.c_int, [_vp, _vp]),
     "nbody_accel_tree_f32": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_accel_tree_f64": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_tree_info": (C.c_int, [_vp, C.POINTER(TreeView)]),
@@ -954,9 +969,9 @@ class Ragged64Handle(RaggedHandle):
     _prefix, _suffix, _dtype = "nbody_ragged64", "", np.float64
 
 
-class RestrictedHandle(EnsembleHandle):
-    """nbody_restricted_*: float32 worlds of one size with m tracers each; the bodies' calls are EnsembleHandle's."""
-    _prefix = "nbody_restricted"
+class _TracerCalls:
+    """The tracer calls of a restricted handle, beside the bodies' calls of the ensemble handle it is mixed into: m tracers per
+    world in arrays of the handle's `_dtype`, the typed C calls with its `_suffix`."""
 
     @property
     def n_tracers(self):
@@ -964,19 +979,30 @@ class RestrictedHandle(EnsembleHandle):
         return int(self._call("_num_tracers"))
 
     def upload_tracers(self, n_worlds, n_tracers, pos, vel):
-        """pos, vel [n_worlds, n_tracers, 2] float32, contiguous; n_tracers == 0 removes the tracers."""
-        self._check(self._call("_tracers_upload_f32", int(n_worlds), int(n_tracers), _ptr(pos), _ptr(vel)))
+        """pos, vel [n_worlds, n_tracers, 2] of the handle's dtype, contiguous; n_tracers == 0 removes the tracers."""
+        self._check(self._call("_tracers_upload" + self._suffix, int(n_worlds), int(n_tracers), _ptr(pos), _ptr(vel)))
 
     def download_tracers(self):
         b, m = self.shape[0], self.n_tracers
-        pos, vel = np.zeros((b, m, 2), np.float32), np.zeros((b, m, 2), np.float32)
-        self._check(self._call("_tracers_download_f32", _ptr(pos), _ptr(vel)))
+        pos, vel = np.zeros((b, m, 2), self._dtype), np.zeros((b, m, 2), self._dtype)
+        self._check(self._call("_tracers_download" + self._suffix, _ptr(pos), _ptr(vel)))
         return pos, vel
 
     def tracers_accel(self):
-        acc = np.zeros((self.shape[0], self.n_tracers, 2), np.float32)
-        self._check(self._call("_tracers_accel_f32", _ptr(acc)))
+        acc = np.zeros((self.shape[0], self.n_tracers, 2), self._dtype)
+        self._check(self._call("_tracers_accel" + self._suffix, _ptr(acc)))
         return acc
+
+
+class RestrictedHandle(_TracerCalls, EnsembleHandle):
+    """nbody_restricted_*: float32 worlds of one size with m tracers each; the bodies' calls are EnsembleHandle's."""
+    _prefix = "nbody_restricted"
+
+
+class Restricted64Handle(_TracerCalls, Ensemble64Handle):
+    """nbody_restricted64_*: float64 worlds of one size with m tracers each, the sibling of RestrictedHandle; the bodies' calls
+    are Ensemble64Handle's."""
+    _prefix = "nbody_restricted64"
 
 
 RAGGED_MAX_LAUNCHES = 6

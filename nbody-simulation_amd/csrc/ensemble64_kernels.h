@@ -17,6 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 #include "ensemble_kernels.h"
 
 namespace nbody {
@@ -46,5 +48,10 @@ hipError_t launch_ensemble64_step(hipStream_t s, int64_t n_worlds, Ensemble64Arg
 // dynamic-LDS limit is raised, once per device); n_bodies and tiles of `a` are not read.  Every world computes exactly what
 // launch_ensemble64_step computes for a world of its size.
 hipError_t launch_ensemble64_step_ragged(hipStream_t s, int64_t blocks, size_t lds_bytes, const uint2* items, Ensemble64Args a);
+
+// Raises `kernel`'s limit of dynamic LDS to ensemble64_lds_bytes(kEnsembleMaxBodies), once per device: `raised` is that
+// function's own zero-initialised table of 64 (a raised limit covers one function, so every kernel that stages a world of more
+// than 64 KB keeps a table: the two above, and the tracers' kernel of restricted64_kernels.h).
+hipError_t ens64_raise_lds_limit(const void* kernel, std::atomic<bool>* raised);
 
 }  // namespace nbody

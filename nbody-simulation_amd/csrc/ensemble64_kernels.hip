@@ -30,90 +30,41 @@
 //        each of the world's blocks.  No flag buffer, no extra kernel, nothing read back.  The OR goes through one borrowed
 //        word of the staged weights and plain barriers, not __syncthreads_or: the kernel has no static LDS at all.
 //
+// The staging, the EXACT chain and the FAST sum are written once in ensemble64_world.h, which the tracers' kernel of the
+// restricted ensemble (restricted64_kernels.hip) runs too.
+//
 // This translation unit is compiled with -ffp-contract=off: nothing fuses unless written as an fma.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
-
 #include "../../include/nbody_hip.h"
 #include "ensemble64_kernels.h"
-#include "ensemble_device.h"
-#include "fast_domain.h"
-#include "pair.h"
+#include "ensemble64_world.h"
 
 namespace nbody {
 namespace {
 
-constexpr int kEns64Run = 64;  // sources of one lane summed on their own before they join its total
-
 // What a block computes: one tile of the targets of the world whose rows are row0 .. row0 + n — its sources staged in LDS with
-// FAST's decision taken on the way, then the EXACT or the FAST arm.  A function of the world through (n, row0, tile) alone: the
-// uniform kernel and the ragged one share it, and with it every bit.  Every thread of the block calls it (it holds barriers).
+// FAST's decision taken on the way, then the EXACT or the FAST arm, all three from ensemble64_world.h.  A function of the world
+// through (n, row0, tile) alone: the uniform kernel and the ragged one share it, and with it every bit.  Every thread of the
+// block calls it (it holds barriers).
 template <int SPLIT>
 __device__ __forceinline__ void ens64_world_tile(const Ensemble64Args& a, const int n, const size_t row0, const unsigned tile) {
   constexpr int TPB = kEnsembleBlock / SPLIT;  // targets per block
-  constexpr int TB = kEns64TermBlock;
   extern __shared__ __attribute__((aligned(16))) unsigned char ens64_lds[];
-  const int npad = (n + TB - 1) / TB * TB;
-  double2* const spos = reinterpret_cast<double2*>(ens64_lds);
-  uint32_t* const sw = reinterpret_cast<uint32_t*>(spos + npad);
-
-  // ---- the world's sources into LDS, and FAST's decision on the way
-  int bad = 0;
-  uint32_t w0 = 0;  // thread 0: the weight of source 0, whose LDS word carries the world's decision before it carries the weight
-  for (int s = (int)threadIdx.x; s < npad; s += kEnsembleBlock) {
-    double2 p = double2{__builtin_nan(""), __builtin_nan("")};
-    uint32_t w = 0;
-    if (s < n) {
-      p = a.pos_in[row0 + s];
-      w = a.weight[row0 + s];
-      bad |= (int)outside_fast(p.x) | (int)outside_fast(p.y);
-    }
-    if (a.fast && s == 0) {
-      w0 = w;
-      w = 0;
-    }
-    spos[s] = p;
-    sw[s] = w;
-  }
-  __syncthreads();
-  // The block-wide OR without __syncthreads_or: its reduction takes 256 B of static LDS, and 2 x 81 920 B of dynamic LDS are
-  // the CU's 160 KiB to the byte.  So sw[0] is borrowed: 0 from the staging, 1 from every wave that saw a position outside the
-  // domain (the same value, whoever writes), read by all, then given its weight.  (a.fast is uniform: every thread takes the
-  // same barriers.)
-  int hazard = 1;
-  if (a.fast) {
-    if (__builtin_amdgcn_ballot_w64(bad != 0) != 0 && (threadIdx.x & 63) == 0) sw[0] = 1u;
-    __syncthreads();
-    hazard = (int)sw[0];
-    __syncthreads();
-    if (threadIdx.x == 0) sw[0] = w0;
-    __syncthreads();
-  }
+  const Ens64WorldLds w(ens64_lds, n);
+  const int hazard = ens64_stage_world(w, a.pos_in, a.weight, row0, a.fast);
   const double clamp = a.clamp;
+  double px[1], py[1], ax[1], ay[1];
 
   if (hazard) {
-    // ---- EXACT: thread = target, term blocks in ascending j (no barrier follows: threads without a target leave)
+    // ---- EXACT: thread = target (no barrier follows: threads without a target leave)
     if ((int)threadIdx.x >= TPB) return;
     const int t = (int)tile * TPB + (int)threadIdx.x;
     if (t >= n) return;
-    const double2 p = spos[t];
-    double ax = 0.0, ay = 0.0;
-    for (int k0 = 0; k0 < npad; k0 += TB) {
-      double2 term[TB];
-#pragma unroll
-      for (int jj = 0; jj < TB; ++jj) {  // any order of evaluation ...
-        const double2 q = spos[k0 + jj];
-        term[jj] = pair_term_select(p.x, p.y, q.x, q.y, (double)sw[k0 + jj], clamp);
-      }
-#pragma unroll
-      for (int jj = 0; jj < TB; ++jj) {  // ... one order of addition: ascending j
-        ax = ax + term[jj].x;
-        ay = ay + term[jj].y;
-      }
-    }
-    ens_integrate(a, row0 + t, p.x, p.y, ax, ay);
+    const double2 p = w.spos[t];
+    ens64_exact_sum(w, p.x, p.y, clamp, ax[0], ay[0]);
+    ens_integrate(a, row0 + t, p.x, p.y, ax[0], ay[0]);
     return;
   }
 
@@ -121,30 +72,10 @@ __device__ __forceinline__ void ens64_world_tile(const Ensemble64Args& a, const 
   const int part = (int)threadIdx.x % SPLIT;
   const int t = (int)tile * TPB + (int)threadIdx.x / SPLIT;
   const bool live = t < n;
-  const double2 p = spos[live ? t : 0];
-  const int cnt = (n - part + SPLIT - 1) / SPLIT;  // this lane's sources: part + k * SPLIT, k < cnt
-  double ax = 0.0, ay = 0.0;
-  for (int k0 = 0; k0 < cnt; k0 += kEns64Run) {
-    const int k1 = k0 + kEns64Run < cnt ? k0 + kEns64Run : cnt;
-    double x0 = 0.0, y0 = 0.0, x1 = 0.0, y1 = 0.0;
-    int s = part + k0 * SPLIT;
-    const int s1 = part + k1 * SPLIT;
-#pragma unroll 2
-    for (; s + SPLIT < s1; s += 2 * SPLIT) {
-      const double2 qa = spos[s], qb = spos[s + SPLIT];
-      pair_fast(p.x, p.y, qa.x, qa.y, (double)sw[s], clamp, x0, y0);
-      pair_fast(p.x, p.y, qb.x, qb.y, (double)sw[s + SPLIT], clamp, x1, y1);
-    }
-    if (s < s1) {
-      const double2 qa = spos[s];
-      pair_fast(p.x, p.y, qa.x, qa.y, (double)sw[s], clamp, x0, y0);
-    }
-    ax = ax + (x0 + x1);
-    ay = ay + (y0 + y1);
-  }
-  ax = ens_group_sum<SPLIT>(ax);
-  ay = ens_group_sum<SPLIT>(ay);
-  if (live && part == 0) ens_integrate(a, row0 + t, p.x, p.y, ax, ay);
+  const double2 p = w.spos[live ? t : 0];
+  px[0] = p.x, py[0] = p.y;
+  ens64_fast_sum<SPLIT, 1>(w, part, px, py, clamp, ax, ay);
+  if (live && part == 0) ens_integrate(a, row0 + t, p.x, p.y, ax[0], ay[0]);
 }
 
 template <int SPLIT>
@@ -174,6 +105,8 @@ __global__ __launch_bounds__(kEnsembleBlock) void ensemble64_step_ragged(const E
   }
 }
 
+}  // namespace
+
 // Dynamic LDS above 64 KB (n > 3272: rows are padded to 8 and 3280 x 20 B = 65 600; the one-target-per-lane layout only) needs
 // the function's limit raised: once per device and per function (`raised` is that function's own table, zero-initialised).
 hipError_t ens64_raise_lds_limit(const void* kernel, std::atomic<bool>* raised) {
@@ -185,8 +118,6 @@ hipError_t ens64_raise_lds_limit(const void* kernel, std::atomic<bool>* raised) 
   if (h == hipSuccess && dev >= 0 && dev < 64) raised[dev] = true;
   return h;
 }
-
-}  // namespace
 
 hipError_t launch_ensemble64_step(hipStream_t s, int64_t n_worlds, Ensemble64Args a) {
   if (n_worlds < 1 || a.n_bodies < 1 || a.n_bodies > kEnsembleMaxBodies || n_worlds * a.n_bodies > kEnsembleMaxRows) return hipErrorInvalidValue;

@@ -22,6 +22,9 @@ sibling, float64 arrays only: EXACT and AUTO bit-identical to the oracle's updat
 own world's bodies and nothing else: the restricted problem under many seeds.  The bodies are bit-identical to an `Ensemble` of
 the same worlds; a tracer is EXACT bit-identical to the oracle's direct_accel at it + Euler, FAST within the tolerance of
 DESIGN.md, AUTO per world and per step on the device with a per-tracer exception for a tracer outside FAST's domain.
+`RestrictedEnsemble64` (nbody_restricted64_*) is its double-precision sibling, float64 arrays only: the bodies are bit-identical
+to an `Ensemble64` of the same worlds; a tracer is EXACT (and AUTO) bit-identical to the oracle's direct_accel at it + Euler on
+float64, FAST (opt-in, per world and per step on the device, with the same per-tracer exception) within 1e-12 of sum |term|.
 """
 from __future__ import annotations
 
@@ -36,13 +39,14 @@ MAX_ROWS = 1 << 26         # worlds * bodies
 _ARITH = {"auto": _capi.ARITH_AUTO, "fast": _capi.ARITH_FAST, "exact": _capi.ARITH_EXACT}
 
 
-def _checked(position, velocity, weight, dtype=np.float32, who=None):
+def _checked(position, velocity, weight, dtype=np.float32, who=None, other=None):
     """-> (B, n, position[B,n,2], velocity[B,n,2], weight[B,n] or None), contiguous; ValueError for anything else.  The
-    messages name `who`, or the class of that dtype: Ensemble (float32) or Ensemble64 (float64)."""
+    messages name `who`, or the class of that dtype: Ensemble (float32) or Ensemble64 (float64); a wrong dtype adds `other`, or
+    which of those two takes the other one."""
     position, velocity = np.asarray(position), np.asarray(velocity)
     dtype = np.dtype(dtype)
-    name, other = ("Ensemble", "Ensemble64 takes float64") if dtype == np.float32 else ("Ensemble64", "Ensemble takes float32")
-    who = who or name
+    name, sibling = ("Ensemble", "Ensemble64 takes float64") if dtype == np.float32 else ("Ensemble64", "Ensemble takes float32")
+    who, other = who or name, other or sibling
     for name, a in (("position", position), ("velocity", velocity)):
         if a.dtype != dtype:
             raise ValueError(f"{who}: {name} must be {dtype} (got {a.dtype}); {other}")
@@ -74,7 +78,7 @@ def _checked(position, velocity, weight, dtype=np.float32, who=None):
 
 
 class _EnsembleBase:
-    """What Ensemble, Ensemble64 and RestrictedEnsemble share; each names its dtype and makes its own kind of handle."""
+    """What Ensemble, Ensemble64 and the restricted ensembles share; each names its dtype and makes its own kind of handle."""
     _dtype = None
 
     @staticmethod
@@ -151,17 +155,19 @@ class Ensemble64(_EnsembleBase):
         return _capi.Ensemble64Handle(device)
 
 
-def _checked_tracers(tracers, b, who="RestrictedEnsemble"):
-    """tracers: None or (position[B,m,2], velocity[B,m,2]) float32 ([m,2] for one world) -> (m, position, velocity), contiguous
+def _checked_tracers(tracers, b, who="RestrictedEnsemble", dtype=np.float32):
+    """tracers: None or (position[B,m,2], velocity[B,m,2]) of `dtype` ([m,2] for one world) -> (m, position, velocity), contiguous
     (m == 0: no tracers); ValueError for anything else."""
     if tracers is None:
         return 0, None, None
     if not isinstance(tracers, (tuple, list)) or len(tracers) != 2:
         raise ValueError(f"{who}: tracers must be a pair (position[B, m, 2], velocity[B, m, 2])")
     tp, tv = np.asarray(tracers[0]), np.asarray(tracers[1])
+    dtype = np.dtype(dtype)
+    other = "" if dtype == np.float32 else "; RestrictedEnsemble takes float32"
     for name, a in (("tracer position", tp), ("tracer velocity", tv)):
-        if a.dtype != np.float32:
-            raise ValueError(f"{who}: {name} must be float32 (got {a.dtype})")
+        if a.dtype != dtype:
+            raise ValueError(f"{who}: {name} must be {dtype} (got {a.dtype}){other}")
     if tp.ndim == 2 and b == 1:
         tp = tp[None]
         if tv.ndim == 2:
@@ -178,22 +184,21 @@ def _checked_tracers(tracers, b, who="RestrictedEnsemble"):
     return m, np.ascontiguousarray(tp), np.ascontiguousarray(tv)
 
 
-class RestrictedEnsemble(_EnsembleBase):
-    """B worlds of n bodies and m tracers each, float32: position, velocity [B, n, 2], weight [B, n] integers or None (all 1),
-    tracers None or (position[B, m, 2], velocity[B, m, 2]).  Every update steps the bodies as `Ensemble` does, bit for bit, and
-    the tracers in the field of their own world's bodies at the pre-step positions."""
-    _dtype = np.float32
+class _RestrictedBase(_EnsembleBase):
+    """What RestrictedEnsemble and RestrictedEnsemble64 share: the tracers beside the bodies.  Each names its dtype, makes its own
+    kind of handle and says which class takes the other dtype."""
+    _other = None
 
-    @staticmethod
-    def _new_handle(device):
-        return _capi.RestrictedHandle(device)
+    def _check(self, position, velocity, weight, tracers):
+        who = type(self).__name__
+        args = _checked(position, velocity, weight, self._dtype, who=who, other=self._other)
+        return args, _checked_tracers(tracers, args[0], who, self._dtype)
 
     def __init__(self, position, velocity, weight=None, tracers=None, *, device=0, clamp=0.001, arith="auto"):
         if arith not in _ARITH:
             raise ValueError(f"arith must be one of {sorted(_ARITH)}")
         self.h = None
-        args = _checked(position, velocity, weight, who="RestrictedEnsemble")
-        tr = _checked_tracers(tracers, args[0])
+        args, tr = self._check(position, velocity, weight, tracers)
         self.h = self._new_handle(device)
         self.h.set_params(clamp=float(clamp), arith=_ARITH[arith])
         self._upload(*args)
@@ -204,14 +209,13 @@ class RestrictedEnsemble(_EnsembleBase):
 
     def upload(self, position, velocity, weight=None, tracers=None):
         """Replaces the worlds by others, of any shape; the previous tracers go with them."""
-        args = _checked(position, velocity, weight, who="RestrictedEnsemble")
-        tr = _checked_tracers(tracers, args[0])
+        args, tr = self._check(position, velocity, weight, tracers)
         self._upload(*args)
         self._upload_tracers(*tr)
 
     def set_tracers(self, tracers):
         """Replaces the tracers: (position[B, m, 2], velocity[B, m, 2]); None, or m == 0, removes them."""
-        self._upload_tracers(*_checked_tracers(tracers, self.h.shape[0]))
+        self._upload_tracers(*_checked_tracers(tracers, self.h.shape[0], type(self).__name__, self._dtype))
 
     @property
     def shape(self):
@@ -225,6 +229,30 @@ class RestrictedEnsemble(_EnsembleBase):
     def tracers_accel(self):
         """-> acc[B,m,2]: the accelerations at the tracers' current positions; the state is untouched."""
         return self.h.tracers_accel()
+
+
+class RestrictedEnsemble(_RestrictedBase):
+    """B worlds of n bodies and m tracers each, float32: position, velocity [B, n, 2], weight [B, n] integers or None (all 1),
+    tracers None or (position[B, m, 2], velocity[B, m, 2]).  Every update steps the bodies as `Ensemble` does, bit for bit, and
+    the tracers in the field of their own world's bodies at the pre-step positions."""
+    _dtype = np.float32
+
+    @staticmethod
+    def _new_handle(device):
+        return _capi.RestrictedHandle(device)
+
+
+class RestrictedEnsemble64(_RestrictedBase):
+    """The restricted ensemble in double precision: the same constructor and methods, float64 arrays only.  Every update steps
+    the bodies as `Ensemble64` does, bit for bit, and the tracers in double: arith "auto" and "exact" are the exact chain, "fast"
+    is opt-in and gated per world and per step on the device, with a per-tracer exception for a tracer outside FAST's domain;
+    clamp is a float, widened to double by the library."""
+    _dtype = np.float64
+    _other = "RestrictedEnsemble takes float32"
+
+    @staticmethod
+    def _new_handle(device):
+        return _capi.Restricted64Handle(device)
 
 
 def _checked_ragged(positions, velocities, weights, dtype=np.float32):

@@ -2,7 +2,7 @@
 """Restricted ensemble against a loop over contexts with tracers: the same worlds, the same steps, the same GPU, the same process.
 
     python tools/restricted_bench.py [--out FILE] [--shapes 256x2x4096,256x64x4096,64x1024x16384] [--steps 20] [--reps 3]
-                                     [--leg-timeout 240]
+                                     [--leg-timeout 240] [--dtype f32|f64]
 
 For every shape B x n x m (worlds x bodies x tracers per world) and for FAST and EXACT arithmetic one LEG runs once, in a child
 process of its own under its own time limit (a leg that fails or runs out of time is reported as such and the others still run):
@@ -15,6 +15,8 @@ in a synchronise of its stream (the method of tools/ensemble_bench.py, DESIGN.md
 fastest timed call; the condition per leg is that the restricted call beats the loop's median by more than that.  The pair rate
 is B * (n^2 + m*n) * steps pairs per restricted call — all body-body and tracer-body pairs — at 14 flop per pair
 against the 157.3 TFLOP/s f32 peak: an end-to-end figure of the call, launches and synchronise included, not a kernel's.
+--dtype f64 measures nb.RestrictedEnsemble64 against f64 contexts with f64 tracers, the rate against the 78.6 TFLOP/s f64 vector
+peak (AMD's public figure for the part); the default, f32, is the measurement described above.
 This is a tool, not a test: it needs an MI355X and fails without one.
 """
 import argparse
@@ -29,25 +31,27 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 PEAK_F32 = 157.3e12
+PEAK_F64 = 78.6e12    # vector f64, AMD's public figure
 FLOP_PER_PAIR = 14
 MAX_CONTEXTS = 256
 
 
-def leg(b, n, m, arith, steps, reps):
+def leg(b, n, m, arith, steps, reps, f64=False):
     import numpy as np
     import nbody_simulation_amd as nb
     C = nb._capi
-    worlds = [nb.scenes.plummer(n, seed=0xE5E0000 + k) for k in range(b)]
-    pos = np.stack([w[0] for w in worlds]).astype(np.float32)
-    vel = np.stack([w[1] for w in worlds]).astype(np.float32)
+    dt = np.float64 if f64 else np.float32
+    worlds = [nb.scenes.plummer(n, seed=0xE5E0000 + k, dtype=dt) for k in range(b)]
+    pos = np.stack([w[0] for w in worlds]).astype(dt)
+    vel = np.stack([w[1] for w in worlds]).astype(dt)
     wgt = np.stack([w[2] for w in worlds])
     rng = np.random.default_rng(0x7ACE)
     lo, hi = pos.min(axis=1, keepdims=True), pos.max(axis=1, keepdims=True)
     if n == 1:
         lo, hi = lo - 100.0, hi + 100.0
-    tp = (lo + (hi - lo) * rng.random((b, m, 2))).astype(np.float32)   # tracers over their world's box
-    tv = rng.normal(0, 1, (b, m, 2)).astype(np.float32)
-    rst = nb.RestrictedEnsemble(pos, vel, wgt, (tp, tv), arith=arith)
+    tp = (lo + (hi - lo) * rng.random((b, m, 2))).astype(dt)   # tracers over their world's box
+    tv = rng.normal(0, 1, (b, m, 2)).astype(dt)
+    rst = (nb.RestrictedEnsemble64 if f64 else nb.RestrictedEnsemble)(pos, vel, wgt, (tp, tv), arith=arith)
     nctx = min(b, MAX_CONTEXTS)
     rounds = (b + nctx - 1) // nctx
     ctxs = []
@@ -78,7 +82,8 @@ def leg(b, n, m, arith, steps, reps):
     for c in ctxs:
         c.close()
     rst.close()
-    return dict(b=b, n=n, m=m, arith=arith, steps=steps, contexts=nctx, rounds=rounds, restricted_s=tr, contexts_s=tc)
+    return dict(b=b, n=n, m=m, arith=arith, dtype="f64" if f64 else "f32", steps=steps, contexts=nctx, rounds=rounds, restricted_s=tr,
+                contexts_s=tc)
 
 
 def main():
@@ -88,25 +93,28 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--leg-timeout", type=float, default=240.0)
+    ap.add_argument("--dtype", choices=("f32", "f64"), default="f32")
     ap.add_argument("--leg", help=argparse.SUPPRESS)   # BxNxM:arith — the child process of one leg
     a = ap.parse_args()
     if a.leg:
         shape, arith = a.leg.split(":")
         b, n, m = (int(v) for v in shape.split("x"))
-        print("LEG " + json.dumps(leg(b, n, m, arith, a.steps, a.reps)), flush=True)
+        print("LEG " + json.dumps(leg(b, n, m, arith, a.steps, a.reps, f64=a.dtype == "f64")), flush=True)
         return 0
     if not os.path.exists("/dev/kfd"):
         print("restricted_bench: no GPU here; a measurement path does not fall back", file=sys.stderr)
         return 2
-    lines = [f"# tools/restricted_bench.py: steps per call {a.steps}, timed calls per side {a.reps} (alternating, after one warm-up call each)",
+    peak = PEAK_F64 if a.dtype == "f64" else PEAK_F32
+    lines = [f"# tools/restricted_bench.py{' --dtype f64' if a.dtype == 'f64' else ''}: steps per call {a.steps}, timed calls per side {a.reps} (alternating, after one warm-up call each)",
              "# shape = worlds x bodies x tracers per world; seconds are host-clock times of one whole call (it ends in a stream synchronise)",
              "# ratio = contexts / restricted (medians); spread = the loop's slowest - fastest timed call; gain = contexts median - restricted median",
-             f"# rate = B*(n^2 + m*n)*steps pairs per restricted call * {FLOP_PER_PAIR} flop over the median time, as a share of {PEAK_F32 / 1e12:.1f} TFLOP/s (end to end)",
+             f"# rate = B*(n^2 + m*n)*steps pairs per restricted call * {FLOP_PER_PAIR} flop over the median time, as a share of {peak / 1e12:.1f} TFLOP/s (end to end)",
              f"{'shape':>14} {'arith':>6} {'restricted_s (each call)':>34} {'contexts_s (each call)':>34} {'ratio':>7} {'gain_s':>9} {'spread_s':>9} {'TFLOP/s':>8} {'of peak':>8}"]
     missed = []
     for shape in a.shapes.split(","):
         for arith in ("fast", "exact"):
-            cmd = [sys.executable, os.path.abspath(__file__), "--leg", f"{shape}:{arith}", "--steps", str(a.steps), "--reps", str(a.reps)]
+            cmd = [sys.executable, os.path.abspath(__file__), "--leg", f"{shape}:{arith}", "--steps", str(a.steps), "--reps", str(a.reps),
+                   "--dtype", a.dtype]
             try:
                 r = subprocess.run(cmd, capture_output=True, text=True, timeout=a.leg_timeout)
             except subprocess.TimeoutExpired:
@@ -128,7 +136,7 @@ def main():
             if not mc - mr > spread:
                 missed.append(f"{shape} {arith}")
             lines.append(f"{shape:>14} {arith:>6} {' '.join(f'{t:.5f}' for t in d['restricted_s']):>34} {' '.join(f'{t:.5f}' for t in d['contexts_s']):>34} "
-                         f"{mc / mr:7.2f} {mc - mr:9.5f} {spread:9.5f} {flops / 1e12:8.2f} {100 * flops / PEAK_F32:7.1f}%"
+                         f"{mc / mr:7.2f} {mc - mr:9.5f} {spread:9.5f} {flops / 1e12:8.2f} {100 * flops / peak:7.1f}%"
                          + (f"   ({d['contexts']} contexts x {d['rounds']} rounds)" if d["rounds"] > 1 else ""))
         else:
             continue
