@@ -5,7 +5,7 @@
 //
 // P supplies: Real, Vec2 (the element types), Mass (what the device keeps per body), Args (the kernel's arguments);
 //   kCreate                        the create call's name, the prefix of its messages;
-//   kWho                           the word that every other message of the handle begins with ("ensemble", "ragged");
+//   kWho                           the word that every other message of the handle begins with ("ensemble", "ragged", "restricted");
 //   stage(weight, rows, tmp)       -> the rows Mass values to upload (tmp is theirs to fill);
 //   route(args, mass, params)      the masses and the arithmetic of a launch, from the handle's parameters;
 //   launch(stream, n_worlds, args) one step, or one force evaluation, of all worlds.
@@ -13,6 +13,8 @@
 // The ragged handle (ragged_driver.h: worlds of different sizes, several launches per step) is built from the same parts: the
 // state, create / destroy, params and errors as they are, and upload, download, update and accel through the *_rows / *_with
 // functions below, which take the number of rows and the step's launches from their caller.
+// The restricted handle (restricted_driver.h: tracers beside the bodies, a second launch per step) is the whole of this driver
+// under its own kWho, with the tracers' launch added to a step through ens_update_with.
 #pragma once
 #include <cstring>
 #include <new>
@@ -154,19 +156,33 @@ int ens_store_rows(EnsembleState<P>* e, int64_t n_rows, const typename P::Real* 
   return NBODY_OK;
 }
 
+// What an upload of worlds of one size refuses, before the handle is touched.
 template <class P>
-int ens_upload(EnsembleState<P>* e, int64_t n_worlds, int64_t n_bodies, const typename P::Real* pos, const typename P::Real* vel,
-               const uint32_t* weight) {
+int ens_upload_check(EnsembleState<P>* e, int64_t n_worlds, int64_t n_bodies, const typename P::Real* pos, const typename P::Real* vel) {
   if (!e) return NBODY_ERR_INVALID;
   if (n_bodies < 1 || n_bodies > kEnsembleMaxBodies)
-    return ens_fail(e, NBODY_ERR_INVALID, "ensemble upload: n_bodies must be 1 .. 4096 (above that a context per world is the tool)");
+    return ens_fail(e, NBODY_ERR_INVALID, std::string(P::kWho) + " upload: n_bodies must be 1 .. 4096 (above that a context per world is the tool)");
   if (n_worlds < 1 || n_worlds > kEnsembleMaxRows / n_bodies)
-    return ens_fail(e, NBODY_ERR_INVALID, "ensemble upload: n_worlds must be >= 1 and n_worlds * n_bodies <= 2^26");
-  if (!pos || !vel) return ens_fail(e, NBODY_ERR_INVALID, "ensemble upload: pos_xy or vel_xy is NULL");
+    return ens_fail(e, NBODY_ERR_INVALID, std::string(P::kWho) + " upload: n_worlds must be >= 1 and n_worlds * n_bodies <= 2^26");
+  if (!pos || !vel) return ens_fail(e, NBODY_ERR_INVALID, std::string(P::kWho) + " upload: pos_xy or vel_xy is NULL");
+  return NBODY_OK;
+}
+
+// The checked arguments stored as the handle's worlds.
+template <class P>
+int ens_upload_store(EnsembleState<P>* e, int64_t n_worlds, int64_t n_bodies, const typename P::Real* pos, const typename P::Real* vel,
+                     const uint32_t* weight) {
   if (int rc = ens_store_rows(e, n_worlds * n_bodies, pos, vel, weight)) return rc;
   e->n_worlds = n_worlds;
   e->n_bodies = n_bodies;
   return NBODY_OK;
+}
+
+template <class P>
+int ens_upload(EnsembleState<P>* e, int64_t n_worlds, int64_t n_bodies, const typename P::Real* pos, const typename P::Real* vel,
+               const uint32_t* weight) {
+  if (int rc = ens_upload_check(e, n_worlds, n_bodies, pos, vel)) return rc;
+  return ens_upload_store(e, n_worlds, n_bodies, pos, vel, weight);
 }
 
 template <class P> int ens_download(EnsembleState<P>* e, typename P::Real* pos, typename P::Real* vel) {

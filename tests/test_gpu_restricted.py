@@ -328,3 +328,31 @@ def test_lifetime_download_order_and_errors(nb, orc):
         assert cnt.sum_gravity == 0.0
         r.update(DT, cnt, n_steps=2)
         assert cnt.sum_gravity > 0.0 and cnt.build_bvh == 0.0 and cnt.post_calculations == 0.0
+
+
+def test_a_refused_upload_leaves_bodies_and_tracers_as_they_were(nb, orc):
+    """An upload refused for its arguments changes nothing.  The C call on the handle itself: the Python class would refuse first."""
+    C = nb._capi
+    n, m = 3, 5
+    pos, vel, w = _worlds(nb, n, 2, seed=1900, awkward_at=-1)
+    tp, tv = _tracers_for(pos, m, 2700, with_skip=False)
+    big = np.zeros((2, 4097, 2), F32)
+    with nb.RestrictedEnsemble(pos, vel, w, (tp, tv), arith="exact") as r:
+        r.update(DT, None, n_steps=1)
+        before = (*r.h.download(), *r.h.download_tracers())
+        assert not np.array_equal(before[0], pos) and not np.array_equal(before[2], tp)
+        for call in (lambda: r.h.upload(2, 4097, big, big, None), lambda: r.h.upload(2, n, None, vel, w)):
+            with pytest.raises(C.NBodyError) as e:
+                call()
+            assert e.value.code == C.ERR_INVALID
+            assert r.h._call("_last_error").decode().startswith("restricted upload:")
+            assert r.h.shape == (2, n) and r.h.n_tracers == m
+        after = (*r.h.download(), *r.h.download_tracers())
+        for x, y in zip(after, before):
+            assert x.shape == y.shape and x.tobytes() == y.tobytes()
+        r.update(DT, None, n_steps=1)
+        p, v, _ = r.particles()
+        gp, gv = r.tracers()
+    rp, rv, rtp, rtv = _exact_steps(orc, pos, vel, w, tp, tv, 2)
+    for x, y, what in ((p, rp, "positions"), (v, rv, "velocities"), (gp, rtp, "tracer positions"), (gv, rtv, "tracer velocities")):
+        _assert_worlds_equal(x, y, what)
