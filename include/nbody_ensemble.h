@@ -115,7 +115,8 @@ int nbody_ensemble64_accel(nbody_ensemble64* e, double* acc_xy);                
  *     past n_launches) the dynamic LDS and the number of blocks.  It is pure host code: no device, no handle, every output
  *     pointer may be NULL; sizes outside the limits give NBODY_ERR_INVALID and nothing is written.
  *   Not offered on this handle: f64 (nbody_ragged64_* below is the double-precision sibling), a per-world delta or clamp,
- *     tracers, tree methods, several devices, and what the ensemble above does not offer either. */
+ *     tracers (nbody_rr_* at the end of this file steps worlds of different sizes with tracers of their own), tree methods,
+ *     several devices, and what the ensemble above does not offer either. */
 #define NBODY_RAGGED_MAX_LAUNCHES 6
 typedef struct nbody_ragged nbody_ragged;
 int nbody_ragged_create(nbody_ragged** out, int device_id);
@@ -216,7 +217,7 @@ int nbody_ragged64_plan(int64_t n_worlds, const int64_t* n_bodies, int32_t* laun
  *     NULL handle gives NBODY_ERR_INVALID (0 from nbody_restricted_num_worlds / _num_bodies / _num_tracers);
  *     nbody_restricted_last_error(NULL): the last failed nbody_restricted_create on this thread, in a slot of its own.
  *   Not offered on this handle: f64 (nbody_restricted64_* below is the double-precision sibling); worlds of different sizes
- *     or a per-world n_tracers (a follow-up of its own, as ragged was for bodies); tree methods; several devices; snapshots, delta streams and frames; hipGraph replay.  The
+ *     or a per-world n_tracers on this handle (nbody_rr_* at the end of this file offers both); tree methods; several devices; snapshots, delta streams and frames; hipGraph replay.  The
  *     library reads no environment variable for any of this. */
 typedef struct nbody_restricted nbody_restricted;
 int nbody_restricted_create(nbody_restricted** out, int device_id);
@@ -286,5 +287,85 @@ int64_t nbody_restricted64_num_tracers(const nbody_restricted64* e);            
 int nbody_restricted64_update(nbody_restricted64* e, double delta, int n_steps, nbody_counting* counter);
 int nbody_restricted64_accel(nbody_restricted64* e, double* acc_xy);                            /* the bodies; state untouched */
 int nbody_restricted64_tracers_accel(nbody_restricted64* e, double* acc_xy);                    /* the tracers; state untouched */
+
+/* ---- ragged restricted ensembles: worlds of different sizes, each with tracers of its own, a handle of its own (f32) ----
+ * A stability map over systems with different numbers of massive bodies, capture cross-sections where each system gets as many
+ * test particles as its own geometry needs, halos cut out of a larger run with their own tracer populations: the restricted
+ * problem over worlds that differ in size AND in their number of tracers.  One nbody_restricted per distinct (n_bodies,
+ * n_tracers) is one launch chain per shape again, and padding is wrong for the reason the ragged ensemble gives (a padded body
+ * moves EXACT's chain and FAST's order of additions).  A ragged restricted ensemble holds n_worlds worlds of n_bodies[k] bodies
+ * and n_tracers[k] massless points each and steps all of them with at most NBODY_RR_MAX_LAUNCHES launches per step.
+ *   The prefix.  The calls are nbody_rr_* ("ragged restricted"), not nbody_ragged_restricted_* or nbody_restricted_ragged_*: the
+ *     names that begin with nbody_ragged_ and with nbody_restricted_ are closed sets that belong to those two handles, and a
+ *     handle of its own has a prefix that is a prefix of no other's.
+ *   Arrays.  Body rows as nbody_ragged_*: world after world in world order, no padding, world k's rows [off_k, off_k + n_k).
+ *     Tracer rows are laid out the same way: world k's tracers are the rows [toff_k, toff_k + m_k) with toff_k the sum of the
+ *     counts before it; a world with m_k == 0 has none.  pos / vel interleaved x,y; weight may be NULL (all 1).
+ *   Limits.  n_worlds >= 1, 1 <= n_bodies[k] <= 4096, the sizes add up to at most 2^26 rows; every n_tracers[k] >= 0, the counts
+ *     add up to at most 2^26 rows.  Anything outside gives NBODY_ERR_INVALID before anything is allocated, and the message names
+ *     "ragged restricted".  A refused upload leaves the bodies and the tracers as they were.
+ *   Bodies.  They are bit-identical to an nbody_ragged holding the same worlds: they come from the same kernel and the same
+ *     launches, under EXACT, FAST and AUTO, with or without tracers.
+ *   Tracers.  A tracer's acceleration is the field of its own world's bodies at their pre-step positions (the buffer that
+ *     step's launches of the bodies read): a_t = sum_j calculate_gravity(p_t, p_j, w_j), j ascending; no mass, no self term;
+ *     then main.rs:419-423 in f32, multiply then add, no contraction.  Tracer rows never move.
+ *   Tracers, EXACT.  They are bit-identical to the CPU restatement's direct_accel at the tracers (native accumulation) followed
+ *     by the Euler step of main.rs:419-423.
+ *   Tracers, FAST.  They are bit-identical to an nbody_restricted holding that world alone with those tracers: the two kernels
+ *     share one block body, and the order of additions is a function of n_bodies[k] alone (one lane per tracer, whatever
+ *     n_bodies[k] and n_tracers[k] are).  Hence every tracer is within the tolerance of DESIGN.md (2e-5 of sum_j |term|).
+ *   AUTO.  The route is taken per world and per step on the device, from the staging block's OR over the world's body positions
+ *     (outside FAST's domain: non-finite, >= 2^60 in magnitude, or non-zero below 2^-22), with no flag buffer: the same decision
+ *     in every body block and every tracer block of the world.  The per-tracer exception is nbody_restricted_*'s: in a FAST world
+ *     a tracer whose own pre-step position is outside that domain takes its EXACT value, its neighbours keep their FAST bits.  A
+ *     clamp below 2^-19, or NaN, sends everything to EXACT (FAST asked for by name, too).
+ *   Independence.  A tracer's bits depend on its own state, its world's bodies, n_bodies[k] and the params.  They do not depend
+ *     on n_tracers[k]; on the tracer's slot; on the other worlds' sizes, counts, contents, routes or order; on the launch it
+ *     falls in; or on how the steps are split over calls.
+ *   Launches.  A step runs the bodies' launches of nbody_ragged_plan (at most 6, unchanged) and then the tracers' (at most 6);
+ *     there is no host synchronisation between the steps of a call and nothing is read back.  Tracer blocks are grouped by the
+ *     LDS their world needs, the six classes of the ragged ensemble (n_bodies <= 128, <= 256, ... <= 4096).  A class launches only
+ *     if one of its worlds has tracers, under the LDS of the largest n_bodies among its worlds that have tracers.  World k
+ *     contributes ceil(n_tracers[k] / 512) blocks (a block is up to 512 tracers of one world), contiguous, and within a launch
+ *     the worlds follow one another in world order.  nbody_rr_plan shows this plan: for every world its launch and the first of
+ *     its blocks in that launch — both -1 for a world without tracers, a convention of this call (nbody_ragged_plan has no world
+ *     without a launch) — the number of launches (0 when no world has tracers), and per launch (arrays of
+ *     NBODY_RAGGED_MAX_LAUNCHES, zero past n_launches) the dynamic LDS and the number of blocks.  It is pure host code: no device,
+ *     no handle, every output pointer may be NULL; sizes or counts outside the limits give NBODY_ERR_INVALID and nothing is
+ *     written.  The bodies' plan is nbody_ragged_plan of the sizes, unchanged.
+ *   Lifetime.  nbody_rr_upload_f32 replaces the bodies and removes the tracers (new worlds).  nbody_rr_tracers_upload_f32
+ *     replaces the tracers; its n_worlds must be the bodies'; an all-zero n_tracers removes them (pos_xy / vel_xy may then be
+ *     NULL).  Without tracers the tracer downloads and nbody_rr_tracers_accel_f32 write nothing and return NBODY_OK.
+ *     nbody_rr_sizes writes the sizes and the counts (zeros without tracers); either output may be NULL.
+ *   Booking, params, trivial calls.  As the ensemble's: the whole call goes under sum_gravity; clamp and arith are used;
+ *     n_steps == 0 is a no-op; an update, accel or download before an upload is NBODY_ERR_INVALID.
+ *   Errors.  There is no CPU path: nbody_rr_create fails with NBODY_ERR_NO_DEVICE without a gfx950 device.  A NULL handle gives
+ *     NBODY_ERR_INVALID (0 from nbody_rr_num_worlds / _num_rows / _num_tracer_rows); nbody_rr_last_error(NULL): the last failed
+ *     nbody_rr_create or nbody_rr_plan on this thread, in a slot of its own.
+ *   Not offered on this handle: f64 (a sibling of its own, to follow); a per-world delta or clamp; tree methods; several
+ *     devices; snapshots, delta streams and frames; hipGraph replay.  The library reads no environment variable for any of
+ *     this. */
+#define NBODY_RR_MAX_LAUNCHES 12
+typedef struct nbody_rr nbody_rr;
+int nbody_rr_create(nbody_rr** out, int device_id);
+void nbody_rr_destroy(nbody_rr* e);
+const char* nbody_rr_last_error(const nbody_rr* e);
+int nbody_rr_set_params(nbody_rr* e, const nbody_params* p);
+int nbody_rr_get_params(const nbody_rr* e, nbody_params* out);
+int nbody_rr_upload_f32(nbody_rr* e, int64_t n_worlds, const int64_t* n_bodies /*[n_worlds]*/, const float* pos_xy,
+                        const float* vel_xy, const uint32_t* weight);
+int nbody_rr_download_f32(nbody_rr* e, float* pos_xy, float* vel_xy);             /* the bodies; either may be NULL */
+int nbody_rr_tracers_upload_f32(nbody_rr* e, int64_t n_worlds, const int64_t* n_tracers /*[n_worlds]*/, const float* pos_xy,
+                                const float* vel_xy);
+int nbody_rr_tracers_download_f32(nbody_rr* e, float* pos_xy, float* vel_xy);     /* either may be NULL */
+int64_t nbody_rr_num_worlds(const nbody_rr* e);
+int64_t nbody_rr_num_rows(const nbody_rr* e);                                     /* the sum of the sizes */
+int64_t nbody_rr_num_tracer_rows(const nbody_rr* e);                              /* the sum of the tracer counts */
+int nbody_rr_sizes(const nbody_rr* e, int64_t* n_bodies_out /*[num_worlds]*/, int64_t* n_tracers_out /*[num_worlds]*/);
+int nbody_rr_update_f32(nbody_rr* e, float delta, int n_steps, nbody_counting* counter);
+int nbody_rr_accel_f32(nbody_rr* e, float* acc_xy);                               /* the bodies; state untouched */
+int nbody_rr_tracers_accel_f32(nbody_rr* e, float* acc_xy);                       /* the tracers; state untouched */
+int nbody_rr_plan(int64_t n_worlds, const int64_t* n_bodies, const int64_t* n_tracers, int32_t* launch_of_world,
+                  int64_t* first_block_of_world, int32_t* n_launches, int32_t* lds_bytes_of_launch, int64_t* blocks_of_launch);
 
 #endif /* NBODY_ENSEMBLE_H */

@@ -166,6 +166,23 @@ _SIGS = {
     "nbody_restricted64_update": (C.c_int, [_vp, _f64, _i32, C.POINTER(Counting)]),
     "nbody_restricted64_accel": (C.c_int, [_vp, _vp]),
     "nbody_restricted64_tracers_accel": (C.c_int, [_vp, _vp]),
+    "nbody_rr_create": (C.c_int, [C.POINTER(_vp), _i32]),
+    "nbody_rr_destroy": (None, [_vp]),
+    "nbody_rr_last_error": (C.c_char_p, [_vp]),
+    "nbody_rr_set_params": (C.c_int, [_vp, C.POINTER(Params)]),
+    "nbody_rr_get_params": (C.c_int, [_vp, C.POINTER(Params)]),
+    "nbody_rr_upload_f32": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "nbody_rr_download_f32": (C.c_int, [_vp, _vp, _vp]),
+    "nbody_rr_tracers_upload_f32": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    "nbody_rr_tracers_download_f32": (C.c_int, [_vp, _vp, _vp]),
+    "nbody_rr_num_worlds": (_i64, [_vp]),
+    "nbody_rr_num_rows": (_i64, [_vp]),
+    "nbody_rr_num_tracer_rows": (_i64, [_vp]),
+    "nbody_rr_sizes": (C.c_int, [_vp, _vp, _vp]),
+    "nbody_rr_update_f32": (C.c_int, [_vp, _f32, _i32, C.POINTER(Counting)]),
+    "nbody_rr_accel_f32": (C.c_int, [_vp, _vp]),
+    "nbody_rr_tracers_accel_f32": (C.c_int, [_vp, _vp]),
+    "nbody_rr_plan": (C.c_int, [_i64, _vp, _vp, _vp, _vp, C.POINTER(_i32), _vp, _vp]),
     "nbody_accel_tree_f32": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_accel_tree_f64": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_tree_info": (C.c_int, [_vp, C.POINTER(TreeView)]),
@@ -1005,7 +1022,43 @@ class Restricted64Handle(_TracerCalls, Ensemble64Handle):
     _prefix = "nbody_restricted64"
 
 
+class RRHandle(RaggedHandle):
+    """nbody_rr_*: float32 worlds of different sizes, each with tracers of its own; the bodies' calls are RaggedHandle's.  The
+    tracer rows of all worlds come one after another in world order, as the body rows do."""
+    _prefix = "nbody_rr"
+
+    @property
+    def n_tracer_rows(self):
+        """The tracers of all worlds together; 0 without any."""
+        return int(self._call("_num_tracer_rows"))
+
+    @property
+    def sizes(self):
+        """(the bodies of every world, the tracers of every world), int64[worlds] each."""
+        b = self.shape[0]
+        bodies, tracers = np.zeros(b, np.int64), np.zeros(b, np.int64)
+        self._check(self._call("_sizes", _ptr(bodies), _ptr(tracers)))
+        return bodies, tracers
+
+    def upload_tracers(self, counts, pos, vel):
+        """counts int64[worlds]; pos, vel [tracer rows, 2] float32, contiguous (None where every count is 0: no tracers)."""
+        counts = np.ascontiguousarray(counts, dtype=np.int64)
+        self._check(self._call("_tracers_upload" + self._suffix, int(counts.shape[0]), _ptr(counts), _ptr(pos), _ptr(vel)))
+
+    def download_tracers(self):
+        rows = self.n_tracer_rows
+        pos, vel = np.zeros((rows, 2), self._dtype), np.zeros((rows, 2), self._dtype)
+        self._check(self._call("_tracers_download" + self._suffix, _ptr(pos), _ptr(vel)))
+        return pos, vel
+
+    def tracers_accel(self):
+        acc = np.zeros((self.n_tracer_rows, 2), self._dtype)
+        self._check(self._call("_tracers_accel" + self._suffix, _ptr(acc)))
+        return acc
+
+
 RAGGED_MAX_LAUNCHES = 6
+RR_MAX_LAUNCHES = 12
 
 
 def ragged_plan(sizes, f64=False):
@@ -1022,6 +1075,26 @@ def ragged_plan(sizes, f64=False):
     rc = getattr(lib, prefix + "_plan")(b, _ptr(sizes), _ptr(launch), _ptr(first), C.byref(n), _ptr(lds), _ptr(blocks))
     if rc != OK:
         msg = getattr(lib, prefix + "_last_error")(None)
+        raise NBodyError(rc, msg.decode() if msg else "")
+    return launch, first, lds[:n.value].copy(), blocks[:n.value].copy()
+
+
+def rr_plan(sizes, tracer_counts):
+    """nbody_rr_plan of these sizes and tracer counts (pure host code): the TRACERS' launches of a ragged restricted ensemble ->
+    (launch_of_world int32[worlds], first_block_of_world int64[worlds], both -1 for a world without tracers, lds_bytes
+    int32[launches], blocks int64[launches]); NBodyError(ERR_INVALID) for sizes or counts outside the limits."""
+    lib = load()
+    sizes = np.ascontiguousarray(sizes, dtype=np.int64)
+    counts = np.ascontiguousarray(tracer_counts, dtype=np.int64)
+    b = int(sizes.shape[0])
+    if counts.shape != sizes.shape:
+        raise ValueError(f"rr_plan: {counts.shape[0]} tracer counts beside {b} sizes")
+    launch, first = np.zeros(b, np.int32), np.zeros(b, np.int64)
+    lds, blocks = np.zeros(RAGGED_MAX_LAUNCHES, np.int32), np.zeros(RAGGED_MAX_LAUNCHES, np.int64)
+    n = _i32(0)
+    rc = lib.nbody_rr_plan(b, _ptr(sizes), _ptr(counts), _ptr(launch), _ptr(first), C.byref(n), _ptr(lds), _ptr(blocks))
+    if rc != OK:
+        msg = lib.nbody_rr_last_error(None)
         raise NBodyError(rc, msg.decode() if msg else "")
     return launch, first, lds[:n.value].copy(), blocks[:n.value].copy()
 

@@ -5,7 +5,7 @@
 //
 // P supplies: Real, Vec2 (the element types), Mass (what the device keeps per body), Args (the kernel's arguments);
 //   kCreate                        the create call's name, the prefix of its messages;
-//   kWho                           the word that every other message of the handle begins with ("ensemble", "ragged", "restricted");
+//   kWho                           the word that every other message of the handle begins with ("ensemble", "ragged", "restricted", "ragged restricted");
 //   stage(weight, rows, tmp)       -> the rows Mass values to upload (tmp is theirs to fill);
 //   route(args, mass, params)      the masses and the arithmetic of a launch, from the handle's parameters;
 //   launch(stream, n_worlds, args) one step, or one force evaluation, of all worlds.

@@ -1,6 +1,7 @@
 // What is f32 about an ensemble, for the driver of ensemble_driver.h: the masses uploaded as `weight as f32`, the arith rule of the
-// f32 direct step, the kernel of ensemble_kernels.hip.  Internal; ensemble.hip (nbody_ensemble_*), ragged.hip (nbody_ragged_*)
-// and restricted.hip (nbody_restricted_*, which adds the tracers' launch for restricted_driver.h) build their handles over it.
+// f32 direct step, the kernel of ensemble_kernels.hip.  Internal; ensemble.hip (nbody_ensemble_*), ragged.hip (nbody_ragged_*),
+// restricted.hip (nbody_restricted_*, which adds the tracers' launch for restricted_driver.h) and rr.hip (nbody_rr_*, which adds
+// both the ragged launch and the tracers' launch over work items for rr_driver.h) build their handles over it.
 #pragma once
 #include "ensemble_driver.h"
 

@@ -25,6 +25,12 @@ DESIGN.md, AUTO per world and per step on the device with a per-tracer exception
 `RestrictedEnsemble64` (nbody_restricted64_*) is its double-precision sibling, float64 arrays only: the bodies are bit-identical
 to an `Ensemble64` of the same worlds; a tracer is EXACT (and AUTO) bit-identical to the oracle's direct_accel at it + Euler on
 float64, FAST (opt-in, per world and per step on the device, with the same per-tracer exception) within 1e-12 of sum |term|.
+
+`RaggedRestrictedEnsemble` (nbody_rr_*) holds float32 worlds of DIFFERENT sizes, each with a tracer count of its own — a stability
+map over systems with different numbers of massive bodies, halos with their own tracer populations — and steps them together
+with at most twelve launches per step (`ragged_plan` shows the bodies', `rr_plan` the tracers').  The bodies are bit-identical
+to a `RaggedEnsemble` of the same worlds; a tracer is EXACT bit-identical to the oracle, FAST bit-identical to a
+`RestrictedEnsemble` holding its world alone.
 """
 from __future__ import annotations
 
@@ -255,13 +261,15 @@ class RestrictedEnsemble64(_RestrictedBase):
         return _capi.Restricted64Handle(device)
 
 
-def _checked_ragged(positions, velocities, weights, dtype=np.float32):
+def _checked_ragged(positions, velocities, weights, dtype=np.float32, who=None, other=None):
     """-> (sizes int64[B], position[rows,2], velocity[rows,2], weight uint32[rows] or None), the worlds' rows one after another;
-    ValueError for anything else.  Nothing is copied before every world has passed.  The messages name the class of that dtype:
-    RaggedEnsemble (float32) or RaggedEnsemble64 (float64)."""
+    ValueError for anything else.  Nothing is copied before every world has passed.  The messages name `who`, or the class of
+    that dtype: RaggedEnsemble (float32) or RaggedEnsemble64 (float64); a wrong dtype adds `other`, or which of those two takes
+    the other one."""
     dtype = np.dtype(dtype)
-    who, other = (("RaggedEnsemble", "RaggedEnsemble64 takes float64") if dtype == np.float32
-                  else ("RaggedEnsemble64", "RaggedEnsemble takes float32"))
+    name, sibling = (("RaggedEnsemble", "RaggedEnsemble64 takes float64") if dtype == np.float32
+                     else ("RaggedEnsemble64", "RaggedEnsemble takes float32"))
+    who, other = who or name, other or sibling
     for name, seq in (("positions", positions), ("velocities", velocities)) + ((("weights", weights),) if weights is not None else ()):
         if not hasattr(seq, "__len__"):
             raise ValueError(f"{who}: {name} must be a sequence of per-world arrays")
@@ -387,6 +395,117 @@ class RaggedEnsemble64(_RaggedBase):
 
     def __init__(self, positions, velocities, weights=None, arith="exact", clamp=0.001, device=0):
         self._create(positions, velocities, weights, device, clamp, arith)
+
+
+def _checked_rr_tracers(tracers, sizes, who="RaggedRestrictedEnsemble"):
+    """tracers: None, or one entry per world, each None or a pair (position[m_k, 2], velocity[m_k, 2]) of float32 ->
+    (counts int64[B], position[rows, 2], velocity[rows, 2]), the worlds' tracer rows one after another (both None where no
+    world has a tracer); ValueError for anything else.  Nothing is copied before every world has passed."""
+    b = len(sizes)
+    counts = np.zeros(b, np.int64)
+    if tracers is None:
+        return counts, None, None
+    if not isinstance(tracers, (tuple, list)) or len(tracers) != b:
+        raise ValueError(f"{who}: tracers must be None or a list with one entry per world ({b} worlds): None or a pair "
+                         "(position[m, 2], velocity[m, 2])")
+    tps, tvs, rows = [], [], 0
+    for k, entry in enumerate(tracers):
+        if entry is None:
+            continue
+        if not isinstance(entry, (tuple, list)) or len(entry) != 2:
+            raise ValueError(f"{who}: world {k}: tracers must be None or a pair (position[m, 2], velocity[m, 2])")
+        tp, tv = np.asarray(entry[0]), np.asarray(entry[1])
+        for name, a in (("tracer position", tp), ("tracer velocity", tv)):
+            if a.dtype != np.float32:
+                raise ValueError(f"{who}: world {k}: {name} must be float32 (got {a.dtype})")
+        if tp.ndim != 2 or tp.shape[1] != 2:
+            raise ValueError(f"{who}: world {k}: tracer position must be [m, 2], got {tp.shape}")
+        if tv.shape != tp.shape:
+            raise ValueError(f"{who}: world {k}: tracer velocity {tv.shape} does not match tracer position {tp.shape}")
+        counts[k] = tp.shape[0]
+        rows += tp.shape[0]
+        if rows > MAX_ROWS:
+            raise ValueError(f"{who}: the tracers add up to more than 2^26 rows")
+        if tp.shape[0]:
+            tps.append(tp), tvs.append(tv)
+    if not rows:
+        return counts, None, None
+    return counts, np.ascontiguousarray(np.concatenate(tps)), np.ascontiguousarray(np.concatenate(tvs))
+
+
+class RaggedRestrictedEnsemble(_RaggedBase):
+    """Worlds of different sizes, each with tracers of its own, stepped together (nbody_rr_*), float32: positions, velocities
+    are sequences of [n_k, 2] arrays, weights a sequence of [n_k] integer arrays or None (all 1), tracers None or a list with one
+    entry per world, each None or a pair (position[m_k, 2], velocity[m_k, 2]).  1 .. 4096 bodies per world, at most 2^26 bodies
+    and at most 2^26 tracers in all.  The bodies are bit-identical to a `RaggedEnsemble` of the same worlds; a tracer is EXACT
+    bit-identical to the oracle's direct_accel at it + Euler, FAST bit-identical to a `RestrictedEnsemble` holding its world
+    alone, AUTO per world and per step on the device with the per-tracer exception of `RestrictedEnsemble`."""
+    _dtype = np.float32
+    _who = "RaggedRestrictedEnsemble"
+
+    @staticmethod
+    def _new_handle(device):
+        return _capi.RRHandle(device)
+
+    def _check(self, positions, velocities, weights, tracers):
+        args = _checked_ragged(positions, velocities, weights, self._dtype, who=self._who, other="it takes float32 only")
+        return args, _checked_rr_tracers(tracers, args[0], self._who)
+
+    def __init__(self, positions, velocities, weights=None, tracers=None, *, device=0, clamp=0.001, arith="auto"):
+        if arith not in _ARITH:
+            raise ValueError(f"{self._who}: arith must be one of {sorted(_ARITH)}")
+        self.h = None
+        args, tr = self._check(positions, velocities, weights, tracers)
+        self.h = self._new_handle(device)
+        self.h.set_params(clamp=float(clamp), arith=_ARITH[arith])
+        self._upload(*args)
+        self._upload_tracers(*tr)
+
+    def _upload_tracers(self, counts, tp, tv):
+        self.h.upload_tracers(counts, tp, tv)
+        self._counts = counts
+        self._tcuts = np.cumsum(counts)[:-1]
+
+    def upload(self, positions, velocities, weights=None, tracers=None):
+        """Replaces the worlds by others, of any sizes; the previous tracers go with them."""
+        args, tr = self._check(positions, velocities, weights, tracers)
+        self._upload(*args)
+        self._upload_tracers(*tr)
+
+    def set_tracers(self, tracers):
+        """Replaces the tracers: a list with one entry per world, each None or (position[m_k, 2], velocity[m_k, 2]); None, or no
+        tracer in any world, removes them."""
+        self._upload_tracers(*_checked_rr_tracers(tracers, self._sizes, self._who))
+
+    @property
+    def sizes(self):
+        """(the bodies of every world, the tracers of every world), in world order."""
+        return [int(n) for n in self._sizes], [int(m) for m in self._counts]
+
+    def _per_world_tracers(self, a):
+        return [t.copy() for t in np.split(a, self._tcuts)]
+
+    def tracers(self):
+        """-> a list of pairs (position[m_k, 2], velocity[m_k, 2]) in upload order, empty arrays where m_k == 0; rows never move."""
+        pos, vel = self.h.download_tracers()
+        return list(zip(self._per_world_tracers(pos), self._per_world_tracers(vel)))
+
+    def tracers_accel(self):
+        """-> a list of acc[m_k, 2]: the accelerations at the tracers' current positions; the state is untouched."""
+        return self._per_world_tracers(self.h.tracers_accel())
+
+
+def rr_plan(sizes, tracer_counts):
+    """The launches the TRACERS of a RaggedRestrictedEnsemble of these sizes and tracer counts take per step (nbody_rr_plan; host
+    code, no GPU needed; the bodies' launches are `ragged_plan(sizes)`) -> dict: launch_of_world, first_block_of_world (a
+    world's blocks are contiguous in its launch; both -1 for a world without tracers), lds_bytes and blocks per launch."""
+    sizes, counts = [int(n) for n in sizes], [int(m) for m in tracer_counts]
+    if not sizes or min(sizes) < 1 or max(sizes) > MAX_BODIES or sum(sizes) > MAX_ROWS:
+        raise ValueError(f"rr_plan: at least one world, 1 .. {MAX_BODIES} bodies per world, at most 2^26 in all")
+    if len(counts) != len(sizes) or min(counts) < 0 or sum(counts) > MAX_ROWS:
+        raise ValueError("rr_plan: one tracer count >= 0 per world, at most 2^26 tracers in all")
+    launch, first, lds, blocks = _capi.rr_plan(sizes, counts)
+    return dict(launch_of_world=launch, first_block_of_world=first, lds_bytes=lds, blocks=blocks)
 
 
 def ragged_plan(sizes, dtype=np.float32):
