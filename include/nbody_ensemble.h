@@ -342,7 +342,7 @@ int nbody_restricted64_tracers_accel(nbody_restricted64* e, double* acc_xy);    
  *   Errors.  There is no CPU path: nbody_rr_create fails with NBODY_ERR_NO_DEVICE without a gfx950 device.  A NULL handle gives
  *     NBODY_ERR_INVALID (0 from nbody_rr_num_worlds / _num_rows / _num_tracer_rows); nbody_rr_last_error(NULL): the last failed
  *     nbody_rr_create or nbody_rr_plan on this thread, in a slot of its own.
- *   Not offered on this handle: f64 (a sibling of its own, to follow); a per-world delta or clamp; tree methods; several
+ *   Not offered on this handle: f64 (nbody_rr64_* below is the double-precision sibling); a per-world delta or clamp; tree methods; several
  *     devices; snapshots, delta streams and frames; hipGraph replay.  The library reads no environment variable for any of
  *     this. */
 #define NBODY_RR_MAX_LAUNCHES 12
@@ -367,5 +367,77 @@ int nbody_rr_accel_f32(nbody_rr* e, float* acc_xy);                             
 int nbody_rr_tracers_accel_f32(nbody_rr* e, float* acc_xy);                       /* the tracers; state untouched */
 int nbody_rr_plan(int64_t n_worlds, const int64_t* n_bodies, const int64_t* n_tracers, int32_t* launch_of_world,
                   int64_t* first_block_of_world, int32_t* n_launches, int32_t* lds_bytes_of_launch, int64_t* blocks_of_launch);
+
+/* ---- ragged restricted ensembles in f64: double-precision worlds of different sizes, each with tracers of its own --------
+ * The ragged restricted ensemble above in double precision: n_worlds worlds of n_bodies[k] bodies and n_tracers[k] massless
+ * points each, float64 arrays, stepped with at most NBODY_RR_MAX_LAUNCHES launches per step (the constant serves both
+ * precisions).  One nbody_restricted64 per distinct (n_bodies, n_tracers) is one launch chain per shape; this handle is one.
+ *   The prefix.  The calls are nbody_rr64_*, typed calls without a suffix as the other f64 handles name theirs.  The prefix
+ *     begins with none of nbody_rr_, nbody_ragged64_ or nbody_restricted64_: those are closed sets of their own handles.
+ *   Arrays.  As nbody_rr_*, in double: body rows world after world in world order, no padding, world k's rows [off_k, off_k +
+ *     n_k); tracer rows the same way, world k's tracers the rows [toff_k, toff_k + m_k), none for m_k == 0.  pos / vel
+ *     interleaved x,y; weight may be NULL (all 1); the masses are the u32 weights (`weight as f64` is exact).
+ *   Limits.  n_worlds >= 1, 1 <= n_bodies[k] <= 4096, the sizes add up to at most 2^26 rows; every n_tracers[k] >= 0, the counts
+ *     add up to at most 2^26 rows.  Anything outside gives NBODY_ERR_INVALID before anything is allocated, and the message names
+ *     "ragged restricted".  A refused upload leaves the bodies and the tracers as they were.
+ *   Bodies.  They are bit-identical to an nbody_ragged64 holding the same worlds: the same kernel and the same launches, under
+ *     every arith, with or without tracers.
+ *   Tracers.  a_t = sum_j calculate_gravity(p_t, p_j, w_j as f64) over the bodies of the tracer's own world at their pre-step
+ *     positions (the buffer that step's launches of the bodies read), j ascending, the clamp params.clamp widened to double; no
+ *     mass, no self term; then main.rs:419-423 in double, multiply then add, no contraction.  Tracer rows never move.
+ *   Tracers, EXACT and AUTO.  AUTO is EXACT, as for every f64 handle.  One ascending-row chain of IEEE additions per tracer:
+ *     bit-identical to the CPU restatement's direct_accel at the tracers (native accumulation) on float64 followed by that Euler
+ *     step: what nbody_restricted64_* promises.
+ *   Tracers, FAST (opt-in).  They are bit-identical to an nbody_restricted64 holding that world alone with those tracers: the two
+ *     kernels share one block body, and the order of additions is a function of n_bodies[k] alone (one lane per tracer, whatever
+ *     n_bodies[k] and n_tracers[k] are).  Hence every tracer is within 1e-12 of sum_j |term_j|_1, and for
+ *     n_bodies[k] > 128 a tracer that sits exactly on a body gets that body's FAST acceleration bit for bit.  The route is taken
+ *     per world and per step on the device from the staging's OR over the world's body positions (outside the f64 FAST domain:
+ *     non-finite, >= 2^100 in magnitude, or non-zero below 2^-300), with no flag buffer: the same decision in every body block
+ *     and every tracer block of the world, and such a world's bodies and tracers take EXACT for that step.  In a FAST world a
+ *     tracer whose own pre-step position is outside that domain takes its EXACT value; its neighbours keep their FAST bits.
+ *     With a clamp that is not > 0, or NaN, everything takes EXACT.
+ *   Independence.  A tracer's bits depend on its own state, its world's bodies, n_bodies[k] and the params.  They do not depend
+ *     on n_tracers[k]; on the tracer's slot; on the other worlds' sizes, counts, contents, routes or order; on the launch it
+ *     falls in; or on how the steps are split over calls.
+ *   Launches.  A step runs the bodies' launches of nbody_ragged64_plan (at most 6, unchanged) and then the tracers' (at most 6),
+ *     with no host synchronisation between the steps of a call.  The tracers' plan is nbody_rr_plan's under the f64 LDS function
+ *     (20 bytes a body, the rows padded to a multiple of 8; 81 920 B at n_bodies = 4096 and no other LDS): the six classes by
+ *     n_bodies, a class launching only if one of its worlds has tracers, under the LDS of the largest n_bodies among its worlds
+ *     that have tracers; ceil(n_tracers[k] / 512) contiguous blocks per world, worlds in world order.  nbody_rr64_plan shows it,
+ *     with the outputs and conventions of nbody_rr_plan (-1 / -1 for a world without tracers; pure host code; every output may
+ *     be NULL; nothing is written on NBODY_ERR_INVALID).
+ *   Lifetime.  nbody_rr64_upload replaces the bodies and removes the tracers (new worlds).  nbody_rr64_tracers_upload replaces
+ *     the tracers; its n_worlds must be the bodies'; an all-zero n_tracers removes them (pos_xy / vel_xy may then be NULL).
+ *     Without tracers the tracer downloads and nbody_rr64_tracers_accel write nothing and return NBODY_OK.  nbody_rr64_sizes
+ *     writes the sizes and the counts (zeros without tracers); either output may be NULL.
+ *   Booking, params, trivial calls.  As the ensemble's: the whole call goes under sum_gravity; clamp and arith are used;
+ *     n_steps == 0 is a no-op; an update, accel or download before an upload is NBODY_ERR_INVALID.
+ *   Errors.  There is no CPU path: nbody_rr64_create fails with NBODY_ERR_NO_DEVICE without a gfx950 device.  A NULL handle
+ *     gives NBODY_ERR_INVALID (0 from nbody_rr64_num_worlds / _num_rows / _num_tracer_rows); nbody_rr64_last_error(NULL): the
+ *     last failed nbody_rr64_create or nbody_rr64_plan on this thread, in a slot of its own, apart from nbody_rr_*'s and
+ *     nbody_ragged64_*'s.
+ *   Not offered on this handle: what nbody_rr_* does not offer either. */
+typedef struct nbody_rr64 nbody_rr64;
+int nbody_rr64_create(nbody_rr64** out, int device_id);
+void nbody_rr64_destroy(nbody_rr64* e);
+const char* nbody_rr64_last_error(const nbody_rr64* e);
+int nbody_rr64_set_params(nbody_rr64* e, const nbody_params* p);
+int nbody_rr64_get_params(const nbody_rr64* e, nbody_params* out);
+int nbody_rr64_upload(nbody_rr64* e, int64_t n_worlds, const int64_t* n_bodies /*[n_worlds]*/, const double* pos_xy,
+                      const double* vel_xy, const uint32_t* weight);
+int nbody_rr64_download(nbody_rr64* e, double* pos_xy, double* vel_xy);           /* the bodies; either may be NULL */
+int nbody_rr64_tracers_upload(nbody_rr64* e, int64_t n_worlds, const int64_t* n_tracers /*[n_worlds]*/, const double* pos_xy,
+                              const double* vel_xy);
+int nbody_rr64_tracers_download(nbody_rr64* e, double* pos_xy, double* vel_xy);   /* either may be NULL */
+int64_t nbody_rr64_num_worlds(const nbody_rr64* e);
+int64_t nbody_rr64_num_rows(const nbody_rr64* e);                                 /* the sum of the sizes */
+int64_t nbody_rr64_num_tracer_rows(const nbody_rr64* e);                          /* the sum of the tracer counts */
+int nbody_rr64_sizes(const nbody_rr64* e, int64_t* n_bodies_out /*[num_worlds]*/, int64_t* n_tracers_out /*[num_worlds]*/);
+int nbody_rr64_update(nbody_rr64* e, double delta, int n_steps, nbody_counting* counter);
+int nbody_rr64_accel(nbody_rr64* e, double* acc_xy);                              /* the bodies; state untouched */
+int nbody_rr64_tracers_accel(nbody_rr64* e, double* acc_xy);                      /* the tracers; state untouched */
+int nbody_rr64_plan(int64_t n_worlds, const int64_t* n_bodies, const int64_t* n_tracers, int32_t* launch_of_world,
+                    int64_t* first_block_of_world, int32_t* n_launches, int32_t* lds_bytes_of_launch, int64_t* blocks_of_launch);
 
 #endif /* NBODY_ENSEMBLE_H */

@@ -183,6 +183,23 @@ _SIGS = {
     "nbody_rr_accel_f32": (C.c_int, [_vp, _vp]),
     "nbody_rr_tracers_accel_f32": (C.c_int, [_vp, _vp]),
     "nbody_rr_plan": (C.c_int, [_i64, _vp, _vp, _vp, _vp, C.POINTER(_i32), _vp, _vp]),
+    "nbody_rr64_create": (C.c_int, [C.POINTER(_vp), _i32]),
+    "nbody_rr64_destroy": (None, [_vp]),
+    "nbody_rr64_last_error": (C.c_char_p, [_vp]),
+    "nbody_rr64_set_params": (C.c_int, [_vp, C.POINTER(Params)]),
+    "nbody_rr64_get_params": (C.c_int, [_vp, C.POINTER(Params)]),
+    "nbody_rr64_upload": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "nbody_rr64_download": (C.c_int, [_vp, _vp, _vp]),
+    "nbody_rr64_tracers_upload": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    "nbody_rr64_tracers_download": (C.c_int, [_vp, _vp, _vp]),
+    "nbody_rr64_num_worlds": (_i64, [_vp]),
+    "nbody_rr64_num_rows": (_i64, [_vp]),
+    "nbody_rr64_num_tracer_rows": (_i64, [_vp]),
+    "nbody_rr64_sizes": (C.c_int, [_vp, _vp, _vp]),
+    "nbody_rr64_update": (C.c_int, [_vp, _f64, _i32, C.POINTER(Counting)]),
+    "nbody_rr64_accel": (C.c_int, [_vp, _vp]),
+    "nbody_rr64_tracers_accel": (C.c_int, [_vp, _vp]),
+    "nbody_rr64_plan": (C.c_int, [_i64, _vp, _vp, _vp, _vp, C.POINTER(_i32), _vp, _vp]),
     "nbody_accel_tree_f32": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_accel_tree_f64": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_tree_info": (C.c_int, [_vp, C.POINTER(TreeView)]),
@@ -1041,7 +1058,8 @@ class RRHandle(RaggedHandle):
         return bodies, tracers
 
     def upload_tracers(self, counts, pos, vel):
-        """counts int64[worlds]; pos, vel [tracer rows, 2] float32, contiguous (None where every count is 0: no tracers)."""
+        """counts int64[worlds]; pos, vel [tracer rows, 2] of the handle's dtype, contiguous (None where every count is 0: no
+        tracers)."""
         counts = np.ascontiguousarray(counts, dtype=np.int64)
         self._check(self._call("_tracers_upload" + self._suffix, int(counts.shape[0]), _ptr(counts), _ptr(pos), _ptr(vel)))
 
@@ -1055,6 +1073,11 @@ class RRHandle(RaggedHandle):
         acc = np.zeros((self.n_tracer_rows, 2), self._dtype)
         self._check(self._call("_tracers_accel" + self._suffix, _ptr(acc)))
         return acc
+
+
+class RR64Handle(RRHandle):
+    """nbody_rr64_*: float64 worlds of different sizes, each with tracers of its own, the sibling of RRHandle."""
+    _prefix, _suffix, _dtype = "nbody_rr64", "", np.float64
 
 
 RAGGED_MAX_LAUNCHES = 6
@@ -1079,11 +1102,13 @@ def ragged_plan(sizes, f64=False):
     return launch, first, lds[:n.value].copy(), blocks[:n.value].copy()
 
 
-def rr_plan(sizes, tracer_counts):
-    """nbody_rr_plan of these sizes and tracer counts (pure host code): the TRACERS' launches of a ragged restricted ensemble ->
+def rr_plan(sizes, tracer_counts, f64=False):
+    """nbody_rr_plan (f64: nbody_rr64_plan) of these sizes and tracer counts (pure host code): the TRACERS' launches of a ragged
+    restricted ensemble ->
     (launch_of_world int32[worlds], first_block_of_world int64[worlds], both -1 for a world without tracers, lds_bytes
     int32[launches], blocks int64[launches]); NBodyError(ERR_INVALID) for sizes or counts outside the limits."""
     lib = load()
+    prefix = "nbody_rr64" if f64 else "nbody_rr"
     sizes = np.ascontiguousarray(sizes, dtype=np.int64)
     counts = np.ascontiguousarray(tracer_counts, dtype=np.int64)
     b = int(sizes.shape[0])
@@ -1092,9 +1117,9 @@ def rr_plan(sizes, tracer_counts):
     launch, first = np.zeros(b, np.int32), np.zeros(b, np.int64)
     lds, blocks = np.zeros(RAGGED_MAX_LAUNCHES, np.int32), np.zeros(RAGGED_MAX_LAUNCHES, np.int64)
     n = _i32(0)
-    rc = lib.nbody_rr_plan(b, _ptr(sizes), _ptr(counts), _ptr(launch), _ptr(first), C.byref(n), _ptr(lds), _ptr(blocks))
+    rc = getattr(lib, prefix + "_plan")(b, _ptr(sizes), _ptr(counts), _ptr(launch), _ptr(first), C.byref(n), _ptr(lds), _ptr(blocks))
     if rc != OK:
-        msg = lib.nbody_rr_last_error(None)
+        msg = getattr(lib, prefix + "_last_error")(None)
         raise NBodyError(rc, msg.decode() if msg else "")
     return launch, first, lds[:n.value].copy(), blocks[:n.value].copy()
 

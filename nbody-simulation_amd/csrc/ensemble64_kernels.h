@@ -51,7 +51,7 @@ hipError_t launch_ensemble64_step_ragged(hipStream_t s, int64_t blocks, size_t l
 
 // Raises `kernel`'s limit of dynamic LDS to ensemble64_lds_bytes(kEnsembleMaxBodies), once per device: `raised` is that
 // function's own zero-initialised table of 64 (a raised limit covers one function, so every kernel that stages a world of more
-// than 64 KB keeps a table: the two above, and the tracers' kernel of restricted64_kernels.h).
+// than 64 KB keeps a table: the two above, and the tracers' kernels of restricted64_kernels.h and rr64_kernels.h).
 hipError_t ens64_raise_lds_limit(const void* kernel, std::atomic<bool>* raised);
 
 }  // namespace nbody

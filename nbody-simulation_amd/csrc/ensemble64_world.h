@@ -1,8 +1,9 @@
 // What the f64 kernels that stage a whole world in LDS share on the device: the layout and its staging with FAST's decision
 // taken on the way, the EXACT chain and the FAST sum over the staged rows.  Internal.  ensemble64_kernels.hip (the bodies of
-// nbody_ensemble64_* / nbody_ragged64_* / nbody_restricted64_*) and restricted64_kernels.hip (the tracers of
-// nbody_restricted64_*) are written over it, so that a pair and an order of additions are stated once: what the two kernels
-// promise each other bit for bit (restricted64_kernels.h) holds because they run this text.
+// nbody_ensemble64_* / nbody_ragged64_* / nbody_restricted64_* / nbody_rr64_*) and, through restricted64_device.h,
+// restricted64_kernels.hip and rr64_kernels.hip (the tracers of nbody_restricted64_* and nbody_rr64_*) are written over it, so
+// that a pair and an order of additions are stated once: what the bodies' and the tracers' kernels promise each other bit for
+// bit (restricted64_kernels.h) holds because they run this text.
 //
 // The FAST sum computes R targets at once from the same source reads (the bodies' kernels have R = 1).  The targets are
 // independent of one another: every target has its own accumulators, and its operations and their order do not depend on R.

@@ -1,7 +1,8 @@
 // What is f64 about an ensemble, for the driver of ensemble_driver.h: the masses kept as the caller's u32 weights (the kernel
 // converts on use, `weight as f64` is exact), the opt-in FAST rule of the f64 direct step, the kernel of ensemble64_kernels.hip.
-// Internal; ensemble64.hip (nbody_ensemble64_*), ragged64.hip (nbody_ragged64_*) and restricted64.hip (nbody_restricted64_*,
-// which adds the tracers' launch for restricted_driver.h) build their handles over it.
+// Internal; ensemble64.hip (nbody_ensemble64_*), ragged64.hip (nbody_ragged64_*), restricted64.hip (nbody_restricted64_*,
+// which adds the tracers' launch for restricted_driver.h) and rr64.hip (nbody_rr64_*, which adds the tracers' launch over work
+// items for rr_driver.h) build their handles over it.
 #pragma once
 #include "ensemble64_kernels.h"
 #include "ensemble_driver.h"

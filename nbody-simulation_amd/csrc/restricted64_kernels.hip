@@ -8,13 +8,15 @@
 // The staging, the EXACT chain and the FAST sum are ensemble64_world.h's, the text the bodies' kernel runs; a lane carries R
 // tracers through them, R rows of 256 apart (coalesced), each with its own accumulators — a tracer's order of additions does not
 // know R.  Lanes past the end of a world's tracers compute a tracer at (0, 0) and store nothing.  No static LDS.
+// The block's body is rst64_world_tile (restricted64_device.h), shared with the ragged restricted kernel of rr64_kernels.hip: this
+// kernel only says which world and which tile a block is.
 //
 // This translation unit is compiled with -ffp-contract=off: nothing fuses unless written as an fma.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/nbody_hip.h"
-#include "ensemble64_world.h"
+#include "restricted64_device.h"
 #include "restricted64_kernels.h"
 
 namespace nbody {
@@ -22,50 +24,15 @@ namespace {
 
 template <int R>
 __global__ __launch_bounds__(kEnsembleBlock) void restricted64_tracers(const Ensemble64Args b, const Restricted64Args t) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char rst64_lds[];
   const int n = b.n_bodies;
   const unsigned world = blockIdx.x / t.tiles, tile = blockIdx.x - world * t.tiles;
-  const Ens64WorldLds w(rst64_lds, n);
-  const int hazard = ens64_stage_world(w, b.pos_in, b.weight, (size_t)world * (size_t)n, b.fast);
-  const double clamp = b.clamp;
-
-  const int64_t first = (int64_t)tile * (kEnsembleBlock * R) + (int64_t)threadIdx.x;  // this lane's tracers: first + r * 256
-  const size_t base = (size_t)world * (size_t)t.n_tracers;
-  double px[R], py[R], ax[R], ay[R];
-  bool own_exact = false;
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int64_t k = first + (int64_t)r * kEnsembleBlock;
-    const double2 p = k < t.n_tracers ? t.tpos[base + (size_t)k] : double2{0.0, 0.0};
-    px[r] = p.x, py[r] = p.y;
-    own_exact |= outside_fast(p.x) || outside_fast(p.y);
-  }
-
-  // (no barrier follows the staging: the lanes may part)
-  if (!hazard) ens64_fast_sum<1, R>(w, 0, px, py, clamp, ax, ay);
-  if (hazard || own_exact) {  // an EXACT world: every tracer; a FAST world, rare: the tracers outside FAST's domain — one by one
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      if (!(hazard || outside_fast(px[r]) || outside_fast(py[r]))) continue;
-      ens64_exact_sum(w, px[r], py[r], clamp, ax[r], ay[r]);
-    }
-  }
-
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int64_t k = first + (int64_t)r * kEnsembleBlock;
-    if (k >= t.n_tracers) continue;
-    const size_t row = base + (size_t)k;
-    if (t.tacc_out) t.tacc_out[row] = double2{ax[r], ay[r]};
-    if (t.tvel) {  // main.rs:419-423, multiply then add, no contraction (TU flag)
-      double2 v = t.tvel[row];
-      v.x = v.x + ax[r] * b.delta;
-      v.y = v.y + ay[r] * b.delta;
-      const double sx = v.x * b.delta, sy = v.y * b.delta;
-      t.tvel[row] = v;
-      t.tpos[row] = double2{px[r] + sx, py[r] + sy};
-    }
-  }
+  constexpr int64_t per_block = (int64_t)kEnsembleBlock * R;
+  const int64_t first = (int64_t)tile * per_block;  // the tile's first tracer among its world's
+  const int64_t left = t.n_tracers - first;
+  Tracer64Rows rows;
+  rows.tpos = t.tpos, rows.tvel = t.tvel, rows.tacc_out = t.tacc_out;
+  rst64_world_tile<R>(b, rows, n, (size_t)world * (size_t)n, (size_t)world * (size_t)t.n_tracers + (size_t)first,
+                      (int)(left < per_block ? left : per_block));
 }
 
 }  // namespace

@@ -1,0 +1,50 @@
+// Ragged restricted ensembles in f64: the tracers' step from a table of work items (rr64_kernels.h).
+//
+// What every tracer computes is what restricted64_kernels.hip states, in double:
+//   a_t = sum_j calculate_gravity(p_t, p_j, w_j as f64) over the bodies of its own world, j ascending      src/main.rs:234-253
+//   v_t += a_t*dt ; x_t += v_t*dt                                                                          src/main.rs:419-423
+// and the block's body is the same text, rst64_world_tile (restricted64_device.h): this kernel only reads which world and which
+// of its tracers a block is from its work item, where the uniform kernel computes them from blockIdx.
+//
+// This translation unit is compiled with -ffp-contract=off: nothing fuses unless written as an fma.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/nbody_hip.h"
+#include "restricted64_device.h"
+#include "rr64_kernels.h"
+
+namespace nbody {
+namespace {
+
+// The block's work item {body_row0, n, tracer_row0, count} is the same in every lane (a scalar load), so n and count are
+// uniform: the barriers of the staging see every thread.  Dynamic LDS is the launch's; the kernel uses no other.
+template <int R>
+__global__ __launch_bounds__(kEnsembleBlock) void rr64_tracers(const Ensemble64Args b, const Rr64TracerArgs t, const uint4* __restrict__ items) {
+  const uint4 item = items[blockIdx.x];
+  const size_t body_row0 = (size_t)(unsigned)__builtin_amdgcn_readfirstlane(item.x);
+  const int n = (int)__builtin_amdgcn_readfirstlane(item.y);
+  const size_t tracer_row0 = (size_t)(unsigned)__builtin_amdgcn_readfirstlane(item.z);
+  const int count = (int)__builtin_amdgcn_readfirstlane(item.w);
+  Tracer64Rows rows;
+  rows.tpos = t.tpos, rows.tvel = t.tvel, rows.tacc_out = t.tacc_out;
+  rst64_world_tile<R>(b, rows, n, body_row0, tracer_row0, count);
+}
+
+}  // namespace
+
+hipError_t launch_rr64_tracers(hipStream_t s, int64_t blocks, size_t lds_bytes, const uint4* items, const Ensemble64Args& bodies,
+                               const Rr64TracerArgs& t) {
+  if (blocks < 1 || blocks > kEnsembleMaxRows || !items || lds_bytes > ensemble64_lds_bytes(kEnsembleMaxBodies) || !t.tpos ||
+      !bodies.pos_in || !bodies.weight)
+    return hipErrorInvalidValue;
+  if (lds_bytes > 65536) {  // its own function, so its own limit: the uniform kernel's and the bodies' raised ones do not cover it
+    static std::atomic<bool> raised[64];
+    const hipError_t h = ens64_raise_lds_limit(reinterpret_cast<const void*>(&rr64_tracers<kRestricted64PerLane>), raised);
+    if (h != hipSuccess) return h;
+  }
+  hipLaunchKernelGGL(rr64_tracers<kRestricted64PerLane>, dim3((unsigned)blocks), dim3(kEnsembleBlock), lds_bytes, s, bodies, t, items);
+  return hipGetLastError();
+}
+
+}  // namespace nbody

@@ -397,10 +397,12 @@ class RaggedEnsemble64(_RaggedBase):
         self._create(positions, velocities, weights, device, clamp, arith)
 
 
-def _checked_rr_tracers(tracers, sizes, who="RaggedRestrictedEnsemble"):
-    """tracers: None, or one entry per world, each None or a pair (position[m_k, 2], velocity[m_k, 2]) of float32 ->
+def _checked_rr_tracers(tracers, sizes, who="RaggedRestrictedEnsemble", dtype=np.float32, other=None):
+    """tracers: None, or one entry per world, each None or a pair (position[m_k, 2], velocity[m_k, 2]) of `dtype` ->
     (counts int64[B], position[rows, 2], velocity[rows, 2]), the worlds' tracer rows one after another (both None where no
-    world has a tracer); ValueError for anything else.  Nothing is copied before every world has passed."""
+    world has a tracer); ValueError for anything else.  Nothing is copied before every world has passed.  A wrong dtype adds
+    `other` to the message where one is given: which class takes the other one."""
+    dtype = np.dtype(dtype)
     b = len(sizes)
     counts = np.zeros(b, np.int64)
     if tracers is None:
@@ -416,8 +418,8 @@ def _checked_rr_tracers(tracers, sizes, who="RaggedRestrictedEnsemble"):
             raise ValueError(f"{who}: world {k}: tracers must be None or a pair (position[m, 2], velocity[m, 2])")
         tp, tv = np.asarray(entry[0]), np.asarray(entry[1])
         for name, a in (("tracer position", tp), ("tracer velocity", tv)):
-            if a.dtype != np.float32:
-                raise ValueError(f"{who}: world {k}: {name} must be float32 (got {a.dtype})")
+            if a.dtype != dtype:
+                raise ValueError(f"{who}: world {k}: {name} must be {dtype} (got {a.dtype})" + (f"; {other}" if other else ""))
         if tp.ndim != 2 or tp.shape[1] != 2:
             raise ValueError(f"{who}: world {k}: tracer position must be [m, 2], got {tp.shape}")
         if tv.shape != tp.shape:
@@ -442,14 +444,16 @@ class RaggedRestrictedEnsemble(_RaggedBase):
     alone, AUTO per world and per step on the device with the per-tracer exception of `RestrictedEnsemble`."""
     _dtype = np.float32
     _who = "RaggedRestrictedEnsemble"
+    _other = "it takes float32 only"  # what a wrong dtype of the bodies adds to the message
+    _tracer_other = None              # and of the tracers
 
     @staticmethod
     def _new_handle(device):
         return _capi.RRHandle(device)
 
     def _check(self, positions, velocities, weights, tracers):
-        args = _checked_ragged(positions, velocities, weights, self._dtype, who=self._who, other="it takes float32 only")
-        return args, _checked_rr_tracers(tracers, args[0], self._who)
+        args = _checked_ragged(positions, velocities, weights, self._dtype, who=self._who, other=self._other)
+        return args, _checked_rr_tracers(tracers, args[0], self._who, self._dtype, self._tracer_other)
 
     def __init__(self, positions, velocities, weights=None, tracers=None, *, device=0, clamp=0.001, arith="auto"):
         if arith not in _ARITH:
@@ -475,7 +479,7 @@ class RaggedRestrictedEnsemble(_RaggedBase):
     def set_tracers(self, tracers):
         """Replaces the tracers: a list with one entry per world, each None or (position[m_k, 2], velocity[m_k, 2]); None, or no
         tracer in any world, removes them."""
-        self._upload_tracers(*_checked_rr_tracers(tracers, self._sizes, self._who))
+        self._upload_tracers(*_checked_rr_tracers(tracers, self._sizes, self._who, self._dtype, self._tracer_other))
 
     @property
     def sizes(self):
@@ -495,16 +499,35 @@ class RaggedRestrictedEnsemble(_RaggedBase):
         return self._per_world_tracers(self.h.tracers_accel())
 
 
-def rr_plan(sizes, tracer_counts):
-    """The launches the TRACERS of a RaggedRestrictedEnsemble of these sizes and tracer counts take per step (nbody_rr_plan; host
-    code, no GPU needed; the bodies' launches are `ragged_plan(sizes)`) -> dict: launch_of_world, first_block_of_world (a
-    world's blocks are contiguous in its launch; both -1 for a world without tracers), lds_bytes and blocks per launch."""
+class RaggedRestrictedEnsemble64(RaggedRestrictedEnsemble):
+    """The ragged restricted ensemble in double precision (nbody_rr64_*): the same constructor and methods, float64 arrays
+    only.  The bodies are bit-identical to a `RaggedEnsemble64` of the same worlds; a tracer is under arith "exact" and "auto"
+    (the exact chain, as for every float64 class) bit-identical to the oracle's float64 direct_accel at it + Euler, and under
+    "fast" (opt-in, gated per world and per step on the device, with the per-tracer exception) bit-identical to a
+    `RestrictedEnsemble64` holding its world alone.  clamp is a float, widened to double by the library."""
+    _dtype = np.float64
+    _who = "RaggedRestrictedEnsemble64"
+    _other = _tracer_other = "RaggedRestrictedEnsemble takes float32"
+
+    @staticmethod
+    def _new_handle(device):
+        return _capi.RR64Handle(device)
+
+
+def rr_plan(sizes, tracer_counts, dtype=np.float32):
+    """The launches the TRACERS of a RaggedRestrictedEnsemble (dtype float64: a RaggedRestrictedEnsemble64) of these sizes and
+    tracer counts take per step (nbody_rr_plan / nbody_rr64_plan; host code, no GPU needed; the bodies' launches are
+    `ragged_plan(sizes, dtype)`) -> dict: launch_of_world, first_block_of_world (a world's blocks are contiguous in its launch;
+    both -1 for a world without tracers), lds_bytes and blocks per launch."""
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError(f"rr_plan: dtype must be float32 or float64, got {dtype}")
     sizes, counts = [int(n) for n in sizes], [int(m) for m in tracer_counts]
     if not sizes or min(sizes) < 1 or max(sizes) > MAX_BODIES or sum(sizes) > MAX_ROWS:
         raise ValueError(f"rr_plan: at least one world, 1 .. {MAX_BODIES} bodies per world, at most 2^26 in all")
     if len(counts) != len(sizes) or min(counts) < 0 or sum(counts) > MAX_ROWS:
         raise ValueError("rr_plan: one tracer count >= 0 per world, at most 2^26 tracers in all")
-    launch, first, lds, blocks = _capi.rr_plan(sizes, counts)
+    launch, first, lds, blocks = _capi.rr_plan(sizes, counts, f64=dtype == np.float64)
     return dict(launch_of_world=launch, first_block_of_world=first, lds_bytes=lds, blocks=blocks)
 
 

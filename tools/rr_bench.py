@@ -3,6 +3,7 @@
 GPU, the same process.
 
     python tools/rr_bench.py [--out FILE] [--shapes 256:64-2048:256-16384] [--steps 20] [--reps 3] [--leg-timeout 240]
+                             [--dtype f32|f64]
 
 A shape B:lo-hi:mlo-mhi is B worlds whose sizes are drawn uniformly from lo .. hi and whose tracer counts are drawn uniformly
 from mlo .. mhi (seeded).  For every shape and for FAST and EXACT arithmetic one LEG runs once, in a child process of its own
@@ -14,6 +15,8 @@ started):
 Both are warmed up by one call, then timed `reps` times alternately with the host clock around the whole call — every call ends
 in a synchronise of its stream.  The pair rate is steps * sum (n_k^2 + m_k n_k) pairs per call at 14 flop per pair,
 against the 157.3 TFLOP/s f32 peak: an end-to-end figure of the call, launches and synchronise included, not a kernel's.
+--dtype f64 measures nb.RaggedRestrictedEnsemble64 against one nb.RestrictedEnsemble64 per distinct (n, m), the rate against the
+78.6 TFLOP/s f64 vector peak; FAST is then the opt-in arithmetic, EXACT the default chain.
 This is a tool, not a test: it needs an MI355X and fails without one.
 """
 import argparse
@@ -28,6 +31,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 PEAK_F32 = 157.3e12
+PEAK_F64 = 78.6e12    # vector f64, AMD's public figure
 FLOP_PER_PAIR = 14
 
 
@@ -38,11 +42,13 @@ def parse_shape(shape):
     return int(b), lo, hi, mlo, mhi
 
 
-def leg(shape, arith, steps, reps):
+def leg(shape, arith, steps, reps, f64=False):
     import numpy as np
     import nbody_simulation_amd as nb
     b, lo, hi, mlo, mhi = parse_shape(shape)
-    real = np.float32
+    real = np.float64 if f64 else np.float32
+    ragged_cls, uniform_cls = ((nb.RaggedRestrictedEnsemble64, nb.RestrictedEnsemble64) if f64 else
+                               (nb.RaggedRestrictedEnsemble, nb.RestrictedEnsemble))
     rng = np.random.default_rng(0x7A66ED)
     sizes = rng.integers(lo, hi + 1, b).tolist()
     counts = rng.integers(mlo, mhi + 1, b).tolist()
@@ -54,14 +60,14 @@ def leg(shape, arith, steps, reps):
     for k, m in enumerate(counts):   # tracers scattered over their world's extent, at rest relative to its centre
         c, s = pos[k].mean(axis=0), pos[k].std(axis=0) + 1.0
         tracers.append((np.ascontiguousarray(c + s * rng.normal(0, 1, (m, 2)), real), np.zeros((m, 2), real)))
-    one = nb.RaggedRestrictedEnsemble(pos, vel, wgt, tracers, arith=arith)
+    one = ragged_cls(pos, vel, wgt, tracers, arith=arith)
     groups = {}
     for k, nm in enumerate(zip(sizes, counts)):
         groups.setdefault(nm, []).append(k)
-    per_shape = [nb.RestrictedEnsemble(np.stack([pos[k] for k in ks]), np.stack([vel[k] for k in ks]), np.stack([wgt[k] for k in ks]),
-                                       (np.stack([tracers[k][0] for k in ks]), np.stack([tracers[k][1] for k in ks])), arith=arith)
+    per_shape = [uniform_cls(np.stack([pos[k] for k in ks]), np.stack([vel[k] for k in ks]), np.stack([wgt[k] for k in ks]),
+                             (np.stack([tracers[k][0] for k in ks]), np.stack([tracers[k][1] for k in ks])), arith=arith)
                  for _, ks in sorted(groups.items())]
-    bplan, tplan = nb.ragged_plan(sizes), nb.rr_plan(sizes, counts)
+    bplan, tplan = nb.ragged_plan(sizes, dtype=real), nb.rr_plan(sizes, counts, dtype=real)
 
     def run_one():
         t = time.perf_counter()
@@ -103,25 +109,28 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--leg-timeout", type=float, default=240.0)
+    ap.add_argument("--dtype", choices=("f32", "f64"), default="f32")
     ap.add_argument("--leg", help=argparse.SUPPRESS)   # SHAPE/arith — the child process of one leg
     a = ap.parse_args()
     if a.leg:
         shape, arith = a.leg.split("/")
-        print("LEG " + json.dumps(leg(shape, arith, a.steps, a.reps)), flush=True)
+        print("LEG " + json.dumps(leg(shape, arith, a.steps, a.reps, f64=a.dtype == "f64")), flush=True)
         return 0
     if not os.path.exists("/dev/kfd"):
         print("rr_bench: no GPU here; a measurement path does not fall back", file=sys.stderr)
         return 2
-    lines = [f"# tools/rr_bench.py: steps per call {a.steps}, timed calls per side {a.reps} (alternating, after one warm-up call each)",
+    f64 = a.dtype == "f64"
+    peak = PEAK_F64 if f64 else PEAK_F32
+    lines = [f"# tools/rr_bench.py{' --dtype f64' if f64 else ''}: steps per call {a.steps}, timed calls per side {a.reps} (alternating, after one warm-up call each)",
              "# shape B:lo-hi:mlo-mhi = B worlds, sizes drawn uniformly from lo .. hi, tracer counts from mlo .. mhi (seeded);",
-             "# per shape = one nb.RestrictedEnsemble per distinct (n, m), each update() in turn",
+             f"# per shape = one nb.RestrictedEnsemble{'64' if f64 else ''} per distinct (n, m), each update() in turn",
              "# seconds are host-clock times of one whole call (it ends in a stream synchronise); ratio = per shape / one handle (medians)",
              f"# rate = steps * sum (n_k^2 + m_k n_k) pairs per call * {FLOP_PER_PAIR} flop over the median time of the one handle, as a share of "
-             f"{PEAK_F32 / 1e12:.1f} TFLOP/s (end to end)",
+             f"{peak / 1e12:.1f} TFLOP/s (end to end)",
              f"{'shape':>24} {'arith':>6} {'one_handle_s (each call)':>28} {'per_shape_s (each call)':>28} {'ratio':>7} {'TFLOP/s':>8} {'of peak':>8}   plan"]
     for shape in a.shapes.split(","):
         for arith in ("fast", "exact"):
-            cmd = [sys.executable, os.path.abspath(__file__), "--leg", f"{shape}/{arith}", "--steps", str(a.steps), "--reps", str(a.reps)]
+            cmd = [sys.executable, os.path.abspath(__file__), "--leg", f"{shape}/{arith}", "--steps", str(a.steps), "--reps", str(a.reps)] + (["--dtype", "f64"] if f64 else [])
             try:
                 r = subprocess.run(cmd, capture_output=True, text=True, timeout=a.leg_timeout)
             except subprocess.TimeoutExpired:
@@ -138,7 +147,7 @@ def main():
             m1, mp = t1[len(t1) // 2], tp[len(tp) // 2]
             flops = d["pairs"] * d["steps"] * FLOP_PER_PAIR / m1
             lines.append(f"{shape:>24} {arith:>6} {' '.join(f'{t:.5f}' for t in d['one_s']):>28} {' '.join(f'{t:.5f}' for t in d['per_shape_s']):>28} "
-                         f"{mp / m1:7.2f} {flops / 1e12:8.2f} {100 * flops / PEAK_F32:7.1f}%   {d['rows']} rows, {d['tracer_rows']} tracers, "
+                         f"{mp / m1:7.2f} {flops / 1e12:8.2f} {100 * flops / peak:7.1f}%   {d['rows']} rows, {d['tracer_rows']} tracers, "
                          f"{d['distinct']} distinct (n, m), {d['launches']} launches of {d['blocks']} blocks per step, "
                          f"bits {'equal' if d['same_bits'] else 'DIFFER'}")
         else:
