@@ -496,6 +496,17 @@ int nbody_selftest_walk_estimate(int device, const uint32_t* hist, int64_t hist_
                                  int nodes, int node_count, int fallback, int bad_index, int long_nodes_at_level_end, int level_end,
                                  int node_cap, int keep_scratch, uint32_t* out_off, int32_t* out_info, int32_t* out_verdict,
                                  int32_t* out_pack, int32_t* out_flags, int32_t* out_clear, int64_t clear_words, int64_t* out_used);
+/* The near/far split of a direct step's sources alone on device `device` — no main pass, no finish — over n host bodies
+ * (1 <= n <= 2^24), called exactly as a step without mass classes calls it.  pos_xy: x y per body; mass: n floats or NULL
+ * (needed when heavy_base > 0 or with_minv); heavy_base > 0: bodies of another mass are near too (the sparse route); use_hazard:
+ * FAST's domain check rides along; couples: the far copy in couples {xA, xB, yA, yB}, padded to a multiple of 16 slots;
+ * with_minv (couples only): the inverse masses beside it.  The scratch holds 0xA5 bytes before the call, the flag words zeros.
+ * Out: flags[4] as nbody_direct_workspace_peek lists them, is_near[n], scan[n] (its exclusive sum), near_list[n] of which the
+ * first flags[2] entries are written, far: 2 * 16 * ceil(n / 16) floats with couples, 2 n without, minv: 16 * ceil(n / 16)
+ * floats (with_minv; else may be NULL).  Needs a GPU. */
+int nbody_selftest_nearfar(int device, const float* pos_xy, const float* mass, int64_t n, float heavy_base, float clamp, int use_hazard,
+                           int couples, int with_minv, int32_t* out_flags, uint32_t* out_is_near, uint32_t* out_scan,
+                           uint32_t* out_near_list, float* out_far, float* out_minv);
 /* Restarts of that scan during the last device BVH build of this context (diagnostic; 0 after a host build). */
 int nbody_bvh_build_restarts(const nbody_ctx* ctx);
 /* 1 if the last tree build of this context ran on the device, 0 if the host builder did it (the device builders

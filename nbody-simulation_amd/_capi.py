@@ -255,6 +255,7 @@ _SIGS = {
     "nbody_selftest_div_pair": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_int64, _vp, _vp]),
     "nbody_selftest_exact_sum_chunked": (C.c_int, [_vp, C.c_int64, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int64)]),
     "nbody_selftest_walk_estimate": (C.c_int, [_i32, _vp, _i64, _vp, _i64, _i32, _i32] + [_i32] * 8 + [_vp] * 6 + [_i64, _vp]),
+    "nbody_selftest_nearfar": (C.c_int, [_i32, _vp, _vp, _i64, _f32, _f32, _i32, _i32, _i32] + [_vp] * 6),
     "nbody_bvh_build_restarts": (C.c_int, [_vp]),
     "nbody_last_build_on_device": (C.c_int, [_vp]),
     "nbody_timer_create": (C.c_int, [C.POINTER(_vp)]),
@@ -446,6 +447,28 @@ def selftest_walk_estimate(hist, ids, shift=0, route=2, nodes=1, node_count=1, f
                                                     _ptr(flags), _ptr(clear), int(clear_words), _ptr(used)))
     return dict(off=off, info=info, verdict=verdict, pack=pack, flags=flags, clear=clear, extra=int(used[0]), grid_waves=int(used[1]),
                 kept=bool(used[2]))
+
+
+def selftest_nearfar(pos, mass=None, heavy_base=0.0, clamp=0.001, use_hazard=False, couples=True, with_minv=False, device=0):
+    """The near/far split of a direct step alone on the device (nbody_selftest_nearfar) -> dict of flags (hazard, fallback,
+    n_near, state), is_near, scan, near_list (the n_near entries written), far (the raw far copy: 2 * 16 * ceil(n / 16) floats in
+    couples, or (n, 2) without) and minv (16 * ceil(n / 16) floats, or None)."""
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 2)
+    n = pos.shape[0]
+    if mass is not None:
+        mass = np.ascontiguousarray(mass, np.float32)
+        assert mass.shape == (n,)
+    padded = (n + 15) // 16 * 16
+    flags = np.zeros(4, np.int32)
+    is_near, scan, near_list = (np.empty(n, np.uint32) for _ in range(3))
+    far = np.empty(2 * padded if couples else 2 * n, np.float32)
+    minv = np.empty(padded, np.float32) if with_minv else None
+    check(None, load().nbody_selftest_nearfar(int(device), _ptr(pos), _ptr(mass), n, float(heavy_base), float(clamp), 1 if use_hazard else 0,
+                                              1 if couples else 0, 1 if with_minv else 0, _ptr(flags), _ptr(is_near), _ptr(scan),
+                                              _ptr(near_list), _ptr(far), _ptr(minv)))
+    n_near = min(max(int(flags[2]), 0), n)
+    return dict(flags=tuple(int(f) for f in flags), is_near=is_near, scan=scan, near_list=near_list[:n_near].copy(),
+                far=far if couples else far.reshape(n, 2), minv=minv)
 
 
 def selftest_exact_sum_chunked(x, chunk=2048):

@@ -477,6 +477,54 @@ NB_API int nbody_direct_workspace_peek(void* stream, const void* workspace, int3
   return e == hipSuccess ? NBODY_OK : fail_hip(nullptr, e, "workspace_peek");
 }
 
+// The near/far split alone (launch_nearfar: no main pass, no finish) over host arrays, for tests that pin the classifier and
+// what it hands its consumers.  The block is the flag words followed by the near/far scratch, every byte 0xA5 before the flag
+// words are zeroed: a slot the split leaves unwritten shows.
+NB_API int nbody_selftest_nearfar(int device, const float* pos_xy, const float* mass, int64_t n, float heavy_base, float clamp, int use_hazard,
+                                  int couples, int with_minv, int32_t* out_flags, uint32_t* out_is_near, uint32_t* out_scan,
+                                  uint32_t* out_near_list, float* out_far, float* out_minv) {
+  if (!pos_xy || n < 1 || n > ((int64_t)1 << 24) || !out_flags || !out_is_near || !out_scan || !out_near_list || !out_far)
+    return fail(nullptr, NBODY_ERR_INVALID, "selftest_nearfar: bad arguments");
+  if ((!mass && (heavy_base > 0.f || with_minv)) || (with_minv && (!couples || !out_minv)))
+    return fail(nullptr, NBODY_ERR_INVALID, "selftest_nearfar: the inverse masses need masses, couples and a place to go");
+  if (hipSetDevice(device) != hipSuccess) return NBODY_ERR_NO_DEVICE;
+  const NearFarLayout L = nearfar_layout(n);
+  char* block = nullptr;   // flag words | near/far scratch
+  float* in = nullptr;     // positions | masses
+  auto finish = [&](hipError_t e) {
+    (void)hipDeviceSynchronize();
+    (void)hipFree(block);
+    (void)hipFree(in);
+    return e == hipSuccess ? NBODY_OK : fail_hip(nullptr, e, "selftest_nearfar");
+  };
+  hipError_t e;
+  if ((e = hipMalloc((void**)&block, kFlagBytes + L.total)) != hipSuccess) return finish(e);
+  if ((e = hipMalloc((void**)&in, (size_t)n * 3 * sizeof(float))) != hipSuccess) return finish(e);
+  float* mass_d = mass ? in + 2 * n : nullptr;
+  if ((e = hipMemcpy(in, pos_xy, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return finish(e);
+  if (mass && (e = hipMemcpy(mass_d, mass, (size_t)n * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return finish(e);
+  if ((e = hipMemset(block, 0xA5, kFlagBytes + L.total)) != hipSuccess) return finish(e);
+  int* flags = (int*)block;
+  char* scratch = block + kFlagBytes;
+  if ((e = hipMemsetAsync(flags, 0, kFlagBytes, nullptr)) != hipSuccess) return finish(e);
+  const float2* pos_far = nullptr;
+  const uint32_t* near_list = nullptr;
+  const float* minv_far = nullptr;
+  if ((e = launch_nearfar(nullptr, (const float2*)in, mass_d, heavy_base, (int)n, clamp, use_hazard, flags, scratch, L, &pos_far, &near_list, nullptr,
+                          nullptr, 0, couples != 0, with_minv ? &minv_far : nullptr)) != hipSuccess)
+    return finish(e);
+  if ((e = hipDeviceSynchronize()) != hipSuccess) return finish(e);
+  if ((e = hipMemcpy(out_flags, flags, 4 * sizeof(int32_t), hipMemcpyDeviceToHost)) != hipSuccess) return finish(e);
+  if ((e = hipMemcpy(out_is_near, scratch + L.is_near, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess) return finish(e);
+  if ((e = hipMemcpy(out_scan, scratch + L.scan, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess) return finish(e);
+  const int64_t n_near = std::min<int64_t>(std::max<int64_t>(out_flags[kFlagNearCount], 0), n);
+  if (n_near && (e = hipMemcpy(out_near_list, near_list, (size_t)n_near * 4, hipMemcpyDeviceToHost)) != hipSuccess) return finish(e);
+  const size_t far_floats = 2 * (size_t)(couples ? far_padded(n) : n);
+  if ((e = hipMemcpy(out_far, pos_far, far_floats * sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess) return finish(e);
+  if (with_minv && (e = hipMemcpy(out_minv, minv_far, (size_t)far_padded(n) * sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess) return finish(e);
+  return finish(hipSuccess);
+}
+
 NB_API int nbody_weights_to_mass_dev(void* stream, int64_t n, const void* weight_u32, void* mass_f32) {
   if (n < 0 || (n > 0 && (!weight_u32 || !mass_f32))) return fail(nullptr, NBODY_ERR_INVALID, "weights_to_mass: bad arguments");
   hipError_t e = launch_weights_to_mass((hipStream_t)stream, (const uint32_t*)weight_u32, (float*)mass_f32, n);

@@ -305,7 +305,7 @@ def _dev_accel(nb, pos, w, arith=None, uniform=0.0):
 
 @pytest.fixture
 def force_nearfar(monkeypatch):
-    """The split is chosen by problem size (>= 2^33 pairs); these tests force it on small inputs."""
+    """The split is chosen by problem size (>= 2^32 pairs); these tests force it on small inputs."""
     monkeypatch.setenv("NBODY_DIRECT_NEARFAR", "2")
 
 
