@@ -39,7 +39,8 @@
  *   Params.  nbody_default_params' values at creation; clamp and arith are used, the rest is kept and ignored.
  *   Not offered: f64 on this handle (nbody_ensemble64_* below is the double-precision sibling); worlds of different sizes on
  *     this handle (nbody_ragged_* at the end of this file steps them together); a per-world delta or clamp; tree methods;
- *     tracers on this handle (nbody_restricted_* at the end of this file); several devices; snapshots, delta streams and frames of an ensemble; hipGraph replay.  The library reads no
+ *     tracers on this handle (nbody_restricted_* at the end of this file); several devices; snapshots and delta streams of an ensemble
+ *     (frames are offered: nbody_frames_* at the end of this file); hipGraph replay.  The library reads no
  *     environment variable for any of this.
  * Arrays are world-major, [n_worlds][n_bodies] rows, pos / vel interleaved x,y; weight may be NULL (all 1); an upload replaces
  * the previous ensemble, whatever its shape. */
@@ -217,7 +218,8 @@ int nbody_ragged64_plan(int64_t n_worlds, const int64_t* n_bodies, int32_t* laun
  *     NULL handle gives NBODY_ERR_INVALID (0 from nbody_restricted_num_worlds / _num_bodies / _num_tracers);
  *     nbody_restricted_last_error(NULL): the last failed nbody_restricted_create on this thread, in a slot of its own.
  *   Not offered on this handle: f64 (nbody_restricted64_* below is the double-precision sibling); worlds of different sizes
- *     or a per-world n_tracers on this handle (nbody_rr_* at the end of this file offers both); tree methods; several devices; snapshots, delta streams and frames; hipGraph replay.  The
+ *     or a per-world n_tracers on this handle (nbody_rr_* at the end of this file offers both); tree methods; several devices; snapshots and delta streams
+ *     (frames are offered: nbody_frames_restricted at the end of this file); hipGraph replay.  The
  *     library reads no environment variable for any of this. */
 typedef struct nbody_restricted nbody_restricted;
 int nbody_restricted_create(nbody_restricted** out, int device_id);
@@ -343,7 +345,8 @@ int nbody_restricted64_tracers_accel(nbody_restricted64* e, double* acc_xy);    
  *     NBODY_ERR_INVALID (0 from nbody_rr_num_worlds / _num_rows / _num_tracer_rows); nbody_rr_last_error(NULL): the last failed
  *     nbody_rr_create or nbody_rr_plan on this thread, in a slot of its own.
  *   Not offered on this handle: f64 (nbody_rr64_* below is the double-precision sibling); a per-world delta or clamp; tree methods; several
- *     devices; snapshots, delta streams and frames; hipGraph replay.  The library reads no environment variable for any of
+ *     devices; snapshots and delta streams (frames are offered: nbody_frames_rr at the end of this file); hipGraph replay.  The
+ *     library reads no environment variable for any of
  *     this. */
 #define NBODY_RR_MAX_LAUNCHES 12
 typedef struct nbody_rr nbody_rr;
@@ -439,5 +442,40 @@ int nbody_rr64_accel(nbody_rr64* e, double* acc_xy);                            
 int nbody_rr64_tracers_accel(nbody_rr64* e, double* acc_xy);                      /* the tracers; state untouched */
 int nbody_rr64_plan(int64_t n_worlds, const int64_t* n_bodies, const int64_t* n_tracers, int32_t* launch_of_world,
                     int64_t* first_block_of_world, int32_t* n_launches, int32_t* lds_bytes_of_launch, int64_t* blocks_of_launch);
+
+/* ---- frames of an ensemble: every world's draw() raster from one call ---------------------------------------------
+ * The hand-off of a viewer (World::update feeds draw()) for all eight handles above: a contact sheet of the worlds without
+ * downloading their rows and without one context per world.  World k's tile is the reference's draw() (main.rs:41-72) of its
+ * own rows alone, byte for byte what nbody_render_rgba gives for a context holding that world: its bodies in upload order
+ * (ensemble rows never move) and then, where with_tracers != 0, its tracers in upload order as rows n .. n+m-1 of weight 1.
+ *   The prefix.  nbody_frames_<handle>: the names under each handle's own prefix are closed sets, so these calls have a prefix
+ *     of their own, followed by the handle's name.
+ *   Output.  rgba_out is host memory, [n_worlds][render_px][render_px][4] bytes, R G B A.  Per pixel of a world: a row of
+ *     weight > 10 makes it (0,255,0,255); otherwise with c light rows on it, the last of them in row order having
+ *     v = 0x10 + min(((|vx|+|vy|)*10) as u8, 0xef), it is (255, 255-v, 255-v, min(10 c, 250)); without a row it is 0.  Rows
+ *     outside [0, height)^2, and rows with a NaN position, touch nothing.
+ *   Calls.  Synchronous, on the handle's stream.  They read the current positions and write nothing of the state: stepping
+ *     with frames in between gives the bits of stepping alone.  The device scratch (the tiles, the work words, a ragged
+ *     handle's table of row ranges) belongs to the handle, is grown on demand and is freed with its other arrays.
+ *   Tracers.  with_tracers != 0 on a handle that holds no tracers gives the bodies' frames; in the nbody_rr handles a world
+ *     with no tracers is painted from its bodies.
+ *   Routes.  Chosen by render_px alone.  render_px <= 101 (render_px^2 * 8 <= 81 920 bytes of LDS): one launch, one block per
+ *     world, the world's pixels accumulated in LDS.  Above: a zeroed work buffer, one launch over the rows of all worlds, one over
+ *     their pixels.  The bytes are the same.  Where the two cross over in time has not been measured; profiles/
+ *     ensemble_frames.txt records both at neighbouring sizes.
+ *   Refusals.  NBODY_ERR_INVALID before anything is allocated or launched, the message beginning with the handle's word
+ *     ("ensemble", "ragged", "restricted", "ragged restricted") and naming "frames": nothing uploaded; rgba_out NULL; height or
+ *     render_px 0; render_px not dividing height, or height > 2^24 (as nbody_render_rgba refuses them); n_worlds * render_px^2 >
+ *     2^26 pixels; a world whose bodies and tracers together are more than 2^24 rows when tracers are asked for (the message
+ *     names "tracers").  A NULL handle gives NBODY_ERR_INVALID without a message.
+ *   Not offered: a device-pointer variant; the contact sheet itself (tile the frames on the host); snapshots and delta streams. */
+int nbody_frames_ensemble(nbody_ensemble* e, uint32_t height, uint32_t render_px, uint8_t* rgba_out);
+int nbody_frames_ensemble64(nbody_ensemble64* e, uint32_t height, uint32_t render_px, uint8_t* rgba_out);
+int nbody_frames_ragged(nbody_ragged* e, uint32_t height, uint32_t render_px, uint8_t* rgba_out);
+int nbody_frames_ragged64(nbody_ragged64* e, uint32_t height, uint32_t render_px, uint8_t* rgba_out);
+int nbody_frames_restricted(nbody_restricted* e, uint32_t height, uint32_t render_px, int with_tracers, uint8_t* rgba_out);
+int nbody_frames_restricted64(nbody_restricted64* e, uint32_t height, uint32_t render_px, int with_tracers, uint8_t* rgba_out);
+int nbody_frames_rr(nbody_rr* e, uint32_t height, uint32_t render_px, int with_tracers, uint8_t* rgba_out);
+int nbody_frames_rr64(nbody_rr64* e, uint32_t height, uint32_t render_px, int with_tracers, uint8_t* rgba_out);
 
 #endif /* NBODY_ENSEMBLE_H */

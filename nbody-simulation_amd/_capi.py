@@ -200,6 +200,14 @@ _SIGS = {
     "nbody_rr64_accel": (C.c_int, [_vp, _vp]),
     "nbody_rr64_tracers_accel": (C.c_int, [_vp, _vp]),
     "nbody_rr64_plan": (C.c_int, [_i64, _vp, _vp, _vp, _vp, C.POINTER(_i32), _vp, _vp]),
+    "nbody_frames_ensemble": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp]),
+    "nbody_frames_ensemble64": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp]),
+    "nbody_frames_ragged": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp]),
+    "nbody_frames_ragged64": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp]),
+    "nbody_frames_restricted": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_int, _vp]),
+    "nbody_frames_restricted64": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_int, _vp]),
+    "nbody_frames_rr": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_int, _vp]),
+    "nbody_frames_rr64": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_int, _vp]),
     "nbody_accel_tree_f32": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_accel_tree_f64": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_tree_info": (C.c_int, [_vp, C.POINTER(TreeView)]),
@@ -977,6 +985,20 @@ class _EnsembleHandleBase:
         self._check(self._call("_accel" + self._suffix, _ptr(acc)))
         return acc
 
+    _frames_tracers = False   # the handle's nbody_frames_* call takes with_tracers
+
+    def frames(self, height, render_px, tracers=False):
+        """nbody_frames_<handle>: every world's draw() raster of the current rows -> uint8 (worlds, render_px, render_px, 4).
+        Arguments the C call cannot take as uint32 go to it as 0, which it refuses."""
+        height, render_px = (v if 0 <= v < 1 << 32 else 0 for v in (int(height), int(render_px)))
+        worlds = self.shape[0]
+        # more than 2^26 pixels: the library refuses before it writes, so the output is not sized for them
+        out = np.zeros((worlds, render_px, render_px, 4) if worlds * render_px * render_px <= 1 << 26 else (1, 1, 1, 4), np.uint8)
+        name = "nbody_frames_" + self._prefix[len("nbody_"):]
+        args = (height, render_px, 1 if tracers else 0) if self._frames_tracers else (height, render_px)
+        self._check(getattr(self.lib, name)(self.h, *args, _ptr(out)))
+        return out
+
 
 class EnsembleHandle(_EnsembleHandleBase):
     """nbody_ensemble_*: float32 worlds."""
@@ -1029,6 +1051,7 @@ class Ragged64Handle(RaggedHandle):
 class _TracerCalls:
     """The tracer calls of a restricted handle, beside the bodies' calls of the ensemble handle it is mixed into: m tracers per
     world in arrays of the handle's `_dtype`, the typed C calls with its `_suffix`."""
+    _frames_tracers = True
 
     @property
     def n_tracers(self):
@@ -1066,6 +1089,7 @@ class RRHandle(RaggedHandle):
     """nbody_rr_*: float32 worlds of different sizes, each with tracers of its own; the bodies' calls are RaggedHandle's.  The
     tracer rows of all worlds come one after another in world order, as the body rows do."""
     _prefix = "nbody_rr"
+    _frames_tracers = True
 
     @property
     def n_tracer_rows(self):

@@ -22,3 +22,7 @@ NB_API int nbody_ensemble_update_f32(nbody_ensemble* e, float delta, int n_steps
   return ens_update<EnsF32>(e, delta, n_steps, counter);
 }
 NB_API int nbody_ensemble_accel_f32(nbody_ensemble* e, float* acc_xy) { return ens_accel<EnsF32>(e, acc_xy); }
+// (frames of every world, ensemble_frames.h: a prefix of its own, defined here where the handle is a complete type)
+NB_API int nbody_frames_ensemble(nbody_ensemble* e, uint32_t height, uint32_t render_px, uint8_t* rgba_out) {
+  return ens_frames<EnsF32>(e, height, render_px, rgba_out);
+}

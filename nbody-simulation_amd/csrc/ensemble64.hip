@@ -22,3 +22,7 @@ NB_API int nbody_ensemble64_update(nbody_ensemble64* e, double delta, int n_step
   return ens_update<EnsF64>(e, delta, n_steps, counter);
 }
 NB_API int nbody_ensemble64_accel(nbody_ensemble64* e, double* acc_xy) { return ens_accel<EnsF64>(e, acc_xy); }
+// (frames of every world, ensemble_frames.h: a prefix of its own, defined here where the handle is a complete type)
+NB_API int nbody_frames_ensemble64(nbody_ensemble64* e, uint32_t height, uint32_t render_px, uint8_t* rgba_out) {
+  return ens_frames<EnsF64>(e, height, render_px, rgba_out);
+}

@@ -15,13 +15,17 @@
 // functions below, which take the number of rows and the step's launches from their caller.
 // The restricted handle (restricted_driver.h: tracers beside the bodies, a second launch per step) is the whole of this driver
 // under its own kWho, with the tracers' launch added to a step through ens_update_with.
+// Frames (nbody_frames_*, ensemble_frames.h) are ens_frames below for every handle: the ragged, restricted and ragged restricted
+// drivers hand it their row ranges in a FrameRows and nothing else.
 #pragma once
+#include <algorithm>
 #include <cstring>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "driver.h"
+#include "ensemble_frames.h"
 #include "ensemble_kernels.h"
 
 namespace nbody {
@@ -40,6 +44,13 @@ template <class P> struct EnsembleState {
   typename P::Vec2* vel = nullptr;
   typename P::Mass* mass = nullptr;
   typename P::Vec2* acc = nullptr;
+  // frames (ens_frames): device scratch grown on demand, and a ragged handle's table of row ranges, uploaded by the first frames
+  // call after an upload of bodies or tracers.  Freed with the arrays above.
+  uint8_t* frame_rgba = nullptr;
+  uint32_t* frame_work = nullptr;
+  FrameWorld* frame_table = nullptr;
+  size_t frame_rgba_bytes = 0, frame_work_bytes = 0;
+  bool frame_table_valid = false;
 };
 
 template <class P> thread_local std::string g_ens_create_error;  // one per precision: what a failed create left for its thread
@@ -59,6 +70,9 @@ template <class P> int ens_fail_hip(EnsembleState<P>* e, hipError_t h, const cha
 
 template <class P> void ens_free(EnsembleState<P>* e) {
   free_dev(e->pos[0]); free_dev(e->pos[1]); free_dev(e->vel); free_dev(e->mass); free_dev(e->acc);
+  free_dev(e->frame_rgba); free_dev(e->frame_work); free_dev(e->frame_table);
+  e->frame_rgba_bytes = e->frame_work_bytes = 0;
+  e->frame_table_valid = false;
   e->n_worlds = e->n_bodies = e->rows = 0;
   e->cur = 0;
 }
@@ -242,6 +256,85 @@ template <class P, class Launch> int ens_accel_with(EnsembleState<P>* e, typenam
 
 template <class P> int ens_accel(EnsembleState<P>* e, typename P::Real* acc_xy) {
   return ens_accel_with(e, acc_xy, [e](const typename P::Args& a) { return P::launch(e->stream, e->n_worlds, a); });
+}
+
+// ---- frames: every world's draw() raster (ensemble_frames.h) of the current positions, into host memory
+// What a handle tells ens_frames about its rows, beyond the bodies of worlds of one size.
+template <class P> struct FrameRows {
+  const int64_t* sizes = nullptr;         // worlds of different sizes: the bodies per world; NULL: e->n_bodies in every world
+  const int64_t* counts = nullptr;        // with sizes: the tracers per world, or NULL: none (kept whether or not they are painted)
+  int64_t n_tracers = 0;                  // without sizes: the tracers per world
+  const typename P::Vec2* tpos = nullptr; // the tracers to paint after the bodies, or NULL: the bodies' frames
+  const typename P::Vec2* tvel = nullptr;
+};
+
+// A device buffer of at least `need` bytes; a smaller one is freed and replaced.
+template <class P, class B> int ens_frame_buffer(EnsembleState<P>* e, B*& p, size_t& bytes, size_t need) {
+  if (bytes >= need) return NBODY_OK;
+  free_dev(p);
+  bytes = 0;
+  ENS_HIPCHK(e, hipMalloc((void**)&p, need));
+  bytes = need;
+  return NBODY_OK;
+}
+
+// rgba_out: [n_worlds][render_px][render_px][4] bytes.  Synchronous, on the handle's stream; reads pos[cur], writes no state.
+// Every refusal comes before anything is allocated or launched.
+template <class P>
+int ens_frames(EnsembleState<P>* e, uint32_t height, uint32_t render_px, uint8_t* rgba_out, const FrameRows<P>& rows = FrameRows<P>()) {
+  if (!e) return NBODY_ERR_INVALID;
+  const std::string who = std::string(P::kWho) + " frames: ";
+  if (!e->n_worlds) return ens_fail(e, NBODY_ERR_INVALID, who + "nothing uploaded");
+  if (!rgba_out) return ens_fail(e, NBODY_ERR_INVALID, who + "rgba_out is NULL");
+  // main.rs:51-52 divide by HEIGHT / RENDER_HEIGHT: a cell of 0 world units or a last cell past the frame is an out-of-range
+  // index upstream (a panic): refused, as nbody_render_rgba refuses it
+  if (height == 0 || render_px == 0) return ens_fail(e, NBODY_ERR_INVALID, who + "height and render_px must be > 0");
+  if (height % render_px != 0 || height > kFrameMaxHeight)
+    return ens_fail(e, NBODY_ERR_INVALID, who + "render_px must divide height (height <= 2^24)");
+  const int64_t npix = (int64_t)render_px * render_px;  // <= 2^48
+  if (e->n_worlds > kFrameMaxPixels / npix) return ens_fail(e, NBODY_ERR_INVALID, who + "n_worlds * render_px^2 must be <= 2^26 pixels");
+  const bool tracers = rows.tpos != nullptr;
+  int64_t max_rows = e->n_bodies + (tracers ? rows.n_tracers : 0);
+  if (rows.sizes)
+    for (int64_t k = 0; k < e->n_worlds; ++k) max_rows = std::max(max_rows, rows.sizes[k] + (tracers && rows.counts ? rows.counts[k] : 0));
+  // (a world has at most 4096 bodies: only the sum with its tracers can pass 2^24)
+  if (max_rows > kFrameMaxRows)
+    return ens_fail(e, NBODY_ERR_INVALID, who + "a world's bodies and tracers together must be <= 2^24 rows (paint it without tracers)");
+
+  ENS_HIPCHK(e, hipSetDevice(e->device));
+  const bool lds = frame_route_lds(render_px);
+  if (int rc = ens_frame_buffer(e, e->frame_rgba, e->frame_rgba_bytes, (size_t)(e->n_worlds * npix) * 4)) return rc;
+  if (!lds)
+    if (int rc = ens_frame_buffer(e, e->frame_work, e->frame_work_bytes, (size_t)(e->n_worlds * npix) * 2 * sizeof(uint32_t))) return rc;
+  if (rows.sizes && !e->frame_table_valid) {
+    std::vector<FrameWorld> table((size_t)e->n_worlds);
+    int64_t row0 = 0, trow0 = 0;
+    for (int64_t k = 0; k < e->n_worlds; ++k) {
+      const int64_t m = rows.counts ? rows.counts[k] : 0;
+      table[(size_t)k] = FrameWorld{(uint32_t)row0, (uint32_t)rows.sizes[k], (uint32_t)trow0, (uint32_t)m};  // (each sum <= 2^26)
+      row0 += rows.sizes[k];
+      trow0 += m;
+    }
+    if (!e->frame_table) ENS_HIPCHK(e, hipMalloc((void**)&e->frame_table, table.size() * sizeof(FrameWorld)));
+    ENS_HIPCHK(e, hipMemcpyAsync(e->frame_table, table.data(), table.size() * sizeof(FrameWorld), hipMemcpyHostToDevice, e->stream));
+    ENS_HIPCHK(e, hipStreamSynchronize(e->stream));  // (`table` goes out of scope)
+    e->frame_table_valid = true;
+  }
+  FrameArgs a;
+  a.pos = e->pos[e->cur];
+  a.vel = e->vel;
+  a.mass = e->mass;
+  a.tpos = rows.tpos;
+  a.tvel = rows.tvel;
+  a.table = rows.sizes ? e->frame_table : nullptr;
+  a.n_bodies = (uint32_t)e->n_bodies;
+  a.n_tracers = tracers ? (uint32_t)rows.n_tracers : 0u;
+  a.height = height;
+  a.render_px = render_px;
+  ENS_HIPCHK(e, launch_ensemble_frames<typename P::Real>(e->stream, e->n_worlds, max_rows, a, lds ? nullptr : e->frame_work, e->frame_rgba));
+  ENS_HIPCHK(e, hipMemcpyAsync(rgba_out, e->frame_rgba, (size_t)(e->n_worlds * npix) * 4, hipMemcpyDeviceToHost, e->stream));
+  ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
+  return NBODY_OK;
 }
 
 #undef ENS_HIPCHK

@@ -35,6 +35,10 @@ NB_API int nbody_ragged_update_f32(nbody_ragged* e, float delta, int n_steps, nb
   return ragged_update<RagF32>(e, delta, n_steps, counter);
 }
 NB_API int nbody_ragged_accel_f32(nbody_ragged* e, float* acc_xy) { return ragged_accel<RagF32>(e, acc_xy); }
+// (frames of every world, ensemble_frames.h: a prefix of its own, defined here where the handle is a complete type)
+NB_API int nbody_frames_ragged(nbody_ragged* e, uint32_t height, uint32_t render_px, uint8_t* rgba_out) {
+  return ragged_frames<RagF32>(e, height, render_px, rgba_out);
+}
 
 NB_API int nbody_ragged_plan(int64_t n_worlds, const int64_t* n_bodies, int32_t* launch_of_world, int64_t* first_block_of_world,
                              int32_t* n_launches, int32_t* lds_bytes_of_launch, int64_t* blocks_of_launch) {

@@ -32,6 +32,10 @@ NB_API int nbody_ragged64_update(nbody_ragged64* e, double delta, int n_steps, n
   return ragged_update<RagF64>(e, delta, n_steps, counter);
 }
 NB_API int nbody_ragged64_accel(nbody_ragged64* e, double* acc_xy) { return ragged_accel<RagF64>(e, acc_xy); }
+// (frames of every world, ensemble_frames.h: a prefix of its own, defined here where the handle is a complete type)
+NB_API int nbody_frames_ragged64(nbody_ragged64* e, uint32_t height, uint32_t render_px, uint8_t* rgba_out) {
+  return ragged_frames<RagF64>(e, height, render_px, rgba_out);
+}
 
 NB_API int nbody_ragged64_plan(int64_t n_worlds, const int64_t* n_bodies, int32_t* launch_of_world, int64_t* first_block_of_world,
                                int32_t* n_launches, int32_t* lds_bytes_of_launch, int64_t* blocks_of_launch) {

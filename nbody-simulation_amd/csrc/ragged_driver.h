@@ -73,6 +73,14 @@ template <class P> int ragged_accel(RaggedState<P>* e, typename P::Real* acc_xy)
   return ens_accel_with<P>(e, acc_xy, [e](const typename P::Args& a) { return ragged_launch_all<P>(e, a); });
 }
 
+// Frames: the ensemble's, over the row ranges of these sizes.
+template <class P> int ragged_frames(RaggedState<P>* e, uint32_t height, uint32_t render_px, uint8_t* rgba_out) {
+  if (!e) return NBODY_ERR_INVALID;
+  FrameRows<P> rows;
+  rows.sizes = e->sizes.data();
+  return ens_frames<P>(e, height, render_px, rgba_out, rows);
+}
+
 template <class P> int ragged_sizes(const RaggedState<P>* e, int64_t* n_bodies_out) {
   if (!e || !n_bodies_out) return NBODY_ERR_INVALID;
   for (int64_t k = 0; k < e->n_worlds; ++k) n_bodies_out[k] = e->sizes[(size_t)k];

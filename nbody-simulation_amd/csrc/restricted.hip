@@ -38,3 +38,7 @@ NB_API int nbody_restricted_update_f32(nbody_restricted* e, float delta, int n_s
 }
 NB_API int nbody_restricted_accel_f32(nbody_restricted* e, float* acc_xy) { return rst_accel<RstF32>(e, acc_xy); }
 NB_API int nbody_restricted_tracers_accel_f32(nbody_restricted* e, float* acc_xy) { return rst_tracers_accel<RstF32>(e, acc_xy); }
+// (frames of every world, ensemble_frames.h: a prefix of its own, defined here where the handle is a complete type)
+NB_API int nbody_frames_restricted(nbody_restricted* e, uint32_t height, uint32_t render_px, int with_tracers, uint8_t* rgba_out) {
+  return rst_frames<RstF32>(e, height, render_px, with_tracers, rgba_out);
+}

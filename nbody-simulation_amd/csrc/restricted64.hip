@@ -38,3 +38,7 @@ NB_API int nbody_restricted64_update(nbody_restricted64* e, double delta, int n_
 }
 NB_API int nbody_restricted64_accel(nbody_restricted64* e, double* acc_xy) { return rst_accel<Rst64>(e, acc_xy); }
 NB_API int nbody_restricted64_tracers_accel(nbody_restricted64* e, double* acc_xy) { return rst_tracers_accel<Rst64>(e, acc_xy); }
+// (frames of every world, ensemble_frames.h: a prefix of its own, defined here where the handle is a complete type)
+NB_API int nbody_frames_restricted64(nbody_restricted64* e, uint32_t height, uint32_t render_px, int with_tracers, uint8_t* rgba_out) {
+  return rst_frames<Rst64>(e, height, render_px, with_tracers, rgba_out);
+}

@@ -117,6 +117,18 @@ template <class P> int rst_tracers_accel(RestrictedState<P>* e, typename P::Real
   return NBODY_OK;
 }
 
+// Frames: the ensemble's, with the tracers painted after their world's bodies where they are asked for and there are any.
+template <class P> int rst_frames(RestrictedState<P>* e, uint32_t height, uint32_t render_px, int with_tracers, uint8_t* rgba_out) {
+  if (!e) return NBODY_ERR_INVALID;
+  FrameRows<P> rows;
+  if (with_tracers && e->n_tracers) {
+    rows.n_tracers = e->n_tracers;
+    rows.tpos = e->tpos;
+    rows.tvel = e->tvel;
+  }
+  return ens_frames<P>(e, height, render_px, rgba_out, rows);
+}
+
 template <class P> int64_t rst_num_tracers(const RestrictedState<P>* e) { return e ? e->n_tracers : 0; }
 
 #undef RST_HIPCHK

@@ -52,6 +52,10 @@ NB_API int nbody_rr_update_f32(nbody_rr* e, float delta, int n_steps, nbody_coun
 }
 NB_API int nbody_rr_accel_f32(nbody_rr* e, float* acc_xy) { return rr_accel<RrF32>(e, acc_xy); }
 NB_API int nbody_rr_tracers_accel_f32(nbody_rr* e, float* acc_xy) { return rr_tracers_accel<RrF32>(e, acc_xy); }
+// (frames of every world, ensemble_frames.h: a prefix of its own, defined here where the handle is a complete type)
+NB_API int nbody_frames_rr(nbody_rr* e, uint32_t height, uint32_t render_px, int with_tracers, uint8_t* rgba_out) {
+  return rr_frames<RrF32>(e, height, render_px, with_tracers, rgba_out);
+}
 
 NB_API int nbody_rr_plan(int64_t n_worlds, const int64_t* n_bodies, const int64_t* n_tracers, int32_t* launch_of_world,
                          int64_t* first_block_of_world, int32_t* n_launches, int32_t* lds_bytes_of_launch, int64_t* blocks_of_launch) {

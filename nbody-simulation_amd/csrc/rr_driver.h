@@ -32,6 +32,7 @@ template <class P> struct RrState : RaggedState<P> {
     counts.clear();
     tplan = RrPlan();
     tracer_rows = 0;
+    this->frame_table_valid = false;  // (the frames' table of row ranges holds the counts)
   }
 };
 
@@ -150,6 +151,19 @@ template <class P> int rr_tracers_accel(RrState<P>* e, typename P::Real* acc_xy)
   RR_HIPCHK(e, hipMemcpyAsync(acc_xy, e->tacc, bytes, hipMemcpyDeviceToHost, e->stream));
   RR_HIPCHK(e, hipStreamSynchronize(e->stream));
   return NBODY_OK;
+}
+
+// Frames: the ensemble's, over the row ranges of these sizes and counts; a world without tracers is painted from its bodies.
+template <class P> int rr_frames(RrState<P>* e, uint32_t height, uint32_t render_px, int with_tracers, uint8_t* rgba_out) {
+  if (!e) return NBODY_ERR_INVALID;
+  FrameRows<P> rows;
+  rows.sizes = e->sizes.data();
+  if (e->tracer_rows) rows.counts = e->counts.data();
+  if (with_tracers && e->tracer_rows) {
+    rows.tpos = e->tpos;
+    rows.tvel = e->tvel;
+  }
+  return ens_frames<P>(e, height, render_px, rgba_out, rows);
 }
 
 // The sizes and the tracer counts of every world; either output may be NULL.  Without tracers every count is 0.

@@ -31,6 +31,10 @@ map over systems with different numbers of massive bodies, halos with their own 
 with at most twelve launches per step (`ragged_plan` shows the bodies', `rr_plan` the tracers').  The bodies are bit-identical
 to a `RaggedEnsemble` of the same worlds; a tracer is EXACT bit-identical to the oracle, FAST bit-identical to a
 `RestrictedEnsemble` holding its world alone.
+
+Every class has `frames(height, render_px)` (nbody_frames_*): the reference's draw() raster of every world's own rows from one
+call, uint8 [B, render_px, render_px, 4] — the classes with tracers take `tracers=True` to paint them after their world's
+bodies — and `contact_sheet(frames)` tiles such frames into one image on the host.
 """
 from __future__ import annotations
 
@@ -127,6 +131,11 @@ class _EnsembleBase:
     def accel(self):
         """-> acc[B,n,2]: the accelerations at the current positions; the state is untouched."""
         return self.h.accel()
+
+    def frames(self, height=100_000, render_px=100):
+        """-> uint8 [B, render_px, render_px, 4]: the reference's draw() of every world's current rows, each world alone on its
+        own tile, byte for byte `World.frame` of that world; the state is untouched."""
+        return self.h.frames(height, render_px)
 
     def close(self):
         if getattr(self, "h", None) is not None:
@@ -235,6 +244,11 @@ class _RestrictedBase(_EnsembleBase):
     def tracers_accel(self):
         """-> acc[B,m,2]: the accelerations at the tracers' current positions; the state is untouched."""
         return self.h.tracers_accel()
+
+    def frames(self, height=100_000, render_px=100, tracers=False):
+        """-> uint8 [B, render_px, render_px, 4]: draw() of every world's bodies; tracers=True: followed by its tracers as rows
+        of weight 1 (without tracers: the bodies' frames).  The state is untouched."""
+        return self.h.frames(height, render_px, tracers)
 
 
 class RestrictedEnsemble(_RestrictedBase):
@@ -355,6 +369,11 @@ class _RaggedBase:
     def accel(self):
         """-> a list of acc[n_k, 2]: the accelerations at the current positions; the state is untouched."""
         return self._per_world(self.h.accel())
+
+    def frames(self, height=100_000, render_px=100):
+        """-> uint8 [B, render_px, render_px, 4]: the reference's draw() of every world's current rows, each world alone on its
+        own tile, whatever its size; the state is untouched."""
+        return self.h.frames(height, render_px)
 
     def close(self):
         if getattr(self, "h", None) is not None:
@@ -498,6 +517,11 @@ class RaggedRestrictedEnsemble(_RaggedBase):
         """-> a list of acc[m_k, 2]: the accelerations at the tracers' current positions; the state is untouched."""
         return self._per_world_tracers(self.h.tracers_accel())
 
+    def frames(self, height=100_000, render_px=100, tracers=False):
+        """-> uint8 [B, render_px, render_px, 4]: draw() of every world's bodies; tracers=True: followed by its own tracers as
+        rows of weight 1 (a world without tracers: its bodies).  The state is untouched."""
+        return self.h.frames(height, render_px, tracers)
+
 
 class RaggedRestrictedEnsemble64(RaggedRestrictedEnsemble):
     """The ragged restricted ensemble in double precision (nbody_rr64_*): the same constructor and methods, float64 arrays
@@ -512,6 +536,25 @@ class RaggedRestrictedEnsemble64(RaggedRestrictedEnsemble):
     @staticmethod
     def _new_handle(device):
         return _capi.RR64Handle(device)
+
+
+def contact_sheet(frames, cols=None):
+    """Tiles frames [W, px, px, 4] (what `frames()` returns) row-major into one image [ceil(W / cols) * px, cols * px, 4]: world k
+    at tile (k // cols, k % cols).  cols defaults to ceil(sqrt(W)); tiles past the last world stay zero.  Pure numpy."""
+    frames = np.asarray(frames)
+    if frames.ndim != 4 or frames.shape[0] < 1 or frames.shape[1] != frames.shape[2]:
+        raise ValueError(f"contact_sheet: frames must be [W, px, px, channels] with W >= 1, got {frames.shape}")
+    w, px, _, ch = frames.shape
+    if cols is None:
+        cols = int(np.sqrt(w))
+        cols += cols * cols < w      # ceil(sqrt(W)), in integers
+    cols = int(cols)
+    if cols < 1:
+        raise ValueError(f"contact_sheet: cols must be >= 1, got {cols}")
+    rows = -(-w // cols)
+    sheet = np.zeros((rows * cols, px, px, ch), frames.dtype)
+    sheet[:w] = frames
+    return np.ascontiguousarray(sheet.reshape(rows, cols, px, px, ch).transpose(0, 2, 1, 3, 4).reshape(rows * px, cols * px, ch))
 
 
 def rr_plan(sizes, tracer_counts, dtype=np.float32):
