@@ -39,9 +39,9 @@
  *   Params.  nbody_default_params' values at creation; clamp and arith are used, the rest is kept and ignored.
  *   Not offered: f64 on this handle (nbody_ensemble64_* below is the double-precision sibling); worlds of different sizes on
  *     this handle (nbody_ragged_* at the end of this file steps them together); a per-world delta or clamp; tree methods;
- *     tracers on this handle (nbody_restricted_* at the end of this file); several devices; snapshots and delta streams of an ensemble
- *     (frames are offered: nbody_frames_* at the end of this file); hipGraph replay.  The library reads no
- *     environment variable for any of this.
+ *     tracers on this handle (nbody_restricted_* at the end of this file); several devices; asynchronous snapshots and delta streams
+ *     on a copy stream (the synchronous streams are nbody_deltas_* and the frames nbody_frames_*, both at the end of this
+ *     file); hipGraph replay.  The library reads no environment variable for any of this.
  * Arrays are world-major, [n_worlds][n_bodies] rows, pos / vel interleaved x,y; weight may be NULL (all 1); an upload replaces
  * the previous ensemble, whatever its shape. */
 typedef struct nbody_ensemble nbody_ensemble;
@@ -218,9 +218,9 @@ int nbody_ragged64_plan(int64_t n_worlds, const int64_t* n_bodies, int32_t* laun
  *     NULL handle gives NBODY_ERR_INVALID (0 from nbody_restricted_num_worlds / _num_bodies / _num_tracers);
  *     nbody_restricted_last_error(NULL): the last failed nbody_restricted_create on this thread, in a slot of its own.
  *   Not offered on this handle: f64 (nbody_restricted64_* below is the double-precision sibling); worlds of different sizes
- *     or a per-world n_tracers on this handle (nbody_rr_* at the end of this file offers both); tree methods; several devices; snapshots and delta streams
- *     (frames are offered: nbody_frames_restricted at the end of this file); hipGraph replay.  The
- *     library reads no environment variable for any of this. */
+ *     or a per-world n_tracers on this handle (nbody_rr_* at the end of this file offers both); tree methods; several devices; asynchronous snapshots and delta streams
+ *     on a copy stream (the synchronous streams are nbody_deltas_restricted and the frames nbody_frames_restricted, both at the
+ *     end of this file); hipGraph replay.  The library reads no environment variable for any of this. */
 typedef struct nbody_restricted nbody_restricted;
 int nbody_restricted_create(nbody_restricted** out, int device_id);
 void nbody_restricted_destroy(nbody_restricted* e);
@@ -345,9 +345,9 @@ int nbody_restricted64_tracers_accel(nbody_restricted64* e, double* acc_xy);    
  *     NBODY_ERR_INVALID (0 from nbody_rr_num_worlds / _num_rows / _num_tracer_rows); nbody_rr_last_error(NULL): the last failed
  *     nbody_rr_create or nbody_rr_plan on this thread, in a slot of its own.
  *   Not offered on this handle: f64 (nbody_rr64_* below is the double-precision sibling); a per-world delta or clamp; tree methods; several
- *     devices; snapshots and delta streams (frames are offered: nbody_frames_rr at the end of this file); hipGraph replay.  The
- *     library reads no environment variable for any of
- *     this. */
+ *     devices; asynchronous snapshots and delta streams on a copy stream (the synchronous streams are nbody_deltas_rr and the
+ *     frames nbody_frames_rr, both at the end of this file); hipGraph replay.  The library reads no environment variable for any
+ *     of this. */
 #define NBODY_RR_MAX_LAUNCHES 12
 typedef struct nbody_rr nbody_rr;
 int nbody_rr_create(nbody_rr** out, int device_id);
@@ -468,7 +468,8 @@ int nbody_rr64_plan(int64_t n_worlds, const int64_t* n_bodies, const int64_t* n_
  *     render_px 0; render_px not dividing height, or height > 2^24 (as nbody_render_rgba refuses them); n_worlds * render_px^2 >
  *     2^26 pixels; a world whose bodies and tracers together are more than 2^24 rows when tracers are asked for (the message
  *     names "tracers").  A NULL handle gives NBODY_ERR_INVALID without a message.
- *   Not offered: a device-pointer variant; the contact sheet itself (tile the frames on the host); snapshots and delta streams. */
+ *   Not offered: a device-pointer variant; the contact sheet itself (tile the frames on the host); snapshots (the delta
+ *     streams of an ensemble are nbody_deltas_* below). */
 int nbody_frames_ensemble(nbody_ensemble* e, uint32_t height, uint32_t render_px, uint8_t* rgba_out);
 int nbody_frames_ensemble64(nbody_ensemble64* e, uint32_t height, uint32_t render_px, uint8_t* rgba_out);
 int nbody_frames_ragged(nbody_ragged* e, uint32_t height, uint32_t render_px, uint8_t* rgba_out);
@@ -477,5 +478,66 @@ int nbody_frames_restricted(nbody_restricted* e, uint32_t height, uint32_t rende
 int nbody_frames_restricted64(nbody_restricted64* e, uint32_t height, uint32_t render_px, int with_tracers, uint8_t* rgba_out);
 int nbody_frames_rr(nbody_rr* e, uint32_t height, uint32_t render_px, int with_tracers, uint8_t* rgba_out);
 int nbody_frames_rr64(nbody_rr64* e, uint32_t height, uint32_t render_px, int with_tracers, uint8_t* rgba_out);
+
+/* ---- delta streams of an ensemble: every world's NBD1 stream from one call ---------------------------------------
+ * The recording hand-off for all eight handles above: one lossless delta stream per world (the format "NBD1" of
+ * nbody_delta_begin / nbody_delta_end, decoded by nbody_delta_decoder_*, one decoder per world), about a byte per body and step
+ * where the raw rows are 8 or 16, without one context per world.  A segment is one world's bodies or one world's tracers: n rows
+ * in upload order (ensemble rows never move: no ids, no scatter).
+ *   The prefix.  nbody_deltas_<handle> — with the s: the names under each handle's own prefix, under nbody_frames_ and under
+ *     nbody_delta_ are closed sets.
+ *   Per-world bytes.  Every segment's stream is byte for byte what a context holding that world alone returns from
+ *     nbody_delta_begin / nbody_delta_end (for tracers: nbody_tracers_delta_*) at the same step count after the same resets:
+ *     header (NBD1, element bits 32 | 64, key flag, n, step, payload words), width bytes zero padded to a multiple of 8, the
+ *     bit-plane payload with the predictor chosen per (64-row block, coordinate), ties to predictor 0, lanes past n holding z = 0.
+ *     A segment of 0 rows is its 32-byte header alone: a world of an nbody_rr handle without tracers, every world of a restricted
+ *     handle when tracers are asked for while it holds none.
+ *   Independence.  A segment's bytes depend only on its own position history, the step numbers and the resets; not on the number
+ *     of worlds, its index, the other worlds' sizes or contents, or the launch it falls in.
+ *   Step.  The handle counts the steps it has taken since it was created; the count runs on across uploads, as a context's
+ *     does.  It is written to every header of the call and to *step_out (which may be NULL).
+ *   Sequences.  A handle keeps one sequence for the bodies and one for the tracers (NBODY_DELTAS_TRACERS addresses the latter),
+ *     each with the keys of its last two streams.  The first stream after an upload of bodies is a key frame; an upload of bodies
+ *     removes the tracers and so resets both sequences; an upload of tracers resets the tracers' sequence only.  The bodies'
+ *     streams are the same bytes with or without tracers, and whether or not tracer streams are taken.  NBODY_DELTAS_KEY makes
+ *     this call's streams key frames of the sequence it addresses.
+ *   Read-only.  The call reads the current positions and writes no simulation state: stepping with these calls in between
+ *     gives the bits of stepping alone.
+ *   Commit.  The sequence advances only when the streams have been copied out; a refused call changes nothing.  With cap smaller
+ *     than the streams (out may then be NULL with cap == 0: a question for the size) the call writes *bytes_out = the bytes
+ *     needed, returns NBODY_ERR_INVALID with a message that contains "smaller than the stream", and the same call with a larger
+ *     buffer returns the bytes the first would have returned.
+ *   Output.  The streams one after another in world order in out[0, *bytes_out); every stream's size is a multiple of 8, so
+ *     every stream starts 8-aligned.  offsets_out (may be NULL): [n_worlds + 1], the byte offset of every world's stream and then
+ *     the total.  Synchronous, on the handle's stream; a fixed number of launches, whatever the number of worlds.  The device
+ *     scratch belongs to the handle, is made by the first call after an upload and freed with the rows it describes.
+ *   Refusals.  NBODY_ERR_INVALID before anything is allocated or launched, the message beginning with the handle's word
+ *     ("ensemble", "ragged", "restricted", "ragged restricted") and naming "deltas": nothing uploaded; out NULL with cap != 0;
+ *     bytes_out NULL; unknown flag bits; NBODY_DELTAS_TRACERS on one of the four handles that have no tracer calls; more than 2^24
+ *     blocks of 64 rows in the addressed segments, sum_k ceil(n_k / 64) > 2^24 (the payload is addressed in 32-bit words).  A
+ *     NULL handle gives NBODY_ERR_INVALID without a message.
+ *   nbody_deltas_bound.  Pure host code: the sum of nbody_delta_bound(rows[k], is_f64), the largest the streams of these
+ *     segments can be; 0 for a NULL or negative argument and for more than 2^24 blocks.
+ *   Not offered: snapshots of an ensemble (the calls are synchronous and *_download* hands the rows out whole; an ensemble has no
+ *     copy stream to run under the next step); a device-pointer variant; a per-world reset. */
+#define NBODY_DELTAS_TRACERS 1u /* the tracers' sequence, not the bodies' */
+#define NBODY_DELTAS_KEY 2u     /* make this a key frame */
+int nbody_deltas_ensemble(nbody_ensemble* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* offsets_out,
+                          uint64_t* step_out);
+int nbody_deltas_ensemble64(nbody_ensemble64* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* offsets_out,
+                            uint64_t* step_out);
+int nbody_deltas_ragged(nbody_ragged* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* offsets_out,
+                        uint64_t* step_out);
+int nbody_deltas_ragged64(nbody_ragged64* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* offsets_out,
+                          uint64_t* step_out);
+int nbody_deltas_restricted(nbody_restricted* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* offsets_out,
+                            uint64_t* step_out);
+int nbody_deltas_restricted64(nbody_restricted64* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out,
+                              uint64_t* offsets_out, uint64_t* step_out);
+int nbody_deltas_rr(nbody_rr* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* offsets_out,
+                    uint64_t* step_out);
+int nbody_deltas_rr64(nbody_rr64* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* offsets_out,
+                      uint64_t* step_out);
+size_t nbody_deltas_bound(int64_t n_segments, const int64_t* rows /*[n_segments], each >= 0*/, int is_f64);
 
 #endif /* NBODY_ENSEMBLE_H */

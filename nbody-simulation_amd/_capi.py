@@ -18,6 +18,7 @@ LAB_LIB_PATH = os.path.join(_HERE, "lib", "libnbody_hip_lab.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "nbody_hip.h")
 
 ABI_VERSION = 3   # NBODY_ABI_VERSION of include/nbody_hip.h (tests/test_capi_host.py checks the two agree)
+DELTAS_TRACERS, DELTAS_KEY = 1, 2   # NBODY_DELTAS_* of include/nbody_ensemble.h: the flags of nbody_deltas_<handle>
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_DEGENERATE, ERR_NOMEM = 0, -1, -2, -3, -4, -5
 ARITH_AUTO, ARITH_FAST, ARITH_EXACT = 0, 1, 2
 ORDER_AS_WRITTEN, ORDER_CONSISTENT = 0, 1
@@ -208,6 +209,9 @@ _SIGS = {
     "nbody_frames_restricted64": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_int, _vp]),
     "nbody_frames_rr": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_int, _vp]),
     "nbody_frames_rr64": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_int, _vp]),
+    **{"nbody_deltas_" + h: (C.c_int, [_vp, C.c_uint32, _vp, _sz, C.POINTER(_sz), _vp, C.POINTER(C.c_uint64)])
+       for h in ("ensemble", "ensemble64", "ragged", "ragged64", "restricted", "restricted64", "rr", "rr64")},
+    "nbody_deltas_bound": (_sz, [_i64, _vp, C.c_int]),
     "nbody_accel_tree_f32": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_accel_tree_f64": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_tree_info": (C.c_int, [_vp, C.POINTER(TreeView)]),
@@ -999,6 +1003,32 @@ class _EnsembleHandleBase:
         self._check(getattr(self.lib, name)(self.h, *args, _ptr(out)))
         return out
 
+    def _delta_rows(self, tracers):
+        """The rows of every segment a deltas() call addresses, int64[worlds]."""
+        b, n = self.shape
+        return np.full(b, getattr(self, "n_tracers", 0) if tracers else n, np.int64)
+
+    def deltas(self, tracers=False, key=False, cap=None):
+        """nbody_deltas_<handle>: one NBD1 stream per world of the current positions (tracers=True: of the tracers' sequence;
+        key=True: key frames) -> (buffer uint8[bytes], offsets uint64[worlds + 1], step): world k's stream is
+        buffer[offsets[k]:offsets[k + 1]].  The buffer is sized by nbody_deltas_bound unless `cap` says otherwise; a call the
+        library refuses for a small `cap` raises with the bytes it needs in the error's `needed`."""
+        rows = self._delta_rows(tracers)
+        if cap is None:
+            cap = int(self.lib.nbody_deltas_bound(int(rows.shape[0]), _ptr(rows), 1 if self._dtype == np.float64 else 0))
+        cap = int(cap)
+        buf = np.zeros(max(cap, 1), np.uint8)
+        offsets = np.zeros(rows.shape[0] + 1, np.uint64)
+        size, step = _sz(0), C.c_uint64(0)
+        name = "nbody_deltas_" + self._prefix[len("nbody_"):]
+        flags = (DELTAS_TRACERS if tracers else 0) | (DELTAS_KEY if key else 0)
+        rc = getattr(self.lib, name)(self.h, flags, _ptr(buf) if cap else None, cap, C.byref(size), _ptr(offsets), C.byref(step))
+        if rc != OK:
+            err = self._err(rc)
+            err.needed = size.value
+            raise err
+        return buf[:size.value], offsets, step.value
+
 
 class EnsembleHandle(_EnsembleHandleBase):
     """nbody_ensemble_*: float32 worlds."""
@@ -1041,6 +1071,11 @@ class RaggedHandle(_EnsembleHandleBase):
         acc = np.zeros((self.shape[1], 2), self._dtype)
         self._check(self._call("_accel" + self._suffix, _ptr(acc)))
         return acc
+
+    def _delta_rows(self, tracers):
+        sizes = self.sizes   # (a handle with tracers: the sizes and the counts)
+        bodies, counts = sizes if isinstance(sizes, tuple) else (sizes, np.zeros_like(sizes))
+        return np.ascontiguousarray(counts if tracers else bodies, dtype=np.int64)
 
 
 class Ragged64Handle(RaggedHandle):

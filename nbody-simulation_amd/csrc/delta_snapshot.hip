@@ -7,6 +7,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "delta_codec.h"
+#include "delta_device.h"
 
 namespace nbody {
 namespace {
@@ -39,21 +40,7 @@ template <class T> __global__ __launch_bounds__(256) void delta_keys_in_order(in
   out[npad + row] = delta_key(p[1]);
 }
 
-__device__ __forceinline__ uint32_t wave_or(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v |= (uint32_t)__shfl_xor((int)v, d, 64);
-  return v;
-}
-__device__ __forceinline__ uint64_t wave_or(uint64_t v) {
-  return ((uint64_t)wave_or((uint32_t)(v >> 32)) << 32) | wave_or((uint32_t)v);
-}
-__device__ __forceinline__ int bits_of(uint32_t v) { return 32 - __clz((int)v); }
-__device__ __forceinline__ int bits_of(uint64_t v) { return 64 - __clzll((long long)v); }
-
-template <class K> __device__ __forceinline__ void residuals(K cur, K prev, K prev2, K& z0, K& z1) {
-  z0 = delta_zigzag((K)(cur - prev));
-  z1 = delta_zigzag((K)(cur - (K)(prev + (K)(prev - prev2))));
-}
+// (wave_or, bits_of and residuals: delta_device.h, shared with the ensembles' encoder)
 
 // One wave per block of 64 ids, both coordinates: width byte + payload words of each (block, coordinate).
 template <class K>

@@ -26,3 +26,8 @@ NB_API int nbody_ensemble_accel_f32(nbody_ensemble* e, float* acc_xy) { return e
 NB_API int nbody_frames_ensemble(nbody_ensemble* e, uint32_t height, uint32_t render_px, uint8_t* rgba_out) {
   return ens_frames<EnsF32>(e, height, render_px, rgba_out);
 }
+// (delta streams of every world, ensemble_deltas.h: likewise a prefix of its own)
+NB_API int nbody_deltas_ensemble(nbody_ensemble* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* offsets_out,
+                                 uint64_t* step_out) {
+  return ens_deltas<EnsF32>(e, flags, out, cap, bytes_out, offsets_out, step_out);
+}

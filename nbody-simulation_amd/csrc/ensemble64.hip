@@ -26,3 +26,8 @@ NB_API int nbody_ensemble64_accel(nbody_ensemble64* e, double* acc_xy) { return 
 NB_API int nbody_frames_ensemble64(nbody_ensemble64* e, uint32_t height, uint32_t render_px, uint8_t* rgba_out) {
   return ens_frames<EnsF64>(e, height, render_px, rgba_out);
 }
+// (delta streams of every world, ensemble_deltas.h: likewise a prefix of its own)
+NB_API int nbody_deltas_ensemble64(nbody_ensemble64* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* offsets_out,
+                                   uint64_t* step_out) {
+  return ens_deltas<EnsF64>(e, flags, out, cap, bytes_out, offsets_out, step_out);
+}

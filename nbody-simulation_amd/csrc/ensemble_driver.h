@@ -17,18 +17,51 @@
 // under its own kWho, with the tracers' launch added to a step through ens_update_with.
 // Frames (nbody_frames_*, ensemble_frames.h) are ens_frames below for every handle: the ragged, restricted and ragged restricted
 // drivers hand it their row ranges in a FrameRows and nothing else.
+// Delta streams (nbody_deltas_*, ensemble_deltas.h) are ens_deltas below for every handle in the same way: the other drivers hand
+// it their sizes, counts and tracer positions in a DeltaRows.  The state counts its steps (`updates`) for the streams' headers.
 #pragma once
 #include <algorithm>
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "driver.h"
+#include "ensemble_deltas.h"
 #include "ensemble_frames.h"
 #include "ensemble_kernels.h"
 
 namespace nbody {
+
+// One sequence of delta streams of a handle (ens_deltas): the bodies' or the tracers'.  Everything is device scratch of the
+// handle, made by the first call after an upload of the rows it describes and freed where those rows are freed, which is also
+// how an upload resets the sequence (the next streams are key frames).
+struct DeltaSeq {
+  bool planned = false;        // blocks and base_total below are those of the current rows
+  bool ready = false;          // the scratch below is allocated for them
+  int64_t blocks = 0;          // 64-row blocks of all segments together
+  uint64_t base_total = 0;     // sum over the segments of (32 + width bytes)
+  void* keys[3] = {nullptr, nullptr, nullptr};
+  int cur = 0;                 // keys[cur] is written next; prev = keys[(cur + 2) % 3], prev2 = keys[(cur + 1) % 3]
+  uint32_t have = 0;           // how many of prev, prev2 hold keys of this sequence (0: the next stream is a key frame)
+  uint8_t* widths = nullptr;
+  uint32_t* words = nullptr;
+  uint32_t* offsets = nullptr;
+  void* scan = nullptr;
+  size_t scan_bytes = 0;
+  DeltaSeg* table = nullptr;   // ragged handles
+  uint32_t* seg_of_block = nullptr;
+  uint64_t* stream_off = nullptr;
+  uint8_t* out = nullptr;      // grown to the streams of a call
+  size_t out_bytes = 0;
+  void release() {
+    for (auto& k : keys) free_dev(k);
+    free_dev(widths); free_dev(words); free_dev(offsets); free_dev(scan); free_dev(table); free_dev(seg_of_block);
+    free_dev(stream_off); free_dev(out);
+    *this = DeltaSeq();
+  }
+};
 
 template <class P> struct EnsembleState {
   using Precision = P;
@@ -51,6 +84,11 @@ template <class P> struct EnsembleState {
   FrameWorld* frame_table = nullptr;
   size_t frame_rgba_bytes = 0, frame_work_bytes = 0;
   bool frame_table_valid = false;
+  // delta streams (ens_deltas): the steps taken since the handle was created (it runs on across uploads, as a context's count
+  // does), and the two sequences.  The bodies' goes with the arrays above; the tracers' with the tracers of the handles that
+  // have them (and so with the bodies too: an upload of bodies removes the tracers).
+  uint64_t updates = 0;
+  DeltaSeq dbodies, dtracers;
 };
 
 template <class P> thread_local std::string g_ens_create_error;  // one per precision: what a failed create left for its thread
@@ -73,6 +111,8 @@ template <class P> void ens_free(EnsembleState<P>* e) {
   free_dev(e->frame_rgba); free_dev(e->frame_work); free_dev(e->frame_table);
   e->frame_rgba_bytes = e->frame_work_bytes = 0;
   e->frame_table_valid = false;
+  e->dbodies.release();
+  e->dtracers.release();
   e->n_worlds = e->n_bodies = e->rows = 0;
   e->cur = 0;
 }
@@ -226,6 +266,7 @@ int ens_update_with(EnsembleState<P>* e, typename P::Real delta, int n_steps, nb
     a.delta = delta;
     ENS_HIPCHK(e, launch(a));
     e->cur = 1 - e->cur;  // (the launches are in stream order: the next one reads what this one writes)
+    ++e->updates;
   }
   ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
   // force and integration are one fused kernel: the whole call is booked under sum_gravity, as the direct step books it
@@ -334,6 +375,138 @@ int ens_frames(EnsembleState<P>* e, uint32_t height, uint32_t render_px, uint8_t
   ENS_HIPCHK(e, launch_ensemble_frames<typename P::Real>(e->stream, e->n_worlds, max_rows, a, lds ? nullptr : e->frame_work, e->frame_rgba));
   ENS_HIPCHK(e, hipMemcpyAsync(rgba_out, e->frame_rgba, (size_t)(e->n_worlds * npix) * 4, hipMemcpyDeviceToHost, e->stream));
   ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
+  return NBODY_OK;
+}
+
+// ---- delta streams: every world's NBD1 stream (ensemble_deltas.h) of the current positions, into host memory
+// What a handle tells ens_deltas about its rows, beyond the bodies of worlds of one size.
+template <class P> struct DeltaRows {
+  const int64_t* sizes = nullptr;         // worlds of different sizes: the bodies per world; NULL: e->n_bodies in every world
+  const int64_t* counts = nullptr;        // with sizes: the tracers per world, or NULL: none
+  int64_t n_tracers = 0;                  // without sizes: the tracers per world
+  const typename P::Vec2* tpos = nullptr; // the tracers' positions (NULL where the handle holds none)
+  bool tracer_calls = false;              // the handle has tracer calls at all: NBODY_DELTAS_TRACERS is its to ask
+};
+
+// The scratch of a sequence for its planned rows; on failure the sequence is released whole.
+template <class P> int ens_deltas_scratch(EnsembleState<P>* e, DeltaSeq& q, bool tracers, const DeltaRows<P>& rows) {
+  const size_t blocks = (size_t)q.blocks, kb = blocks * 128 * sizeof(typename P::Real);
+  q.scan_bytes = deltas_scan_temp_bytes(q.blocks);
+  hipError_t h = hipSuccess;
+  for (auto& k : q.keys)
+    if (h == hipSuccess) h = hipMalloc(&k, kb ? kb : 8);
+  if (h == hipSuccess) h = hipMalloc((void**)&q.widths, 2 * blocks + 8);
+  if (h == hipSuccess) h = hipMalloc((void**)&q.words, (2 * blocks + 1) * 4);
+  if (h == hipSuccess) h = hipMalloc((void**)&q.offsets, (2 * blocks + 1) * 4);
+  if (h == hipSuccess) h = hipMalloc(&q.scan, q.scan_bytes ? q.scan_bytes : 8);
+  if (h == hipSuccess) h = hipMalloc((void**)&q.stream_off, ((size_t)e->n_worlds + 1) * 8);
+  if (h == hipSuccess) h = hipMemsetAsync(q.words, 0, (2 * blocks + 1) * 4, e->stream);    // (the scan reads the last entry too)
+  if (h == hipSuccess) h = hipMemsetAsync(q.offsets, 0, (2 * blocks + 1) * 4, e->stream);  // (without a block it is never written)
+  if (h == hipSuccess && rows.sizes) {  // the table of a ragged handle: built here, once per upload of the rows it describes
+    std::vector<DeltaSeg> table((size_t)e->n_worlds);
+    std::vector<uint32_t> seg_of_block(blocks);
+    uint64_t row0 = 0, blk0 = 0, base = 0;
+    for (int64_t k = 0; k < e->n_worlds; ++k) {
+      const int64_t n = tracers ? (rows.counts ? rows.counts[k] : 0) : rows.sizes[k];
+      table[(size_t)k] = DeltaSeg{(uint32_t)row0, (uint32_t)n, (uint32_t)blk0, 0u, base};  // (rows <= 2^26, blocks <= 2^24)
+      for (size_t b = 0; b < delta_blocks(n); ++b) seg_of_block[blk0 + b] = (uint32_t)k;
+      row0 += (uint64_t)n;
+      blk0 += delta_blocks(n);
+      base += kDeltaHeader + delta_width_bytes(n);
+    }
+    h = hipMalloc((void**)&q.table, table.size() * sizeof(DeltaSeg));
+    if (h == hipSuccess) h = hipMalloc((void**)&q.seg_of_block, blocks ? blocks * 4 : 8);
+    if (h == hipSuccess) h = hipMemcpyAsync(q.table, table.data(), table.size() * sizeof(DeltaSeg), hipMemcpyHostToDevice, e->stream);
+    if (h == hipSuccess && blocks) h = hipMemcpyAsync(q.seg_of_block, seg_of_block.data(), blocks * 4, hipMemcpyHostToDevice, e->stream);
+    if (h == hipSuccess) h = hipStreamSynchronize(e->stream);  // (the vectors go out of scope)
+  }
+  if (h != hipSuccess) {
+    (void)hipStreamSynchronize(e->stream);
+    q.release();
+    return ens_fail_hip(e, h, "the scratch of the delta streams");
+  }
+  q.ready = true;
+  return NBODY_OK;
+}
+
+// One stream per world, one after another in world order, into out[0, cap); offsets_out (may be NULL): [n_worlds + 1].
+// Synchronous, on the handle's stream; reads pos[cur] or the tracers, writes no simulation state.  The sequence advances only
+// when the streams have been copied out: a refused call changes nothing.
+template <class P>
+int ens_deltas(EnsembleState<P>* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* offsets_out, uint64_t* step_out,
+               const DeltaRows<P>& rows = DeltaRows<P>()) {
+  using K = typename std::conditional<sizeof(typename P::Real) == 8, uint64_t, uint32_t>::type;
+  if (!e) return NBODY_ERR_INVALID;
+  const std::string who = std::string(P::kWho) + " deltas: ";
+  if (!e->n_worlds) return ens_fail(e, NBODY_ERR_INVALID, who + "nothing uploaded");
+  if (!bytes_out) return ens_fail(e, NBODY_ERR_INVALID, who + "bytes_out is NULL");
+  if (!out && cap) return ens_fail(e, NBODY_ERR_INVALID, who + "out is NULL with cap != 0");
+  if (flags & ~(NBODY_DELTAS_TRACERS | NBODY_DELTAS_KEY)) return ens_fail(e, NBODY_ERR_INVALID, who + "unknown flag bits");
+  const bool tracers = (flags & NBODY_DELTAS_TRACERS) != 0;
+  if (tracers && !rows.tracer_calls) return ens_fail(e, NBODY_ERR_INVALID, who + "NBODY_DELTAS_TRACERS on a handle without tracers");
+  DeltaSeq& q = tracers ? e->dtracers : e->dbodies;
+  if (!q.planned) {  // (once per upload of these rows: the only loop over worlds, and only for a ragged handle)
+    int64_t blocks = 0;
+    uint64_t base = 0;
+    if (rows.sizes) {
+      for (int64_t k = 0; k < e->n_worlds; ++k) {
+        const int64_t n = tracers ? (rows.counts ? rows.counts[k] : 0) : rows.sizes[k];
+        blocks += (int64_t)delta_blocks(n);
+        base += kDeltaHeader + delta_width_bytes(n);
+      }
+    } else {
+      const int64_t n = tracers ? rows.n_tracers : e->n_bodies;
+      blocks = e->n_worlds * (int64_t)delta_blocks(n);  // (rows <= 2^26)
+      base = (uint64_t)e->n_worlds * (kDeltaHeader + delta_width_bytes(n));
+    }
+    q.blocks = blocks;
+    q.base_total = base;
+    q.planned = true;
+  }
+  if (q.blocks > kDeltasMaxBlocks)
+    return ens_fail(e, NBODY_ERR_INVALID, who + "more than 2^24 blocks of 64 rows in the worlds together (nbody_deltas_bound)");
+
+  ENS_HIPCHK(e, hipSetDevice(e->device));
+  if (!q.ready)
+    if (int rc = ens_deltas_scratch(e, q, tracers, rows)) return rc;
+  DeltasArgs a;
+  a.pos = tracers ? (const void*)rows.tpos : (const void*)e->pos[e->cur];
+  a.table = q.table;
+  a.seg_of_block = q.seg_of_block;
+  a.n_segs = (uint32_t)e->n_worlds;
+  a.n = rows.sizes ? 0u : (uint32_t)(tracers ? rows.n_tracers : e->n_bodies);
+  a.blocks = (uint32_t)q.blocks;
+  a.have = (flags & NBODY_DELTAS_KEY) ? 0u : q.have;
+  a.step = e->updates;
+  a.base_total = q.base_total;
+  a.cur = q.keys[q.cur];
+  a.prev = q.keys[(q.cur + 2) % 3];
+  a.prev2 = q.keys[(q.cur + 1) % 3];
+  a.widths = q.widths;
+  a.words = q.words;
+  a.offsets = q.offsets;
+  a.stream_off = q.stream_off;
+  // the size of the streams is known on the device only: measure, fetch it, then write the streams at their final places
+  uint32_t words = 0;
+  if (q.blocks) {
+    ENS_HIPCHK(e, launch_deltas_measure<K>(e->stream, a, q.scan, q.scan_bytes));
+    ENS_HIPCHK(e, hipMemcpyAsync(&words, q.offsets + 2 * q.blocks, 4, hipMemcpyDeviceToHost, e->stream));
+    ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
+    if ((uint64_t)words > 2 * (uint64_t)q.blocks * sizeof(K) * 8) return ens_fail(e, NBODY_ERR_HIP, who + "the encoder reported an impossible size");
+  }
+  const size_t total = (size_t)q.base_total + (size_t)words * 8;
+  *bytes_out = total;
+  if (!out || cap < total) return ens_fail(e, NBODY_ERR_INVALID, who + "the output buffer is smaller than the stream");
+  if (int rc = ens_frame_buffer(e, q.out, q.out_bytes, total)) return rc;
+  a.out = q.out;
+  ENS_HIPCHK(e, launch_deltas_write<K>(e->stream, a));
+  ENS_HIPCHK(e, hipMemcpyAsync(out, q.out, total, hipMemcpyDeviceToHost, e->stream));
+  if (offsets_out)
+    ENS_HIPCHK(e, hipMemcpyAsync(offsets_out, q.stream_off, ((size_t)e->n_worlds + 1) * 8, hipMemcpyDeviceToHost, e->stream));
+  ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (step_out) *step_out = e->updates;
+  q.cur = (q.cur + 1) % 3;  // the oldest keys are overwritten next time
+  q.have = a.have < 2 ? a.have + 1 : 2;
   return NBODY_OK;
 }
 

@@ -36,6 +36,11 @@ NB_API int nbody_ragged64_accel(nbody_ragged64* e, double* acc_xy) { return ragg
 NB_API int nbody_frames_ragged64(nbody_ragged64* e, uint32_t height, uint32_t render_px, uint8_t* rgba_out) {
   return ragged_frames<RagF64>(e, height, render_px, rgba_out);
 }
+// (delta streams of every world, ensemble_deltas.h: likewise a prefix of its own)
+NB_API int nbody_deltas_ragged64(nbody_ragged64* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* offsets_out,
+                                 uint64_t* step_out) {
+  return ragged_deltas<RagF64>(e, flags, out, cap, bytes_out, offsets_out, step_out);
+}
 
 NB_API int nbody_ragged64_plan(int64_t n_worlds, const int64_t* n_bodies, int32_t* launch_of_world, int64_t* first_block_of_world,
                                int32_t* n_launches, int32_t* lds_bytes_of_launch, int64_t* blocks_of_launch) {

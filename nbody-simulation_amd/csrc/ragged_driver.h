@@ -81,6 +81,15 @@ template <class P> int ragged_frames(RaggedState<P>* e, uint32_t height, uint32_
   return ens_frames<P>(e, height, render_px, rgba_out, rows);
 }
 
+// Delta streams: the ensemble's, over segments of these sizes.
+template <class P>
+int ragged_deltas(RaggedState<P>* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* offsets_out, uint64_t* step_out) {
+  if (!e) return NBODY_ERR_INVALID;
+  DeltaRows<P> rows;
+  rows.sizes = e->sizes.data();
+  return ens_deltas<P>(e, flags, out, cap, bytes_out, offsets_out, step_out, rows);
+}
+
 template <class P> int ragged_sizes(const RaggedState<P>* e, int64_t* n_bodies_out) {
   if (!e || !n_bodies_out) return NBODY_ERR_INVALID;
   for (int64_t k = 0; k < e->n_worlds; ++k) n_bodies_out[k] = e->sizes[(size_t)k];

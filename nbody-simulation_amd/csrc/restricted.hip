@@ -42,3 +42,8 @@ NB_API int nbody_restricted_tracers_accel_f32(nbody_restricted* e, float* acc_xy
 NB_API int nbody_frames_restricted(nbody_restricted* e, uint32_t height, uint32_t render_px, int with_tracers, uint8_t* rgba_out) {
   return rst_frames<RstF32>(e, height, render_px, with_tracers, rgba_out);
 }
+// (delta streams of every world, ensemble_deltas.h: likewise a prefix of its own)
+NB_API int nbody_deltas_restricted(nbody_restricted* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* offsets_out,
+                                   uint64_t* step_out) {
+  return rst_deltas<RstF32>(e, flags, out, cap, bytes_out, offsets_out, step_out);
+}

@@ -42,3 +42,8 @@ NB_API int nbody_restricted64_tracers_accel(nbody_restricted64* e, double* acc_x
 NB_API int nbody_frames_restricted64(nbody_restricted64* e, uint32_t height, uint32_t render_px, int with_tracers, uint8_t* rgba_out) {
   return rst_frames<Rst64>(e, height, render_px, with_tracers, rgba_out);
 }
+// (delta streams of every world, ensemble_deltas.h: likewise a prefix of its own)
+NB_API int nbody_deltas_restricted64(nbody_restricted64* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out,
+                                     uint64_t* offsets_out, uint64_t* step_out) {
+  return rst_deltas<Rst64>(e, flags, out, cap, bytes_out, offsets_out, step_out);
+}

@@ -23,6 +23,7 @@ template <class P> struct RestrictedState : EnsembleState<P> {
   void drop_tracers() {
     free_dev(tpos); free_dev(tvel); free_dev(tacc);
     n_tracers = 0;
+    this->dtracers.release();  // (the tracers' delta streams start over with the next tracers)
   }
 };
 
@@ -127,6 +128,17 @@ template <class P> int rst_frames(RestrictedState<P>* e, uint32_t height, uint32
     rows.tvel = e->tvel;
   }
   return ens_frames<P>(e, height, render_px, rgba_out, rows);
+}
+
+// Delta streams: the ensemble's, the bodies' sequence or the tracers' (without tracers: every world's stream is a header of 0 rows).
+template <class P>
+int rst_deltas(RestrictedState<P>* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* offsets_out, uint64_t* step_out) {
+  if (!e) return NBODY_ERR_INVALID;
+  DeltaRows<P> rows;
+  rows.n_tracers = e->n_tracers;
+  rows.tpos = e->tpos;
+  rows.tracer_calls = true;
+  return ens_deltas<P>(e, flags, out, cap, bytes_out, offsets_out, step_out, rows);
 }
 
 template <class P> int64_t rst_num_tracers(const RestrictedState<P>* e) { return e ? e->n_tracers : 0; }

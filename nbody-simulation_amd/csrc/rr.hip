@@ -56,6 +56,11 @@ NB_API int nbody_rr_tracers_accel_f32(nbody_rr* e, float* acc_xy) { return rr_tr
 NB_API int nbody_frames_rr(nbody_rr* e, uint32_t height, uint32_t render_px, int with_tracers, uint8_t* rgba_out) {
   return rr_frames<RrF32>(e, height, render_px, with_tracers, rgba_out);
 }
+// (delta streams of every world, ensemble_deltas.h: likewise a prefix of its own)
+NB_API int nbody_deltas_rr(nbody_rr* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* offsets_out,
+                           uint64_t* step_out) {
+  return rr_deltas<RrF32>(e, flags, out, cap, bytes_out, offsets_out, step_out);
+}
 
 NB_API int nbody_rr_plan(int64_t n_worlds, const int64_t* n_bodies, const int64_t* n_tracers, int32_t* launch_of_world,
                          int64_t* first_block_of_world, int32_t* n_launches, int32_t* lds_bytes_of_launch, int64_t* blocks_of_launch) {

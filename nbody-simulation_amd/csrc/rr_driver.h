@@ -33,6 +33,7 @@ template <class P> struct RrState : RaggedState<P> {
     tplan = RrPlan();
     tracer_rows = 0;
     this->frame_table_valid = false;  // (the frames' table of row ranges holds the counts)
+    this->dtracers.release();         // (the tracers' delta streams start over with the next tracers)
   }
 };
 
@@ -164,6 +165,18 @@ template <class P> int rr_frames(RrState<P>* e, uint32_t height, uint32_t render
     rows.tvel = e->tvel;
   }
   return ens_frames<P>(e, height, render_px, rgba_out, rows);
+}
+
+// Delta streams: the ensemble's, over segments of these sizes or these counts (a world without tracers: a header of 0 rows).
+template <class P>
+int rr_deltas(RrState<P>* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* offsets_out, uint64_t* step_out) {
+  if (!e) return NBODY_ERR_INVALID;
+  DeltaRows<P> rows;
+  rows.sizes = e->sizes.data();
+  if (e->tracer_rows) rows.counts = e->counts.data();
+  rows.tpos = e->tpos;
+  rows.tracer_calls = true;
+  return ens_deltas<P>(e, flags, out, cap, bytes_out, offsets_out, step_out, rows);
 }
 
 // The sizes and the tracer counts of every world; either output may be NULL.  Without tracers every count is 0.

@@ -35,6 +35,11 @@ to a `RaggedEnsemble` of the same worlds; a tracer is EXACT bit-identical to the
 Every class has `frames(height, render_px)` (nbody_frames_*): the reference's draw() raster of every world's own rows from one
 call, uint8 [B, render_px, render_px, 4] — the classes with tracers take `tracers=True` to paint them after their world's
 bodies — and `contact_sheet(frames)` tiles such frames into one image on the host.
+
+Every class has `deltas()` (nbody_deltas_*) too: one lossless NBD1 delta stream per world from one call, byte for byte what a
+`World` holding that world alone hands out through delta_begin / delta_end — the classes with tracers take `tracers=True` for
+the tracers' sequence — and `DeltasDecoder(n_worlds)` is the receiving side, one `DeltaDecoder` per world.  Snapshots of an
+ensemble are not offered: `particles()` hands the rows out whole.
 """
 from __future__ import annotations
 
@@ -47,6 +52,12 @@ MAX_BODIES = 4096          # per world: its sources stage whole in LDS
 MAX_ROWS = 1 << 26         # worlds * bodies
 
 _ARITH = {"auto": _capi.ARITH_AUTO, "fast": _capi.ARITH_FAST, "exact": _capi.ARITH_EXACT}
+
+
+def _streams(handle, tracers, key):
+    """handle.deltas(...) cut into one bytes object per world."""
+    buf, off, step = handle.deltas(tracers, key)
+    return [buf[int(off[k]):int(off[k + 1])].tobytes() for k in range(off.shape[0] - 1)], step
 
 
 def _checked(position, velocity, weight, dtype=np.float32, who=None, other=None):
@@ -136,6 +147,12 @@ class _EnsembleBase:
         """-> uint8 [B, render_px, render_px, 4]: the reference's draw() of every world's current rows, each world alone on its
         own tile, byte for byte `World.frame` of that world; the state is untouched."""
         return self.h.frames(height, render_px)
+
+    def deltas(self, key=False):
+        """-> (streams, step): one NBD1 delta stream (bytes) per world of the current positions, byte for byte what a `World` of
+        that world alone hands out, and the steps taken so far.  The first call after an upload, and any call with key=True,
+        gives key frames; `DeltasDecoder` follows the sequence.  The state is untouched."""
+        return _streams(self.h, False, key)
 
     def close(self):
         if getattr(self, "h", None) is not None:
@@ -249,6 +266,12 @@ class _RestrictedBase(_EnsembleBase):
         """-> uint8 [B, render_px, render_px, 4]: draw() of every world's bodies; tracers=True: followed by its tracers as rows
         of weight 1 (without tracers: the bodies' frames).  The state is untouched."""
         return self.h.frames(height, render_px, tracers)
+
+    def deltas(self, tracers=False, key=False):
+        """-> (streams, step): one NBD1 delta stream (bytes) per world, of the bodies' positions or, with tracers=True, of the
+        tracers' (a sequence of its own; a world without tracers: a header of 0 rows), and the steps taken so far.  The first
+        call after an upload of the rows it addresses, and any call with key=True, gives key frames.  The state is untouched."""
+        return _streams(self.h, tracers, key)
 
 
 class RestrictedEnsemble(_RestrictedBase):
@@ -374,6 +397,12 @@ class _RaggedBase:
         """-> uint8 [B, render_px, render_px, 4]: the reference's draw() of every world's current rows, each world alone on its
         own tile, whatever its size; the state is untouched."""
         return self.h.frames(height, render_px)
+
+    def deltas(self, key=False):
+        """-> (streams, step): one NBD1 delta stream (bytes) per world of the current positions, byte for byte what a `World` of
+        that world alone hands out, and the steps taken so far.  The first call after an upload, and any call with key=True,
+        gives key frames; `DeltasDecoder` follows the sequence.  The state is untouched."""
+        return _streams(self.h, False, key)
 
     def close(self):
         if getattr(self, "h", None) is not None:
@@ -522,6 +551,12 @@ class RaggedRestrictedEnsemble(_RaggedBase):
         rows of weight 1 (a world without tracers: its bodies).  The state is untouched."""
         return self.h.frames(height, render_px, tracers)
 
+    def deltas(self, tracers=False, key=False):
+        """-> (streams, step): one NBD1 delta stream (bytes) per world, of the bodies' positions or, with tracers=True, of the
+        tracers' (a sequence of its own; a world without tracers: a header of 0 rows), and the steps taken so far.  The first
+        call after an upload of the rows it addresses, and any call with key=True, gives key frames.  The state is untouched."""
+        return _streams(self.h, tracers, key)
+
 
 class RaggedRestrictedEnsemble64(RaggedRestrictedEnsemble):
     """The ragged restricted ensemble in double precision (nbody_rr64_*): the same constructor and methods, float64 arrays
@@ -536,6 +571,66 @@ class RaggedRestrictedEnsemble64(RaggedRestrictedEnsemble):
     @staticmethod
     def _new_handle(device):
         return _capi.RR64Handle(device)
+
+
+class DeltasDecoder:
+    """The receiving side of `deltas()` (host only): one `DeltaDecoder` per world.  `apply(streams)` takes the list one call
+    returned; a list of the wrong length is refused, and where a decoder's header checks refuse one stream none of the list is
+    applied."""
+
+    def __init__(self, n_worlds):
+        n_worlds = int(n_worlds)
+        if n_worlds < 1:
+            raise ValueError(f"DeltasDecoder: at least one world, got {n_worlds}")
+        self._decoders = [_capi.DeltaDecoder() for _ in range(n_worlds)]
+        self.step = 0
+
+    def __len__(self):
+        return len(self._decoders)
+
+    def apply(self, streams):
+        if not isinstance(streams, (list, tuple)) or len(streams) != len(self._decoders):
+            raise ValueError(f"DeltasDecoder: {len(self._decoders)} streams expected, one per world")
+        for k, (d, s) in enumerate(zip(self._decoders, streams)):
+            why = _refused(d, bytes(s))
+            if why:
+                raise _capi.NBodyError(_capi.ERR_INVALID, f"DeltasDecoder: world {k}: {why} (nothing applied)")
+        for d, s in zip(self._decoders, streams):
+            d.apply(s)
+        if streams:
+            self.step = self._decoders[0].step
+
+    def positions(self):
+        """-> a list of arrays [n_k, 2], one per world: the positions of the last applied streams."""
+        return [d.positions() for d in self._decoders]
+
+    def close(self):
+        for d in self._decoders:
+            d.close()
+
+
+def _refused(decoder, stream):
+    """What the header checks of nbody_delta_decoder_apply (csrc/delta_decoder.hpp) would say of `stream` in the state `decoder`
+    is in, or None: restated here so that a list of streams can be checked whole before any of it is applied."""
+    if len(stream) < 32 or stream[:4] != b"NBD1":
+        return "not an NBD1 stream"
+    bits, key = stream[4], stream[5]
+    if bits not in (32, 64) or key > 1 or stream[6:8] != b"\0\0":
+        return "bad header"
+    n, total = int.from_bytes(stream[8:16], "little"), int.from_bytes(stream[24:32], "little")
+    if n > 0x7fffffff:
+        return "body count out of range"
+    nblk = (n + 63) // 64
+    wb = (2 * nblk + 7) // 8 * 8
+    if total > 2 * nblk * bits or len(stream) != 32 + wb + 8 * total:
+        return "the size does not match the header"
+    if not key and (decoder.n != n or (decoder.dtype == np.float64) != (bits == 64)):
+        return "a delta stream out of sequence"
+    widths = np.frombuffer(stream, np.uint8, wb, 32)
+    w = widths[:2 * nblk] & 127
+    if (w > bits).any() or widths[2 * nblk:].any() or int(w.sum(dtype=np.int64)) != total:
+        return "the width bytes do not match the payload"
+    return None
 
 
 def contact_sheet(frames, cols=None):
