@@ -301,13 +301,9 @@ void nbody::ctx_destroy_single(nbody_ctx* c) {
   free_dev(c->frame_work);
   free_dev(c->frame_rgba);
   free_dev(c->spec_dev);
-  free_dev(c->stamp_dev);
   if (c->spec_host) (void)hipHostFree(c->spec_host);
   if (c->spec_event) (void)hipEventDestroy(c->spec_event);
-  for (auto& p : c->ph_pending)
-    for (int k = p.borrowed ? 1 : 0; k < 4; ++k)
-      if (p.e[k]) (void)hipEventDestroy(p.e[k]);
-  for (auto e : c->ph_free) (void)hipEventDestroy(e);
+  c->phases.release();
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
   free_snapshot(c);
   free_delta(c);
@@ -401,7 +397,7 @@ struct EstimateSelftestScratch {
   int device = -1;
 };
 thread_local EstimateSelftestScratch g_est_scratch;
-constexpr int kEstFlagWords = 128;    // the block a step packs: flags + level counters (tree_driver.hip, kSpecWords)
+constexpr int kEstFlagWords = 128;    // the block a step packs: flags + level counters (ctx.h, StepAheadRecord::build)
 constexpr int kEstBigcountAt = 32;    // where this self-test puts the level counters inside it (64 of them)
 }  // namespace
 NB_API int nbody_selftest_walk_estimate(int device, const uint32_t* hist, int64_t hist_n, const uint32_t* ids, int64_t n, int shift, int route,

@@ -185,6 +185,36 @@ struct PhaseEvents {
   hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
   bool borrowed = false;  // e[0] is the previous step's e[3]
 };
+// What the context keeps of its steps' phase timing (phase_clock.h: StepClock, phase_drain).  The steps enqueued ahead
+// (tree_driver.hip, bvh_step_ahead) are timed by their own kernels instead of three event records per step (each ~6 us of idle
+// stream): the kernels write the 100 MHz wall clock at the phase boundaries, slot = {build begins, walk begins, integration
+// begins, step ends}; read back when the phases are drained.
+struct PhaseTiming {
+  unsigned long long* stamp_dev = nullptr;  // [kStampSlots][4]
+  std::vector<int> stamp_pending;           // slots of finished steps not yet read
+  int stamp_next = 0;
+  int stamp_open = -1;                      // slot whose end is still to be written (by the next step's first kernel, or a stamp kernel)
+  std::vector<PhaseEvents> pending;         // recorded phase events
+  std::vector<hipEvent_t> free_events;      // reusable events
+  nbody_counting* counter = nullptr;        // the caller's counter of the call in progress
+  void release() {                          // (the context is being destroyed)
+    if (stamp_dev) (void)hipFree(stamp_dev);
+    for (auto& p : pending)
+      for (int k = p.borrowed ? 1 : 0; k < 4; ++k)
+        if (p.e[k]) (void)hipEventDestroy(p.e[k]);
+    for (auto e : free_events) (void)hipEventDestroy(e);
+  }
+};
+// The pinned record a BVH step enqueued ahead of the host packs for it (tree_driver.hip, bvh_step_ahead).  The device side sees
+// plain words: TileTail::pack writes verdict | build | info_before in one run, the integration's Gate carries info_after.
+struct StepAheadRecord {
+  int verdict[2];       // node count or 0, ok
+  int build[128];       // the build's flags, and its level counters where the build's layout has them (512 B)
+  int info_before[8];   // the walk's info once its preparation is done
+  int info_after[8];    // ... and after the walk (its exact term count), read one step late
+};
+static_assert(sizeof(StepAheadRecord) == (2 + 128 + 8 + 8) * sizeof(int), "the record's parts lie back to back");
+constexpr int kAheadBuildWords = sizeof(StepAheadRecord::build) / sizeof(int);
 }  // namespace nbody
 
 struct nbody_ctx {
@@ -226,20 +256,11 @@ struct nbody_ctx {
   uint32_t frame_px = 0;
   unsigned long long last_stats[3] = {0, 0, 0};
   bool want_stats = false;
-  // Phase clock of the steps enqueued ahead (tree_driver.hip, bvh_step_ahead): instead of three event records per step (each ~6 us of idle
-  // stream) the step's own kernels write the 100 MHz wall clock at the phase boundaries: slot = {build begins, walk begins,
-  // integration begins, step ends}; read back when the phases are drained.
-  unsigned long long* stamp_dev = nullptr;               // [kStampSlots][4]
-  std::vector<int> stamp_pending;                        // slots of finished steps not yet read
-  int stamp_next = 0;
-  int stamp_open = -1;                                   // slot whose end is still to be written (by the next step's first kernel, or a stamp kernel)
-  std::vector<nbody::PhaseEvents> ph_pending;           // recorded phase events
-  std::vector<hipEvent_t> ph_free;                       // reusable events
-  nbody_counting* ph_counter = nullptr;                // the caller's counter of the call in progress
+  nbody::PhaseTiming phases;  // the tree steps' phase clock
   // a BVH step enqueued whole, ahead of the host's knowledge of its build (tree_driver.hip, bvh_step_ahead)
   int* spec_dev = nullptr;    // [2] verdict of the build: node count or 0, ok
-  int* spec_host_dev = nullptr;  // spec_host as the device addresses it (kernels write the record there themselves)
-  int* spec_host = nullptr;   // pinned: verdict [2] | build flags + level counters [128] | walk info before [8] and after [8] the walk
+  nbody::StepAheadRecord* spec_host_dev = nullptr;  // spec_host as the device addresses it (kernels write the record there themselves)
+  nbody::StepAheadRecord* spec_host = nullptr;      // pinned
   hipEvent_t spec_event = nullptr;
   // the direct sum at arbitrary points and the tracers' share of a direct step (target_driver.hip): flag word, a batch of targets and results, the FAST partial sums
   void* probe_ws = nullptr;

@@ -92,6 +92,56 @@ template <class T> void record_bvh_levels(State<T>& s, const int* bigcount, bool
   s.bvh_levels_hint = used;
 }
 
+static_assert(kBvhFlagWords + kBvhLevels <= kAheadBuildWords, "flags and level counters travel as one 512-byte block (StepAheadRecord)");
+
+// The f32 device BVH build enqueued blind (tree_build_driver.hip), as bvh_build_device and bvh_step_ahead both do it.
+// How many long-node levels go first: as many as the last tree had (`hint`, 0: unknown — then a balanced tree's, plus two: a
+// lopsided tree has more), plus one.  The spare level is four launches that find nothing to do (19 us of a 1.1 ms step): once the
+// count has stood for eight builds (`stable`) it is dropped — the verdict still checks that no long node is left, and a tree that
+// grows a level then costs ONE repeated step and brings the spare back.  0: no long-node level at all.  (NBODY_BVH_BLIND_LEVELS,
+// laboratory: tests force too few levels.)
+int bvh_blind_levels(int64_t n, int hint, int stable);
+// ... and its tail: subtrees, numbering, and — in the numbering's launch — the row gather into set[1 - cur], the permutation
+// read where the build left it and copied out to order_dev on the way.  `zero8` (optional): eight words that launch clears too.
+int bvh_finish_gather(nbody_ctx* c, State<float>& s, const BvhBuildLayout& L, int sub_start, int* zero8 = nullptr);
+
+// "The bodies themselves" as the targets of a walk over the tree of `kind`, all of them or (count >= 0) the slice
+// [begin, begin + count) of the tree-ordered targets.  `rows`: which set holds the rows in tree order (s.cur once a build is
+// committed).  BVH under AS_WRITTEN: accelerations are computed for the snapshot's rows (main.rs:406-412 iterate `cloned`; tree
+// order = row order after the build's permutation), the other set; the quad tree reaches its rows through the order.
+template <class T> struct WalkTargets {
+  const void* pos = nullptr;
+  int64_t n = 0;
+  int64_t first = 0;                // the slice's first target
+  int64_t acc_first = 0;            // ... and where in `acc` its results start (the quad tree's go through the index)
+  const uint32_t* index = nullptr;  // quad tree: target t is row index[t]
+  const uint32_t* ids = nullptr;    // the targets' particle ids; nullptr: the targets are not the bodies
+};
+template <class T> WalkTargets<T> self_targets(const State<T>& s, int rows, int kind, int order, int64_t begin = 0, int64_t count = -1) {
+  const auto& as_rows = s.set[order == NBODY_ORDER_AS_WRITTEN ? 1 - rows : rows];
+  WalkTargets<T> t;
+  t.first = count >= 0 ? begin : 0;
+  t.n = count >= 0 ? count : s.n;
+  t.ids = as_rows.ids + t.first;
+  if (kind == NBODY_TREE_BVH) { t.pos = as_rows.pos + t.first; t.acc_first = t.first; }
+  else { t.pos = s.set[rows].pos; t.index = s.order_dev + t.first; }
+  return t;
+}
+template <class T> WalkTargets<T> point_targets(const void* pos, int64_t n) {  // any other points (device memory)
+  WalkTargets<T> t;
+  t.pos = pos;
+  t.n = n;
+  return t;
+}
+// What a walk takes from its caller besides the targets (tree_driver.hip, tree_walk_phase).  The bodies' walk: the context's
+// timer and statistics, the state's back-off.
+struct WalkOpts {
+  nbody_timer* timer = nullptr;  // times the walk kernels
+  bool stats = false;            // the walk statistics are collected (by the fused walk: the others do not count)
+  int* backoff = nullptr;        // walks for which the split walks are not tried: read, and moved, through here
+};
+template <class T> WalkOpts bodies_walk(nbody_ctx* c, State<T>& s) { return WalkOpts{c->timer, c->want_stats, &s.ws_backoff}; }
+
 // The walk's parameters and tree arrays; the caller sets the leaves, the targets, `acc` and the node count.
 template <class T> WalkArgs<T> walk_args(const nbody_ctx* c, const State<T>& s, int kind) {
   WalkArgs<T> w{};

@@ -121,18 +121,9 @@ template <class T> int bvh_build_device(nbody_ctx* c, State<T>& s) {
     // the row gather — and checked once at the end: asking in between costs a round trip per question, an empty level
     // a few microseconds.  A lopsided tree still has long nodes then: levels two at a time (asking after each pair)
     // until none is left, then the tail once more for the subtrees that were not there the first time.
-    const int first_levels = bvh_build_first_levels(n);
-    int lv_end = first_levels > 0 ? first_levels + 2 : 0;
-    if (lv_end > 0) lv_end = std::max(1, lab_int("NBODY_BVH_BLIND_LEVELS", lv_end));  // tests force the lopsided path
-    if (lv_end > kBvhKeyDepth + 1) lv_end = kBvhKeyDepth + 1;
+    int lv_end = bvh_blind_levels(n, 0, 0);
     int hostf[kBvhFlagWords + kBvhLevels];
-    auto tail = [&](int sub_start) -> int {
-      GatherArgs<T> g = row_gather_args(s, bvh_build_order(s.bb_scratch, L));  // read where the build left it,
-      g.perm_copy = s.order_dev;                                                 // and copied out on the way
-      HIPCHK(c, bvh_build_finish(c->stream, in.weight, n, leaf, sub_start, s.bb_scratch, L, nullptr, s.geom0, s.geom1, s.link,
-                                 s.node_depth, s.node_mass, s.node_size, &g));  // (numbering and row gather in one launch)
-      return NBODY_OK;
-    };
+    auto tail = [&](int sub_start) -> int { return bvh_finish_gather(c, s, L, sub_start); };
     auto ask = [&]() -> int {
       HIPCHK(c, hipMemcpyAsync(hostf, s.bb_scratch + L.flags, kBvhFlagWords * sizeof(int), hipMemcpyDeviceToHost, c->stream));
       HIPCHK(c, hipMemcpyAsync(hostf + kBvhFlagWords, s.bb_scratch + L.bigcount, kBvhLevels * sizeof(int), hipMemcpyDeviceToHost,
@@ -211,6 +202,22 @@ template <class T> int quad_build_device(nbody_ctx* c, State<T>& s) {
 }
 
 }  // namespace
+
+int bvh_blind_levels(int64_t n, int hint, int stable) {
+  const int first_levels = bvh_build_first_levels(n);
+  int lv_end = first_levels > 0 ? first_levels + 2 : 0;
+  if (lv_end > 0 && hint > 0) lv_end = hint + ((stable >= 8 && lab_int("NBODY_BVH_SPARE_LEVEL", 0) == 0) ? 0 : 1);
+  if (lv_end > 0) lv_end = std::max(1, lab_int("NBODY_BVH_BLIND_LEVELS", lv_end));
+  return std::min(lv_end, kBvhKeyDepth + 1);
+}
+int bvh_finish_gather(nbody_ctx* c, State<float>& s, const BvhBuildLayout& L, int sub_start, int* zero8) {
+  GatherArgs<float> g = row_gather_args(s, bvh_build_order(s.bb_scratch, L));
+  g.perm_copy = s.order_dev;
+  g.zero8 = zero8;
+  HIPCHK(c, bvh_build_finish(c->stream, s.set[s.cur].weight, (int)s.n, c->params.leaf_size, sub_start, s.bb_scratch, L, nullptr, s.geom0,
+                             s.geom1, s.link, s.node_depth, s.node_mass, s.node_size, &g));
+  return NBODY_OK;
+}
 
 // Host image of a device-built tree, for the export API.
 template <class T> int download_tree(nbody_ctx* c, State<T>& s) {

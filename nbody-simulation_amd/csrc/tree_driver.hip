@@ -1,6 +1,6 @@
-// libnbody_hip — the Barnes-Hut step driver: phase timing, the walk phase (main.rs:406-416), the f32 BVH step enqueued whole
+// libnbody_hip — the Barnes-Hut step driver: the walk phase (main.rs:406-416) and its routes, the f32 BVH step enqueued whole
 // ahead of the host (bvh_step_ahead), the plain and the sharded step, the row exchange of a sharded step, and the tree entry
-// points of the C ABI (nbody_update_tree_*, nbody_wait, nbody_accel_tree_*, ...).  Builds: tree_build_driver.hip.
+// points of the C ABI (nbody_update_tree_*, nbody_wait, nbody_accel_tree_*, ...).  Builds: tree_build_driver.hip; phase timing: phase_clock.h.
 // Kernels: walk_prepare.hip, walk_tile.hip, walk_tile_fast.hip, walk_lab.hip (launched through walk_launch.hip), tree_kernels.hip, bvh_build.hip and its units (bvh_units.h).
 #include <algorithm>
 #include <cstdio>
@@ -9,6 +9,7 @@
 
 #include "bvh_build.h"
 #include "driver.h"
+#include "phase_clock.h"
 #include "walk_split.h"
 
 namespace nbody {
@@ -31,78 +32,6 @@ namespace {
 int walk_split_mode() {
   const int mode = env_int("NBODY_WALK_SPLIT", 1);
   return (!kLabBuild && (mode == 2 || mode == 4)) ? 1 : mode;
-}
-
-// ---- phase timing by events (see PhaseEvents in ctx.h)
-// `prev`: the step enqueued just before this one, with nothing in between — its end event doubles as this step's start
-// (every recorded event is a marker in the queue, ~6 us of idle stream: two back to back would be the largest gap of a step).
-// ---- ... and by the kernels' own clock for the steps enqueued ahead (ctx.h, stamp_*): no event records between the phases
-constexpr int kStampSlots = 256;
-int close_open_stamp(nbody_ctx* c) {  // the last stamped step's end, when no stamped step follows it directly
-  if (c->stamp_open < 0) return NBODY_OK;
-  HIPCHK(c, launch_stamp(c->stream, c->stamp_dev + 4 * (size_t)c->stamp_open + 3));
-  c->stamp_open = -1;
-  return NBODY_OK;
-}
-int phase_begin(nbody_ctx* c, PhaseEvents* out, const PhaseEvents* prev = nullptr) {
-  if (int rc = close_open_stamp(c)) return rc;
-  PhaseEvents p;
-  for (int k = prev ? 1 : 0; k < 4; ++k) {
-    if (!c->ph_free.empty()) {
-      p.e[k] = c->ph_free.back();
-      c->ph_free.pop_back();
-    } else {
-      HIPCHK(c, hipEventCreate(&p.e[k]));
-    }
-  }
-  if (prev) {
-    p.e[0] = prev->e[3];
-    p.borrowed = true;
-  } else {
-    HIPCHK(c, hipEventRecord(p.e[0], c->stream));
-  }
-  *out = p;
-  return NBODY_OK;
-}
-int phase_mark(nbody_ctx* c, const PhaseEvents& p, int k) {
-  HIPCHK(c, hipEventRecord(p.e[k], c->stream));
-  if (k == 3) c->ph_pending.push_back(p);
-  return NBODY_OK;
-}
-// One step's phases, in seconds, into the context's Counting and the caller's.
-void book_phases(nbody_ctx* c, const double sec[3]) {
-  for (nbody_counting* k : {&c->counting, c->ph_counter}) {
-    if (!k) continue;
-    k->build_bvh += sec[0];
-    k->sum_gravity += sec[1];
-    k->post_calculations += sec[2];
-  }
-}
-// Reads every recorded step's phases into the context's (and the caller's) Counting.  Waits for them.
-int phase_drain(nbody_ctx* c) {
-  if (int rc = close_open_stamp(c)) return rc;
-  if (!c->stamp_pending.empty()) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::vector<unsigned long long> h((size_t)kStampSlots * 4);
-    HIPCHK(c, hipMemcpy(h.data(), c->stamp_dev, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    for (int slot : c->stamp_pending) {
-      const unsigned long long* t = h.data() + 4 * (size_t)slot;
-      const double sec[3] = {1e-8 * (double)(long long)(t[1] - t[0]), 1e-8 * (double)(long long)(t[2] - t[1]), 1e-8 * (double)(long long)(t[3] - t[2])};  // 100 MHz ticks
-      book_phases(c, sec);
-    }
-    c->stamp_pending.clear();
-  }
-  for (auto& p : c->ph_pending) {
-    HIPCHK(c, hipEventSynchronize(p.e[3]));
-    float ms[3] = {0.f, 0.f, 0.f};
-    for (int k = 0; k < 3; ++k) HIPCHK(c, hipEventElapsedTime(&ms[k], p.e[k], p.e[k + 1]));
-    const double sec[3] = {1e-3 * ms[0], 1e-3 * ms[1], 1e-3 * ms[2]};
-    book_phases(c, sec);
-  }
-  for (auto& p : c->ph_pending)
-    for (int k = p.borrowed ? 1 : 0; k < 4; ++k) c->ph_free.push_back(p.e[k]);
-  c->ph_pending.clear();
-  return NBODY_OK;
 }
 
 // NBODY_TRACE: one line per launched walk that says WHICH walk it was.  Nearly every route computes the same bits by design,
@@ -136,360 +65,312 @@ template <class T> int ensure_walk_scratch(nbody_ctx* c, State<T>& s, const Walk
   return NBODY_OK;
 }
 
-// Phase 2 (main.rs:406-416).  tgt_pos == nullptr: the particles themselves.
-template <class T>
-int tree_walk_phase(nbody_ctx* c, State<T>& s, int kind, const void* tgt_pos, int64_t n_tgt, void* acc,
-                    int64_t slice_begin = 0, int64_t slice_count = -1) {
-  using T2w = typename State<T>::T2;
-  WalkArgs<T> w = walk_args(c, s, kind);
-  w.n_nodes = s.n_nodes;
-  w.acc = acc;
-  w.stats = c->want_stats ? c->stats_dev : nullptr;
-  if (w.stats) HIPCHK(c, hipMemsetAsync(c->stats_dev, 0, 3 * sizeof(unsigned long long), c->stream));
-  const bool bvh = kind == NBODY_TREE_BVH;
-  const auto& leaves = s.set[bvh ? s.cur : 1 - s.cur];  // the quad tree's leaves own copies of their points
-  w.leaf_pos = leaves.pos;
-  w.leaf_mass = leaves.mass;
-  // the particles themselves: all of them, or a contiguous block of tree-ordered targets
-  const int64_t first = slice_count >= 0 ? slice_begin : 0;
-  if (tgt_pos) { w.tgt_pos = tgt_pos; w.n_tgt = n_tgt; }
-  else if (bvh) {
-    // AS_WRITTEN: accelerations are computed for the snapshot's rows (main.rs:406-412 iterate `cloned`); tree order = row
-    // order after the build's permutation
-    const T2w* base = (c->params.order == NBODY_ORDER_AS_WRITTEN) ? s.set[1 - s.cur].pos : s.set[s.cur].pos;
-    w.tgt_pos = base + first;
-    w.acc = (T2w*)acc + first;
-    w.n_tgt = slice_count >= 0 ? slice_count : s.n;
-  } else { w.tgt_pos = s.set[s.cur].pos; w.n_tgt = slice_count >= 0 ? slice_count : s.n; w.tgt_index = s.order_dev + first; }
-  bool done = false;
-  {
-    // Big leaves: a leaf's terms are evaluated lane = particle (walk_tile.hip, walk_tile_fast.hip): in one pass with the terms handed over
-    // through LDS (walk_tile), or in three passes through a term array.  NBODY_WALK_SPLIT: 0 never (fused walk), 1 one pass
-    // when it pays (default), 3 one pass whenever possible; laboratory build only: 4 / 2 three passes when it pays / whenever
-    // possible (the round-1 design the one-pass walk replaced; the product treats them as 1).
-    const int mode = walk_split_mode();
-    const bool tile_mode = mode == 3 || (mode == 1 && w.n_tgt >= 4096);
-    const bool eligible = w.big_leaves && !w.stats && w.n_tgt > 0 && w.n_nodes > 0 && lab_int("NBODY_WALK_PER_THREAD", 0) == 0;
-    if (eligible && tile_mode && (mode == 3 || s.ws_backoff == 0)) {  // one pass, terms through LDS (walk_tile)
-      const WalkSplitLayout L = walk_split_layout(w.n_tgt);
-      int rc = ensure_walk_scratch(c, s, L);
-      if (rc) return rc;
-      const bool self = tgt_pos == nullptr;
-      if (self && !s.wt_hist) {
-        HIPCHK(c, hipMalloc((void**)&s.wt_hist, (size_t)(s.n > 0 ? s.n : 1) * 4));
-        HIPCHK(c, hipMemsetAsync(s.wt_hist, 0, (size_t)(s.n > 0 ? s.n : 1) * 4, c->stream));  // a shard's slice never writes the other ids
-        s.wt_hist_n = -1;
-      }
-      // the targets' particle ids (the snapshot's rows under AS_WRITTEN, the permuted rows otherwise)
-      const uint32_t* tgt_ids = !self ? nullptr
-                                : ((c->params.order == NBODY_ORDER_AS_WRITTEN) ? s.set[1 - s.cur].ids : s.set[s.cur].ids) + first;
-      const bool hist = self && s.wt_hist_n == w.n_tgt && s.wt_hist_begin == slice_begin && lab_int("NBODY_WALK_TILE_COUNT", 0) == 0;
-      int shift = 0;
-      if (hist && (rc = estimate_shift(c, s.wt_total, s.wt_hist, s.n, &shift)) != NBODY_OK) return rc;
-      int info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      unsigned long long total = 0;
-      TileRoute tile_route;
-      for (int estimate = hist ? 1 : 0; !done; estimate = 2) {
-        {
-          TimerScope ts(c->timer, c->stream);
-          HIPCHK(c, launch_tree_walk_tile(c->stream, w, s.ws_scratch, L, tgt_ids, self ? s.wt_hist : nullptr, estimate, shift, &tile_route));
-        }
-        HIPCHK(c, hipMemcpyAsync(info, s.ws_scratch + L.info, sizeof(info), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        std::memcpy(&total, &info[6], 8);
-        if (env_int("NBODY_TRACE", 0) != 0)
-          std::fprintf(stderr, "[nbody] tile walk: %llu terms, estimate %s (shift %d, total %d), %d per wave, overflow %d\n", total,
-                       estimate == 1 ? "from the last walk" : (estimate == 0 ? "counted" : "none"), shift, info[0], info[3], info[1]);
-        trace_route("tile", &tile_route, "plain", false, w.n_tgt, sizeof(T) == 8);
-        // an estimate whose scan does not fit (a counted one past 2^32 terms; counts of older walks under another theta
-        // in a shard's new slice): walk without one (the counts it leaves behind are scaled next time)
-        done = info[1] == 0;
-        if (!done && estimate == 2) return fail(c, NBODY_ERR_HIP, "tile walk: overflow flag without an estimate");
-      }
-      s.wt_hist_n = self ? w.n_tgt : -1;
-      s.wt_hist_begin = slice_begin;
-      s.wt_total = total;
-      if (mode != 3 && walk_near_direct(total, w.n_tgt, s.n)) s.ws_backoff = 64;  // the fused walk; look again in 64 walks
-#ifdef NBODY_LAB
-    } else if (std::is_same<T, float>::value && eligible && (mode == 2 || (mode == 4 && w.n_tgt >= 4096 && s.ws_backoff == 0))) {
-      s.wt_hist_n = -1;
-      const int64_t hard_cap = ((int64_t)1 << 31) - 65536;  // terms (16 GB; the offsets are 32 bits wide); past that the fused walk
-      const WalkSplitLayout L = walk_split_layout(w.n_tgt);
-      if (int rc = ensure_walk_scratch(c, s, L)) return rc;
-      for (int attempt = 0; attempt < 2 && !done; ++attempt) {
-        int info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        {
-          TimerScope ts(c->timer, c->stream);
-          if constexpr (std::is_same<T, float>::value)
-            HIPCHK(c, launch_tree_walk_split(c->stream, w, s.ws_scratch, L, s.ws_terms, s.ws_capacity));
-        }
-        HIPCHK(c, hipMemcpyAsync(info, s.ws_scratch + L.info, sizeof(info), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (env_int("NBODY_TRACE", 0) != 0)
-          std::fprintf(stderr, "[nbody] split walk: %d terms, overflow %d, %d terms per term-pass wave; longest such wave %d us (leaf %d us, node %d us; timing builds)\n",
-                       info[0], info[1], info[3], info[5] >> 20, (info[5] >> 10) & 1023, info[5] & 1023);
-        trace_route("three-pass", nullptr, "none", false, w.n_tgt, sizeof(T) == 8);
-        if (info[1] == 0) {
-          done = true;
-        } else if (info[2] != 0 || info[0] > hard_cap) {
-          s.ws_backoff = 64;  // too many terms for this tree: fused walk for a while
-          break;
-        } else {  // the term array was too small (or absent): half as much again, once
-          free_dev(s.ws_terms);
-          s.ws_capacity = 0;
-          int64_t want = (int64_t)info[0] + info[0] / 2 + 4096;
-          if (want > hard_cap) want = hard_cap;
-          if (hipMalloc(&s.ws_terms, (size_t)want * sizeof(float2)) != hipSuccess) {  // no room: the fused walk needs none
-            (void)hipGetLastError();
-            s.ws_terms = nullptr;
-            s.ws_backoff = 64;
-            break;
-          }
-          s.ws_capacity = want;
-        }
-      }
-#endif
-    } else if (s.ws_backoff > 0 && eligible) {
-      --s.ws_backoff;
-    }
+// Big leaves, one pass: a leaf's terms are evaluated lane = particle and handed over through LDS (walk_tile.hip,
+// walk_tile_fast.hip), the waves cut by an estimate of each target's work: the last walk's counts when these targets have a
+// history, a counting traversal otherwise, none if that estimate's scan does not fit.
+template <class T> int walk_one_pass(nbody_ctx* c, State<T>& s, const WalkArgs<T>& w, const WalkTargets<T>& t, const WalkOpts& o, int mode) {
+  const WalkSplitLayout L = walk_split_layout(w.n_tgt);
+  int rc = ensure_walk_scratch(c, s, L);
+  if (rc) return rc;
+  const bool self = t.ids != nullptr;
+  if (self && !s.wt_hist) {
+    HIPCHK(c, hipMalloc((void**)&s.wt_hist, (size_t)(s.n > 0 ? s.n : 1) * 4));
+    HIPCHK(c, hipMemsetAsync(s.wt_hist, 0, (size_t)(s.n > 0 ? s.n : 1) * 4, c->stream));  // a shard's slice never writes the other ids
+    s.wt_hist_n = -1;
   }
-  if (!done) {
-    const char* route = "none";
+  const bool hist = self && s.wt_hist_n == w.n_tgt && s.wt_hist_begin == t.first && lab_int("NBODY_WALK_TILE_COUNT", 0) == 0;
+  int shift = 0;
+  if (hist && (rc = estimate_shift(c, s.wt_total, s.wt_hist, s.n, &shift)) != NBODY_OK) return rc;
+  int info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned long long total = 0;
+  TileRoute tile_route;
+  for (int estimate = hist ? 1 : 0;; estimate = 2) {
     {
-      TimerScope ts(c->timer, c->stream);
-      HIPCHK(c, launch_tree_walk<T>(c->stream, w, lab_int("NBODY_WALK_PER_THREAD", 0) == 0, &route));
+      TimerScope ts(o.timer, c->stream);
+      HIPCHK(c, launch_tree_walk_tile(c->stream, w, s.ws_scratch, L, t.ids, self ? s.wt_hist : nullptr, estimate, shift, &tile_route));
     }
-    trace_route(route, nullptr, "none", false, w.n_tgt, sizeof(T) == 8);
+    HIPCHK(c, hipMemcpyAsync(info, s.ws_scratch + L.info, sizeof(info), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(&total, &info[6], 8);
+    if (env_int("NBODY_TRACE", 0) != 0)
+      std::fprintf(stderr, "[nbody] tile walk: %llu terms, estimate %s (shift %d, total %d), %d per wave, overflow %d\n", total,
+                   estimate == 1 ? "from the last walk" : (estimate == 0 ? "counted" : "none"), shift, info[0], info[3], info[1]);
+    trace_route("tile", &tile_route, "plain", false, w.n_tgt, sizeof(T) == 8);
+    // an estimate whose scan does not fit (a counted one past 2^32 terms; counts of older walks under another theta
+    // in a shard's new slice): walk without one (the counts it leaves behind are scaled next time)
+    if (info[1] == 0) break;
+    if (estimate == 2) return fail(c, NBODY_ERR_HIP, "tile walk: overflow flag without an estimate");
   }
-  if (w.stats) {
-    HIPCHK(c, hipMemcpyAsync(c->last_stats, c->stats_dev, sizeof(c->last_stats), hipMemcpyDeviceToHost, c->stream));
-  }
+  s.wt_hist_n = self ? w.n_tgt : -1;
+  s.wt_hist_begin = t.first;
+  s.wt_total = total;
+  if (mode != 3 && walk_near_direct(total, w.n_tgt, s.n)) *o.backoff = 64;  // the fused walk; look again in 64 walks
   return NBODY_OK;
 }
 
-// A whole f32 BVH step enqueued AHEAD of the host's knowledge of it.  The plain sequence asks the device three
-// questions per step (is the build complete?  did the walk's estimate wrap?  how many terms were there?) and the old
-// step driver added a wait at every phase boundary: five round trips on a 1.2 ms step.  Here the stream gets, in one go,
+#ifdef NBODY_LAB
+// Laboratory: three passes through a term array (walk_lab.hip; the round-1 design the one-pass walk replaced).  `*done` stays
+// false when the fused walk has to do it: too many terms for this tree, or no room for them.
+int walk_three_pass(nbody_ctx* c, State<float>& s, const WalkArgs<float>& w, const WalkOpts& o, bool* done) {
+  s.wt_hist_n = -1;
+  const int64_t hard_cap = ((int64_t)1 << 31) - 65536;  // terms (16 GB; the offsets are 32 bits wide); past that the fused walk
+  const WalkSplitLayout L = walk_split_layout(w.n_tgt);
+  if (int rc = ensure_walk_scratch(c, s, L)) return rc;
+  for (int attempt = 0; attempt < 2 && !*done; ++attempt) {
+    int info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    {
+      TimerScope ts(o.timer, c->stream);
+      HIPCHK(c, launch_tree_walk_split(c->stream, w, s.ws_scratch, L, s.ws_terms, s.ws_capacity));
+    }
+    HIPCHK(c, hipMemcpyAsync(info, s.ws_scratch + L.info, sizeof(info), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (env_int("NBODY_TRACE", 0) != 0)
+      std::fprintf(stderr, "[nbody] split walk: %d terms, overflow %d, %d terms per term-pass wave; longest such wave %d us (leaf %d us, node %d us; timing builds)\n",
+                   info[0], info[1], info[3], info[5] >> 20, (info[5] >> 10) & 1023, info[5] & 1023);
+    trace_route("three-pass", nullptr, "none", false, w.n_tgt, false);
+    if (info[1] == 0) {
+      *done = true;
+    } else if (info[2] != 0 || info[0] > hard_cap) {
+      *o.backoff = 64;  // too many terms for this tree: fused walk for a while
+      break;
+    } else {  // the term array was too small (or absent): half as much again, once
+      free_dev(s.ws_terms);
+      s.ws_capacity = 0;
+      int64_t want = (int64_t)info[0] + info[0] / 2 + 4096;
+      if (want > hard_cap) want = hard_cap;
+      if (hipMalloc(&s.ws_terms, (size_t)want * sizeof(float2)) != hipSuccess) {  // no room: the fused walk needs none
+        (void)hipGetLastError();
+        s.ws_terms = nullptr;
+        *o.backoff = 64;
+        break;
+      }
+      s.ws_capacity = want;
+    }
+  }
+  return NBODY_OK;
+}
+#endif
+
+// The fused walk (lane = target; tree_kernels.hip): small leaves, walks with statistics, and whatever the split walks leave.
+template <class T> int walk_fused(nbody_ctx* c, const WalkArgs<T>& w, const WalkOpts& o) {
+  const char* route = "none";
+  {
+    TimerScope ts(o.timer, c->stream);
+    HIPCHK(c, launch_tree_walk<T>(c->stream, w, lab_int("NBODY_WALK_PER_THREAD", 0) == 0, &route));
+  }
+  trace_route(route, nullptr, "none", false, w.n_tgt, sizeof(T) == 8);
+  return NBODY_OK;
+}
+
+// Phase 2 (main.rs:406-416): the installed tree walked at `t`, the accelerations to `acc`, by one of the three routes above.
+// NBODY_WALK_SPLIT: 0 never a split walk, 1 one pass when it pays (default), 3 one pass whenever possible; laboratory build only:
+// 4 / 2 three passes when it pays / whenever possible (the product treats them as 1).
+template <class T> int tree_walk_phase(nbody_ctx* c, State<T>& s, int kind, const WalkTargets<T>& t, void* acc, const WalkOpts& o) {
+  WalkArgs<T> w = walk_args(c, s, kind);
+  w.n_nodes = s.n_nodes;
+  w.stats = o.stats ? c->stats_dev : nullptr;
+  if (w.stats) HIPCHK(c, hipMemsetAsync(c->stats_dev, 0, 3 * sizeof(unsigned long long), c->stream));
+  const auto& leaves = s.set[kind == NBODY_TREE_BVH ? s.cur : 1 - s.cur];  // the quad tree's leaves own copies of their points
+  w.leaf_pos = leaves.pos; w.leaf_mass = leaves.mass;
+  w.tgt_pos = t.pos; w.n_tgt = t.n; w.tgt_index = t.index;
+  w.acc = (typename State<T>::T2*)acc + t.acc_first;
+  const int mode = walk_split_mode();
+  const bool pays = w.n_tgt >= 4096 && *o.backoff == 0;
+  const bool eligible = w.big_leaves && !w.stats && w.n_tgt > 0 && w.n_nodes > 0 && lab_int("NBODY_WALK_PER_THREAD", 0) == 0;
+  constexpr bool lab_f32 = kLabBuild && std::is_same<T, float>::value;
+  bool done = false;
+  int rc = NBODY_OK;
+  if (eligible && (mode == 3 || (mode == 1 && pays))) {
+    rc = walk_one_pass<T>(c, s, w, t, o, mode);
+    done = true;
+  } else if (lab_f32 && eligible && (mode == 2 || (mode == 4 && pays))) {
+    if constexpr (lab_f32) rc = walk_three_pass(c, s, w, o, &done);
+  } else if (*o.backoff > 0 && eligible) {
+    --*o.backoff;
+  }
+  if (!rc && !done) rc = walk_fused<T>(c, w, o);
+  if (!rc && w.stats) HIPCHK(c, hipMemcpyAsync(c->last_stats, c->stats_dev, sizeof(c->last_stats), hipMemcpyDeviceToHost, c->stream));
+  return rc;
+}
+
+// A whole f32 BVH step enqueued AHEAD of the host's knowledge of it.  The plain sequence asks the device three questions per step
+// (is the build complete?  did the walk's estimate wrap?  how many terms were there?) and the old step driver added a wait at
+// every phase boundary: five round trips on a 1.2 ms step.  Here the stream gets, in one go,
 //     build (blind: the levels the last tree had, plus one) -> verdict of the build, ON THE DEVICE -> row gather ->
 //     the walk's preparation (estimate scan, wrap check, budget) -> a 0.5 KB copy of {verdict, flags, level counters,
-//     walk info} to pinned memory + an event -> the walk kernel, reading the node count from device memory and
-//     returning at once if the verdict or the preparation said no
-// and the host waits for that EVENT only — it fires when the long kernel starts, so the integration and the whole next
-// step's build are enqueued while the walk runs and the stream never drains between steps.  Everything the host
-// decides on is known before the walk; the rows a step starts from stay intact until it has decided (the gather writes
-// the other set, the integration is enqueued after the decision), so a step whose speculation fails is simply done
-// again by the plain sequence.  The walk's exact term count (next estimate's scale) is read one step late.
-// Returns NBODY_OK (step done), 1 (not applicable / speculation failed: take the plain sequence), or an error.
-constexpr int kSpecWords = 2 + 128 + 8 + 8;  // verdict | flags + level counters (512 B) | info before the walk | info after it
-
+//     walk info} to pinned memory (StepAheadRecord) + an event -> the walk kernel, reading the node count from device memory
+//     and returning at once if the verdict or the preparation said no
+// and the host waits for that EVENT only — it fires when the long kernel starts, so the integration and the whole next step's
+// build are enqueued while the walk runs and the stream never drains between steps.  Everything the host decides on is known
+// before the walk; the rows a step starts from stay intact until it has decided (the gather writes the other set, the integration
+// is enqueued after the decision), so a step whose speculation fails is simply done again by the plain sequence.  The walk's
+// exact term count (next estimate's scale) is read one step late.
 template <class T> int step_ahead_collect(nbody_ctx* c, State<T>& s) {  // the previous ahead-step's term count, if one is due
   if (!s.ahead_total_due) return NBODY_OK;
   s.ahead_total_due = false;
-  const int* post = c->spec_host + 2 + 128 + 8;
   unsigned long long total = 0;
-  std::memcpy(&total, &post[6], 8);
+  std::memcpy(&total, &c->spec_host->info_after[6], 8);
   s.wt_total = total;
   if (walk_near_direct(total, s.n, s.n)) s.ws_backoff = 64;  // the fused walk for a while
   return NBODY_OK;
 }
 
-template <class T> int bvh_step_ahead(nbody_ctx* c, State<T>& s, T delta, PhaseEvents* chain) {
-  if constexpr (!std::is_same<T, float>::value) {
+struct AheadStep {  // one such step, from "it applies" to its decision
+  BvhBuildLayout L;
+  WalkSplitLayout WL;
+  bool fused_scan = false;  // the walk's preparation is the one fused kernel (walk_scan_est_tail)
+  bool stamps = false;      // the phases are timed by the step's own kernels
+  StepClock clock;
+  int lv_end = 0, shift = 0;  // blind levels of the build, scale of the walk's estimate
+  TileRoute route;
+};
+
+// Does the step ahead apply?  NBODY_OK, or 1: take the plain sequence.  Changes nothing but what it allocates the first time.
+int step_ahead_applies(nbody_ctx* c, const State<float>& s, AheadStep& a) {
+  const int n = (int)s.n, leaf = c->params.leaf_size;
+  if (n < 4096 || leaf < 16 || walk_split_mode() != 1 || c->want_stats || s.ws_backoff != 0) return 1;
+  if (!s.wt_hist || s.wt_hist_n != n || s.wt_hist_begin != 0) return 1;  // no walk of these targets to estimate from yet
+  if (env_int("NBODY_STEP_AHEAD", 1) == 0 || env_int("NBODY_TREE_BUILD_HOST", 0) != 0 || lab_int("NBODY_WALK_PER_THREAD", 0) != 0 ||
+      lab_int("NBODY_WALK_TILE_COUNT", 0) != 0)
     return 1;
-  } else {
-    const int n = (int)s.n;
-    const int leaf = c->params.leaf_size;
-    const int mode = walk_split_mode();
-    if (n < 4096 || leaf < 16 || mode != 1 || c->want_stats || s.ws_backoff != 0) return 1;
-    if (!s.wt_hist || s.wt_hist_n != n || s.wt_hist_begin != 0) return 1;  // no walk of these targets to estimate from yet
-    if (env_int("NBODY_STEP_AHEAD", 1) == 0 || env_int("NBODY_TREE_BUILD_HOST", 0) != 0 || lab_int("NBODY_WALK_PER_THREAD", 0) != 0 ||
-        lab_int("NBODY_WALK_TILE_COUNT", 0) != 0)
-      return 1;
-    const BvhBuildLayout L = bvh_build_layout(n, leaf);
-    const WalkSplitLayout WL = walk_split_layout(n);
-    if (s.bb_scratch_bytes < L.total || s.ws_scratch_bytes < WL.total || s.node_cap < (size_t)L.node_cap || s.node_aux_cap < (size_t)L.node_cap)
-      return 1;  // the plain sequence sizes the buffers the first time
-    static_assert(kBvhFlagWords + kBvhLevels <= 128, "flags and level counters travel as one 512-byte block");
-    if (L.bigcount - L.flags + kBvhLevels * sizeof(int) > 128 * sizeof(int)) return 1;
-    if (!c->spec_dev) {
-      HIPCHK(c, hipMalloc((void**)&c->spec_dev, (2 + kSpecWords) * sizeof(int)));  // the verdict, then the record packed for the host
-      HIPCHK(c, hipHostMalloc((void**)&c->spec_host, kSpecWords * sizeof(int), hipHostMallocMapped));
-      HIPCHK(c, hipHostGetDevicePointer((void**)&c->spec_host_dev, c->spec_host, 0));
-      HIPCHK(c, hipEventCreateWithFlags(&c->spec_event, hipEventDisableTiming));
-    }
-    // Phase timing: by the step's own kernels (the 100 MHz wall clock written at the three boundaries: no event records, each of
-    // which leaves ~6 us of idle stream) when the walk's preparation is the one fused kernel; by events otherwise.
-    const bool fused_scan = n <= std::min<int64_t>(kWalkFusedScanMaxTargets, lab_int("NBODY_WALK_FUSED_SCAN_MAX", (int)kWalkFusedScanMaxTargets));
-    const bool stamps = fused_scan && lab_int("NBODY_PHASE_STAMPS", 1) != 0;
-    PhaseEvents ph;
-    int rc = NBODY_OK;
-    unsigned long long* stamp = nullptr;  // this step's slot
-    unsigned long long* stamp_prev_end = nullptr;
-    int slot = -1;
-    if (stamps) {
-      if (!c->stamp_dev) {
-        HIPCHK(c, hipMalloc((void**)&c->stamp_dev, (size_t)kStampSlots * 4 * sizeof(unsigned long long)));
-        HIPCHK(c, hipMemsetAsync(c->stamp_dev, 0, (size_t)kStampSlots * 4 * sizeof(unsigned long long), c->stream));
-      }
-      slot = c->stamp_next;
-      c->stamp_next = (c->stamp_next + 1) % kStampSlots;
-      stamp = c->stamp_dev + 4 * (size_t)slot;
-      if (c->stamp_open >= 0) stamp_prev_end = c->stamp_dev + 4 * (size_t)c->stamp_open + 3;  // bvh_init closes the step before
-      c->stamp_open = -1;
-    } else {
-      rc = phase_begin(c, &ph, chain->e[3] ? chain : nullptr);
-    }
-    *chain = PhaseEvents{};
-    if (rc) return rc;
-    auto& in = s.set[s.cur];
-    auto& out = s.set[1 - s.cur];
-    // ---- build: as many long-node levels as the last tree had, plus one (a balanced tree's, plus two, the first time)
-    const int first_levels = bvh_build_first_levels(n);
-    int lv_end = first_levels > 0 ? first_levels + 2 : 0;
-    // (a lopsided tree has more than a balanced one + 2).  The spare level is four launches that find nothing to do (19 us of a
-    // 1.1 ms step): once the count has stood for eight builds it is dropped — the verdict still checks that no long node is
-    // left (bigcount[lv_end] == 0), and a tree that grows a level then costs ONE repeated step and brings the spare back.
-    if (lv_end > 0 && s.bvh_levels_hint > 0)
-      lv_end = s.bvh_levels_hint + ((s.bvh_levels_stable >= 8 && lab_int("NBODY_BVH_SPARE_LEVEL", 0) == 0) ? 0 : 1);
-    if (lv_end > 0) lv_end = std::max(1, lab_int("NBODY_BVH_BLIND_LEVELS", lv_end));  // tests: too few levels, the verdict fails
-    if (lv_end > kBvhKeyDepth + 1) lv_end = kBvhKeyDepth + 1;
-    const bool flags_clean = s.bb_flags_clean;
-    s.bb_flags_clean = false;
-    HIPCHK(c, bvh_build_begin(c->stream, in.pos, n, s.bb_scratch, L, flags_clean, stamp, stamp_prev_end));
-    if (lv_end > 0) HIPCHK(c, bvh_build_levels(c->stream, n, leaf, 0, lv_end, s.bb_scratch, L));
-    int* walk_info = (int*)(s.ws_scratch + WL.info);
-    GatherArgs<T> g = row_gather_args(s, bvh_build_order(s.bb_scratch, L));  // read where the build left it,
-    g.perm_copy = s.order_dev;                                                 // and copied out on the way
-    g.zero8 = walk_info;  // the estimate check's counters (launch_tree_walk_tile_prep below)
-    // (the numbering's launch gathers the rows too: bvh_emit_gather)
-    HIPCHK(c, bvh_build_finish(c->stream, in.weight, n, leaf, 0, s.bb_scratch, L, nullptr, s.geom0, s.geom1, s.link, s.node_depth,
-                               s.node_mass, s.node_size, &g));
-    if (!stamps) rc = phase_mark(c, ph, 1);
-    if (rc) return rc;
-    // ---- walk (rows as after the build: `out` is the permuted set, `in` the snapshot)
-    WalkArgs<T> w = walk_args(c, s, NBODY_TREE_BVH);  // (leaf >= 16: big leaves)
-    w.n_nodes = 0;
-    w.n_nodes_dev = c->spec_dev;
-    w.acc = s.acc;
-    w.leaf_pos = out.pos;
-    w.leaf_mass = out.mass;
-    const bool as_written = c->params.order == NBODY_ORDER_AS_WRITTEN;
-    w.tgt_pos = as_written ? in.pos : out.pos;
-    w.n_tgt = n;
-    const uint32_t* tgt_ids = as_written ? in.ids : out.ids;
-    int shift = 0;
-    if ((rc = estimate_shift(c, s.wt_total, s.wt_hist, s.n, &shift)) != NBODY_OK) return rc;
-    int64_t waves = 0;
-    // The estimate check's last work-group concludes on the build (the verdict the walk kernel reads), packs verdict, build
-    // flags and walk info for one copy to the host and clears the build's counters for the next step.
-    TileTail tail;
-    tail.flags = (const int*)(s.bb_scratch + L.flags);
-    tail.flag_words = 128;
-    tail.bigcount = (const int*)(s.bb_scratch + L.bigcount);
-    tail.level_end = lv_end;
-    tail.node_cap = L.node_cap;
-    tail.verdict = c->spec_dev;
-    tail.pack = c->spec_host_dev;  // (straight into the host's pinned record: no copy on the stream)
-    tail.clear = (int*)(s.bb_scratch + L.flags);
-    tail.clear_words = (int)((L.zero_end - L.flags) / sizeof(int));
-    tail.info_zeroed = true;
-    // (one kernel instead of three: 17 us against 32 at 151 405 targets, 31 against 67 at a million; NBODY_WALK_FUSED_SCAN_MAX=0: the three)
-    tail.fused_scan = fused_scan;
-    tail.stamp = stamps ? stamp + 1 : nullptr;
-    HIPCHK(c, launch_tree_walk_tile_prep<T>(c->stream, w, s.ws_scratch, WL, tgt_ids, s.wt_hist, 1, shift, &waves, &tail));
-    s.bb_flags_clean = true;
-    int* h = c->spec_host;
-    HIPCHK(c, hipEventRecord(c->spec_event, c->stream));  // (the tail kernel has written h[0 .. 2 + 128 + 8) by then)
-    TileRoute tile_route;
-    {
-      TimerScope ts(c->timer, c->stream);
-      HIPCHK(c, launch_tree_walk_tile_main<T>(c->stream, w, s.ws_scratch, WL, tgt_ids, s.wt_hist, waves, &tile_route));
-    }
-    if (!stamps) rc = phase_mark(c, ph, 2);
-    if (rc) return rc;
-    // ---- the step's one wait: for the event in front of the walk kernel
-    HIPCHK(c, hipEventSynchronize(c->spec_event));
-    rc = step_ahead_collect<T>(c, s);  // (the previous step's copies are older than this event)
-    if (rc) return rc;
-    const int* flags = h + 2;
-    const int* bigcount = flags + (L.bigcount - L.flags) / sizeof(int);
-    const int* info = h + 2 + 128;
-    if (env_int("NBODY_TRACE", 0) != 0) {
-      std::fprintf(stderr, "[nbody] step ahead: build verdict %d (%d nodes, depth %d, fallback %d, %d blind levels)\n", h[1], flags[kBvhNodes],
-                   flags[kBvhMaxDepth], flags[kBvhFallback], lv_end);
-      std::fprintf(stderr, "[nbody] tile walk (step ahead): estimate from the last walk (shift %d, total %d), %d per wave, overflow %d\n", shift,
-                   info[0], info[3], info[1]);
-      trace_route("tile", &tile_route, fused_scan ? "scan-tail" : "check-tail", true, n, false);
-    }
-    if (h[1] == 0) {  // the build needs more levels or the host builder: nothing was integrated, `in` is intact
-      s.wt_hist_n = -1;  // (the walk returned at once and left zeros in the history)
-      s.bvh_levels_hint = 0;
-      s.bvh_levels_stable = 0;
-      if (!stamps) (void)phase_mark(c, ph, 3);  // (a stamped slot is simply not booked: the plain sequence that follows books the step)
-      return 1;
-    }
-    // the build stands: what bvh_build_device records
-    record_bvh_levels(s, bigcount, true);
-    commit_tree(c, s, NBODY_TREE_BVH, flags[kBvhNodes], flags[kBvhMaxDepth], flags[kBvhStops], true, true);
-    c->last_build_device = true;
-    if (info[1] != 0) {  // the estimate's scan wrapped (the walk kernel returned at once): walk again the plain way
-      rc = tree_walk_phase<T>(c, s, NBODY_TREE_BVH, nullptr, 0, s.acc);
-      if (rc) return rc;
-    } else {
-      s.ahead_total_due = true;
-    }
-    Gate carry;  // the walk's info after the walk (its exact term count), read one step late: the integration's first threads take it along
-    carry.carry_src = walk_info;
-    carry.carry_dst = c->spec_host_dev + 2 + 128 + 8;
-    carry.carry_words = 8;
-    carry.stamp = stamps ? stamp + 2 : nullptr;
-    HIPCHK(c, launch_integrate<T>(c->stream, s.set[s.cur].pos, s.set[s.cur].vel, s.acc, s.n, delta, carry));
-    if (stamps) {
-      c->stamp_open = slot;  // its end: the next stamped step's first kernel, or close_open_stamp
-      c->stamp_pending.push_back(slot);
-      return NBODY_OK;
-    }
-    rc = phase_mark(c, ph, 3);
-    if (!rc) *chain = ph;  // the next step starts where this one ends
+  a.L = bvh_build_layout(n, leaf);
+  a.WL = walk_split_layout(n);
+  if (s.bb_scratch_bytes < a.L.total || s.ws_scratch_bytes < a.WL.total || s.node_cap < (size_t)a.L.node_cap || s.node_aux_cap < (size_t)a.L.node_cap)
+    return 1;  // the plain sequence sizes the buffers the first time
+  if (a.L.bigcount - a.L.flags + kBvhLevels * sizeof(int) > sizeof(StepAheadRecord::build)) return 1;
+  if (!c->spec_dev) {
+    HIPCHK(c, hipMalloc((void**)&c->spec_dev, 2 * sizeof(int) + sizeof(StepAheadRecord)));
+    HIPCHK(c, hipHostMalloc((void**)&c->spec_host, sizeof(StepAheadRecord), hipHostMallocMapped));
+    HIPCHK(c, hipHostGetDevicePointer((void**)&c->spec_host_dev, c->spec_host, 0));
+    HIPCHK(c, hipEventCreateWithFlags(&c->spec_event, hipEventDisableTiming));
+  }
+  // Phase timing: by the step's own kernels when the walk's preparation is the one fused kernel; by events otherwise.
+  // (one kernel instead of three: 17 us against 32 at 151 405 targets, 31 against 67 at a million; NBODY_WALK_FUSED_SCAN_MAX=0: the three)
+  a.fused_scan = n <= std::min<int64_t>(kWalkFusedScanMaxTargets, lab_int("NBODY_WALK_FUSED_SCAN_MAX", (int)kWalkFusedScanMaxTargets));
+  a.stamps = a.fused_scan && lab_int("NBODY_PHASE_STAMPS", 1) != 0;
+  return NBODY_OK;
+}
+
+// Build, the walk's preparation, the event the host waits for, the walk: everything up to the step's one decision.
+int step_ahead_enqueue(nbody_ctx* c, State<float>& s, AheadStep& a, PhaseEvents* chain) {
+  const int n = (int)s.n;
+  int rc = a.clock.begin(c, a.stamps, chain);
+  if (rc) return rc;
+  const auto &in = s.set[s.cur], &out = s.set[1 - s.cur];
+  // ---- build
+  a.lv_end = bvh_blind_levels(n, s.bvh_levels_hint, s.bvh_levels_stable);
+  const bool flags_clean = s.bb_flags_clean;
+  s.bb_flags_clean = false;
+  HIPCHK(c, bvh_build_begin(c->stream, in.pos, n, s.bb_scratch, a.L, flags_clean, a.clock.stamp(0), a.clock.stamp_prev_end()));
+  if (a.lv_end > 0) HIPCHK(c, bvh_build_levels(c->stream, n, c->params.leaf_size, 0, a.lv_end, s.bb_scratch, a.L));
+  int* walk_info = (int*)(s.ws_scratch + a.WL.info);  // the estimate check's counters: cleared by the numbering's launch
+  if ((rc = bvh_finish_gather(c, s, a.L, 0, walk_info)) || (rc = a.clock.mark(1))) return rc;
+  // ---- walk (rows as after the build: `out` is the permuted set, `in` the snapshot)
+  WalkArgs<float> w = walk_args(c, s, NBODY_TREE_BVH);  // (leaf >= 16: big leaves)
+  const WalkTargets<float> t = self_targets(s, 1 - s.cur, NBODY_TREE_BVH, c->params.order);
+  w.n_nodes = 0; w.n_nodes_dev = c->spec_dev;  // (the verdict's node count, read on the device)
+  w.leaf_pos = out.pos; w.leaf_mass = out.mass;
+  w.tgt_pos = t.pos; w.n_tgt = t.n; w.acc = s.acc;
+  if ((rc = estimate_shift(c, s.wt_total, s.wt_hist, s.n, &a.shift)) != NBODY_OK) return rc;
+  // The estimate check's last work-group concludes on the build (the verdict the walk kernel reads), packs verdict, build
+  // flags and walk info for the host and clears the build's counters for the next step.
+  TileTail tail;
+  tail.flags = (const int*)(s.bb_scratch + a.L.flags); tail.flag_words = kAheadBuildWords;
+  tail.bigcount = (const int*)(s.bb_scratch + a.L.bigcount); tail.level_end = a.lv_end; tail.node_cap = a.L.node_cap;
+  tail.verdict = c->spec_dev;
+  tail.pack = c->spec_host_dev->verdict;  // (straight into the host's pinned record, from its first word on: no copy on the stream)
+  tail.clear = (int*)(s.bb_scratch + a.L.flags); tail.clear_words = (int)((a.L.zero_end - a.L.flags) / sizeof(int));
+  tail.info_zeroed = true; tail.fused_scan = a.fused_scan; tail.stamp = a.clock.stamp(1);
+  int64_t waves = 0;
+  HIPCHK(c, launch_tree_walk_tile_prep<float>(c->stream, w, s.ws_scratch, a.WL, t.ids, s.wt_hist, 1, a.shift, &waves, &tail));
+  s.bb_flags_clean = true;
+  HIPCHK(c, hipEventRecord(c->spec_event, c->stream));  // (the tail kernel has written the record up to info_before by then)
+  {
+    TimerScope ts(c->timer, c->stream);
+    HIPCHK(c, launch_tree_walk_tile_main<float>(c->stream, w, s.ws_scratch, a.WL, t.ids, s.wt_hist, waves, &a.route));
+  }
+  return a.clock.mark(2);
+}
+
+// The step's one wait — for the event in front of the walk kernel — and what follows from the record: 1 (nothing was integrated,
+// the rows are intact: the plain sequence does the step), or the build stands and the step is integrated.
+int step_ahead_decide(nbody_ctx* c, State<float>& s, AheadStep& a, float delta, PhaseEvents* chain) {
+  HIPCHK(c, hipEventSynchronize(c->spec_event));
+  if (int rc = step_ahead_collect<float>(c, s)) return rc;  // (the previous step's copies are older than this event)
+  const StepAheadRecord& h = *c->spec_host;
+  const int* flags = h.build;
+  const int* bigcount = h.build + (a.L.bigcount - a.L.flags) / sizeof(int);  // the level counters, where the build's layout has them
+  const int* info = h.info_before;
+  if (env_int("NBODY_TRACE", 0) != 0) {
+    std::fprintf(stderr, "[nbody] step ahead: build verdict %d (%d nodes, depth %d, fallback %d, %d blind levels)\n", h.verdict[1],
+                 flags[kBvhNodes], flags[kBvhMaxDepth], flags[kBvhFallback], a.lv_end);
+    std::fprintf(stderr, "[nbody] tile walk (step ahead): estimate from the last walk (shift %d, total %d), %d per wave, overflow %d\n", a.shift,
+                 info[0], info[3], info[1]);
+    trace_route("tile", &a.route, a.fused_scan ? "scan-tail" : "check-tail", true, s.n, false);
+  }
+  if (h.verdict[1] == 0) {  // the build needs more levels or the host builder
+    s.wt_hist_n = -1;  // (the walk returned at once and left zeros in the history)
+    s.bvh_levels_hint = s.bvh_levels_stable = 0;
+    a.clock.give_up();  // (the plain sequence that follows books the step)
+    return 1;
+  }
+  // the build stands: what bvh_build_device records
+  record_bvh_levels(s, bigcount, true);
+  commit_tree(c, s, NBODY_TREE_BVH, flags[kBvhNodes], flags[kBvhMaxDepth], flags[kBvhStops], true, true);
+  c->last_build_device = true;
+  s.ahead_total_due = info[1] == 0;  // (otherwise the estimate's scan wrapped and the walk kernel returned at once: walk again the plain way)
+  if (!s.ahead_total_due)
+    if (int rc = tree_walk_phase<float>(c, s, NBODY_TREE_BVH, self_targets(s, s.cur, NBODY_TREE_BVH, c->params.order), s.acc, bodies_walk(c, s)))
+      return rc;
+  Gate carry;  // the walk's info after the walk (its exact term count), read one step late: the integration's first threads take it along
+  carry.carry_src = (const int*)(s.ws_scratch + a.WL.info);
+  carry.carry_dst = c->spec_host_dev->info_after;
+  carry.carry_words = sizeof(StepAheadRecord::info_after) / sizeof(int); carry.stamp = a.clock.stamp(2);
+  HIPCHK(c, launch_integrate<float>(c->stream, s.set[s.cur].pos, s.set[s.cur].vel, s.acc, s.n, delta, carry));
+  return a.clock.close(chain);  // (events: the next step starts where this one ends)
+}
+
+// Returns NBODY_OK (step done), 1 (not applicable / speculation failed: take the plain sequence), or an error.
+template <class T> int bvh_step_ahead(nbody_ctx* c, State<T>& s, T delta, PhaseEvents* chain) {
+  if constexpr (std::is_same<T, float>::value) {
+    AheadStep a;
+    int rc = step_ahead_applies(c, s, a);
+    if (!rc) rc = step_ahead_enqueue(c, s, a, chain);
+    if (!rc) rc = step_ahead_decide(c, s, a, delta, chain);
     return rc;
   }
+  return 1;
 }
 
 // The tracers' share of a tree step (ctx.h, Tracers): the step's tree walked at the tracers' positions, after the bodies' walk
 // and before anything is integrated (a BVH's leaves ARE the bodies' rows), in batches that bound the walk's scratch; then their
-// integration behind the bodies'.  The timer and the walk statistics stay the bodies' alone, and so does ws_backoff: how many
-// terms the tracers take says nothing about which walk suits the bodies.  (What the tracers' walk does displace is the bodies'
-// history for the next walk's estimate — wt_hist_n — so that walk counts its terms instead; and each batch of a tile walk reads
-// its `info` back, one host wait of the kind the bodies' walk has.)
+// integration behind the bodies'.  The timer and the walk statistics stay the bodies' alone, and so does ws_backoff — the batches
+// move a copy of it: how many terms the tracers take says nothing about which walk suits the bodies.  (What the tracers' walk
+// does displace is the bodies' history for the next walk's estimate — wt_hist_n — so that walk counts its terms instead; and
+// each batch of a tile walk reads its `info` back, one host wait of the kind the bodies' walk has.)
 constexpr int64_t kTracerWalkBatch = 1 << 20;
 template <class T> int tracers_walk(nbody_ctx* c, State<T>& s, int kind) {
   using T2 = typename State<T>::T2;
   const Tracers& tr = c->tracers;
-  nbody_timer* timer = c->timer;
-  const bool want_stats = c->want_stats;
-  const int backoff = s.ws_backoff;
-  c->timer = nullptr;
-  c->want_stats = false;
+  int backoff = s.ws_backoff;
   int rc = NBODY_OK;
   for (int64_t b0 = 0; b0 < tr.m && !rc; b0 += kTracerWalkBatch)
-    rc = tree_walk_phase<T>(c, s, kind, (const T2*)tr.pos + b0, std::min<int64_t>(kTracerWalkBatch, tr.m - b0), (T2*)tr.acc + b0);
-  c->timer = timer;
-  c->want_stats = want_stats;
-  s.ws_backoff = backoff;
+    rc = tree_walk_phase<T>(c, s, kind, point_targets<T>((const T2*)tr.pos + b0, std::min<int64_t>(kTracerWalkBatch, tr.m - b0)), (T2*)tr.acc + b0,
+                            WalkOpts{nullptr, false, &backoff});
   return rc;
 }
 
 // One step in the plain sequence — no host wait between the phases but those a phase needs for itself — over every row, or
 // (count >= 0) a rank's slice [begin, begin + count) of the tree-ordered targets (update_tree_shard).
 template <class T> int plain_tree_step(nbody_ctx* c, State<T>& s, int kind, T delta, int64_t begin = 0, int64_t count = -1) {
-  PhaseEvents ph;
-  int rc = phase_begin(c, &ph);
+  StepClock clock;
+  int rc = clock.begin(c, false);
   if (!rc) rc = tree_build_phase<T>(c, s, kind);
-  if (!rc) rc = phase_mark(c, ph, 1);
-  if (!rc) rc = tree_walk_phase<T>(c, s, kind, nullptr, 0, s.acc, begin, count);
+  if (!rc) rc = clock.mark(1);
+  if (!rc) rc = tree_walk_phase<T>(c, s, kind, self_targets(s, s.cur, kind, c->params.order, begin, count), s.acc, bodies_walk(c, s));
   const bool tracers = count < 0 && c->tracers.m > 0;  // (a sharded step refuses them)
   if (!rc && tracers) rc = tracers_walk<T>(c, s, kind);
-  if (!rc) rc = phase_mark(c, ph, 2);
+  if (!rc) rc = clock.mark(2);
   if (rc) return rc;
   auto& st = s.set[s.cur];
   if (count < 0) {
@@ -501,7 +382,7 @@ template <class T> int plain_tree_step(nbody_ctx* c, State<T>& s, int kind, T de
     hipError_t e = launch_integrate_rows<T>(c->stream, st.pos, st.vel, s.acc, rows, begin, count, delta);
     if (e != hipSuccess) return fail_hip(c, e, "launch_integrate_rows");
   }
-  return phase_mark(c, ph, 3);
+  return clock.close();
 }
 
 // `async`: return once everything is enqueued (for a step ahead: once the host's one decision per step is made) instead of
@@ -512,19 +393,19 @@ template <class T> int update_tree(nbody_ctx* c, int kind, T delta, int n_steps,
   if (n_steps < 0) return fail(c, NBODY_ERR_INVALID, "update_tree: n_steps < 0");
   HIPCHK(c, hipSetDevice(c->device));
   State<T>& s = state_of<T>(c);
-  c->ph_counter = counter;
+  c->phases.counter = counter;
   auto done = [&](int rc) {
     int rc2 = phase_drain(c);  // (waits for the last step: the call is synchronous)
     if (!rc2 && s.ahead_total_due) {
       hipError_t e = hipStreamSynchronize(c->stream);
       rc2 = e == hipSuccess ? step_ahead_collect<T>(c, s) : fail_hip(c, e, "hipStreamSynchronize");
     }
-    c->ph_counter = nullptr;
+    c->phases.counter = nullptr;
     return rc ? rc : rc2;
   };
   PhaseEvents chain;  // the step before, when the next one follows it directly on the stream
   for (int step = 0; step < n_steps; ++step) {
-    if (c->ph_pending.size() >= 64 || c->stamp_pending.size() >= 64) {
+    if (phase_backlog(c)) {
       int rc = phase_drain(c);
       if (rc) return done(rc);
       chain = PhaseEvents{};
@@ -544,7 +425,7 @@ template <class T> int update_tree(nbody_ctx* c, int kind, T delta, int n_steps,
   if (async) {  // the phase events and the last walk's term count are collected by nbody_wait or the next synchronous call
     // (a stamped step's end is written now: whatever the caller does before its next step is not this step's integration)
     if (int rc = close_open_stamp(c)) return rc;
-    c->ph_counter = nullptr;
+    c->phases.counter = nullptr;
     return NBODY_OK;
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -559,10 +440,10 @@ template <class T> int update_tree_shard(nbody_ctx* c, int kind, T delta, int64_
   State<T>& s = state_of<T>(c);
   if (begin < 0 || count < 0 || begin + count > s.n) return fail(c, NBODY_ERR_INVALID, "update_tree_shard: slice out of range");
   HIPCHK(c, hipSetDevice(c->device));
-  c->ph_counter = counter;
+  c->phases.counter = counter;
   auto done = [&](int rc) {
     int rc2 = phase_drain(c);
-    c->ph_counter = nullptr;
+    c->phases.counter = nullptr;
     return rc ? rc : rc2;
   };
   if (int rc = plain_tree_step<T>(c, s, kind, delta, begin, count)) return done(rc);
@@ -604,11 +485,9 @@ template <class T> int accel_built_tree(nbody_ctx* c, State<T>& s, int kind, int
   int rc = NBODY_OK;
   if (!target_xy) {
     // particles themselves, post-build row order, regardless of params.order
-    const void* tp = s.set[s.cur].pos;
-    int saved = c->params.order;
-    c->params.order = NBODY_ORDER_CONSISTENT;
-    rc = tree_walk_phase<T>(c, s, kind, kind == NBODY_TREE_BVH ? tp : nullptr, s.n, s.acc);
-    c->params.order = saved;
+    WalkTargets<T> t = self_targets(s, s.cur, kind, NBODY_ORDER_CONSISTENT);
+    if (kind == NBODY_TREE_BVH) t.ids = nullptr;  // (walked as points at the rows' places: neither uses nor leaves a history)
+    rc = tree_walk_phase<T>(c, s, kind, t, s.acc, bodies_walk(c, s));
     if (rc) return rc;
     if (s.n) HIPCHK(c, hipMemcpyAsync(acc_xy, s.acc, (size_t)s.n * sizeof(T2), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -621,7 +500,7 @@ template <class T> int accel_built_tree(nbody_ctx* c, State<T>& s, int kind, int
   hipError_t e = hipMalloc((void**)&ta, (size_t)n_targets * sizeof(T2));
   if (e != hipSuccess) { (void)hipFree(tp); return fail_hip(c, e, "hipMalloc"); }
   e = hipMemcpyAsync(tp, target_xy, (size_t)n_targets * sizeof(T2), hipMemcpyHostToDevice, c->stream);
-  rc = (e == hipSuccess) ? tree_walk_phase<T>(c, s, kind, tp, n_targets, ta) : fail_hip(c, e, "hipMemcpyAsync");
+  rc = (e == hipSuccess) ? tree_walk_phase<T>(c, s, kind, point_targets<T>(tp, n_targets), ta, bodies_walk(c, s)) : fail_hip(c, e, "hipMemcpyAsync");
   if (!rc) {
     e = hipMemcpyAsync(acc_xy, ta, (size_t)n_targets * sizeof(T2), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
