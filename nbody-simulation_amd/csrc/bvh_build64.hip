@@ -690,9 +690,16 @@ __global__ __launch_bounds__(256) void b64_swap(Ptrs a, int level) {
 }
 
 // ---- the end -----------------------------------------------------------------------------------------------------------
+// Ids that stand for a node.  The counter starts at 1 and grows by two; a request that does not fit (make_children64) leaves it
+// past node_cap without having made its ids, so with an even node_cap the id node_cap - 1 was never handed out: its record is
+// whatever an earlier build, of other rows under another layout, left there, and nobody may follow its begin / length / child.
+__device__ __forceinline__ int ids_made(const Ptrs& a) {
+  const int c = a.flags[kB64NodeCount];
+  return c <= a.node_cap ? c : a.node_cap - 1 + (a.node_cap & 1);
+}
 // make_leaf (bvh_tree.rs:40-54) + the leaf arm of the upward pass (:98-131): box, unweighted mean in slice order, u32 mass
 __global__ __launch_bounds__(256) void b64_leaves(Ptrs a, const uint32_t* __restrict__ weight) {
-  const int m = a.flags[kB64NodeCount] < a.node_cap ? a.flags[kB64NodeCount] : a.node_cap;
+  const int m = ids_made(a);
   const int id = blockIdx.x * 256 + threadIdx.x;
   if (id >= m) return;
   if (!a.nleaf[id]) {
@@ -718,7 +725,7 @@ __global__ __launch_bounds__(256) void b64_leaves(Ptrs a, const uint32_t* __rest
 
 // internal nodes of one depth: centre of gravity as written (bvh_tree.rs:148-154), subtree size
 __global__ __launch_bounds__(256) void b64_up(Ptrs a, int depth) {
-  const int m = a.flags[kB64NodeCount] < a.node_cap ? a.flags[kB64NodeCount] : a.node_cap;
+  const int m = ids_made(a);
   const int id = blockIdx.x * 256 + threadIdx.x;
   if (id >= m || a.nleaf[id] || a.ndepth[id] != depth) return;
   const int l = a.nchild[id];
@@ -735,7 +742,7 @@ __global__ __launch_bounds__(256) void b64_up(Ptrs a, int depth) {
 
 // pre-order numbers, top down: a node, its left subtree, its right subtree
 __global__ __launch_bounds__(256) void b64_pre(Ptrs a, int depth) {
-  const int m = a.flags[kB64NodeCount] < a.node_cap ? a.flags[kB64NodeCount] : a.node_cap;
+  const int m = ids_made(a);
   const int id = blockIdx.x * 256 + threadIdx.x;
   if (id >= m || a.nleaf[id] || a.ndepth[id] != depth) return;
   const int l = a.nchild[id];
@@ -747,7 +754,7 @@ __global__ __launch_bounds__(256) void b64_pre(Ptrs a, int depth) {
 __global__ __launch_bounds__(256) void b64_emit(Ptrs a, double4* __restrict__ geom0, double4* __restrict__ geom1, int4* __restrict__ link,
                                                 int* __restrict__ depth_out, uint32_t* __restrict__ mass_out, double2* __restrict__ size_out,
                                                 uint32_t* __restrict__ order_out) {
-  const int m = a.flags[kB64NodeCount] < a.node_cap ? a.flags[kB64NodeCount] : a.node_cap;
+  const int m = ids_made(a);
   const int id = blockIdx.x * 256 + threadIdx.x;
   if (id < a.n) order_out[id] = a.ID[id];
   if (id >= m) return;

@@ -59,7 +59,8 @@ __global__ __launch_bounds__(256) void bvh_top_upward(BvhPtrs a, const uint32_t*
   __shared__ int s_first[kBvhLevels + 2];  // where the entries of each depth begin: the levels append theirs one after the
                                            // other, so topq is ordered by depth and a level's loop visits its own range only
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n_top = a.flags[kBvhTopCount];
+  // (a declined build goes on drawing slots for the children it could not make, bvh_big_count: topq holds a.cap entries)
+  const int n_top = a.flags[kBvhTopCount] < a.cap ? a.flags[kBvhTopCount] : a.cap;
   if (tid == 0) { a.flags[kBvhBadIndex] = 0; s_dmax = -1; s_nleaf = 0; }
   for (int d = tid; d < kBvhLevels + 2; d += 256) s_first[d] = n_top;
   __syncthreads();
@@ -151,7 +152,8 @@ __device__ __forceinline__ void emit_node(const BvhPtrs& a, const int i, float4*
     return;
   }
   idx += a.npre[v];
-  if (idx < 0 || idx >= m) {
+  // (m is the root's subtree size: on a declined build a sum over whatever was made, not a bound on the arrays — a.cap is)
+  if (idx < 0 || idx >= m || idx >= a.cap) {
     a.flags[kBvhBadIndex] = 1;
     return;
   }

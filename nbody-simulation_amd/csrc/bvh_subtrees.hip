@@ -70,7 +70,9 @@ struct SubLds {
   uint16_t lb[2][kSub / 2], ll[2][kSub / 2];  // node lists of two consecutive levels: begin, length (subtree-relative)
   int lg[2][kSub / 2];                        // ... and breadth-first id
   int lcount[2];
-  int idbase;  // first id of the children made at this level (one allocation per level)
+  // ids of the children made at this level: pair e (children of the level's e-th node) takes idbase + 2 e while 2 e < idsplit
+  // (what was left of the range the work-group held) and idbase2 + 2 e - idsplit after that (the head of a new range)
+  int idbase, idsplit, idbase2;
   int depth_max;  // deepest node made by this work-group
   int id_next, id_end;  // ids this work-group holds (one atomic on the global counter per range, not per level)
   int loff[kBvhKeyDepth + 2];  // where each level of the subtree starts in its list of internal nodes
@@ -78,6 +80,11 @@ struct SubLds {
   float4 gbox[kSubWaves];
   float2 gsum[kSubWaves];
   unsigned gcx[kSubWaves], gcy[kSubWaves], gtot[kSubWaves], gbad[kSubWaves];
+};
+
+struct LevelIds {  // (a copy in registers: the three words are read once per level, side by side)
+  int base, split, base2;
+  __device__ __forceinline__ int pair_first(int e) const { return 2 * e < split ? base + 2 * e : base2 + 2 * e - split; }
 };
 
 // One node whose points are s.P[lb, lb+len): fold, axis, partition, children — by ONE wave.  Up to kSub points the
@@ -169,7 +176,7 @@ __device__ __forceinline__ void node_in_lds(const BvhPtrs& a, SubLds& s, int gbe
 // swaps are split G ways.  Every wave runs the same number of barriers
 // (the longest node of the level sets the number of rank-list rounds).
 template <int G>
-__device__ __forceinline__ void nodes_by_groups(const BvhPtrs& a, SubLds& s, int gbegin, int cur, int nc, int idbase, int tid,
+__device__ __forceinline__ void nodes_by_groups(const BvhPtrs& a, SubLds& s, int gbegin, int cur, int nc, LevelIds ids, int tid,
                                                 int leaf_size, int depth) {
   static_assert(G >= 2 && kSubWaves % G == 0, "at least one wave beside the chain's");
   constexpr int TILE = 64 * kEPT;
@@ -275,7 +282,7 @@ __device__ __forceinline__ void nodes_by_groups(const BvhPtrs& a, SubLds& s, int
   if (act && gw == 0 && lane == 0) {
     a.nbox[gid] = make_float4(box.mnx, box.mny, box.mxx, box.mxy);
     bool leaf[2];
-    const int first = idbase + 2 * grp;
+    const int first = ids.pair_first(grp);
     make_children(a, gid, first, gbegin + lb, len, m, leaf_size, leaf, &s.depth_max, depth);
     const int nxt = cur ^ 1;
     for (int side = 0; side < 2; ++side) {
@@ -335,36 +342,50 @@ __global__ __launch_bounds__(kSubWaves * 64) void bvh_subtrees(BvhPtrs a, const 
         // ids for this level's children out of the work-group's range; a new range when it runs out.  726 work-groups (1 M
         // points) asking the one global counter at every level wait ~60 ns per request ahead of them.
         const int want = 2 * nc;
-        if (s.id_end - s.id_next < want) {
-          // the first range is what ANY tree over these points needs (leaves hold at most leaf_size points: at least
-          // len / leaf_size of them, twice as many nodes less the root's own id) and is used up to the last id; later ones
-          // (a quarter of that) may leave a few ids unused.  If the ids are nearly out, the exact count is asked for.
-          const int sure = 2 * (len / leaf_size) - 2;
-          int range = s.id_end == 0 ? sure : sure / 4;
-          range = range > want ? range : want;
-          int first = range > want ? try_alloc_nodes(a, range) : -1;
-          if (first < 0) {
-            range = want;
-            first = alloc_nodes(a, want);
-          }
-          s.id_next = first;
-          s.id_end = first < 0 ? first : first + range;
-        }
+        const int have = s.id_end - s.id_next;  // (even, like every request: the two children of a node are neighbours)
         s.idbase = s.id_next;
-        if (s.id_next >= 0) s.id_next += want;
+        if (have >= want) {
+          s.idsplit = want;
+          s.id_next += want;
+        } else {
+          // What the range still holds is used first and the new range begins in mid-level: a level that dropped the rest of
+          // its range (a third of the first range, on a scene of many small clusters) cost more ids than the reserve has to
+          // spare (bvh_build_layout), and a tree that fits was declined.
+          // The first range is what ANY tree over these points needs (leaves hold at most leaf_size points: at least
+          // len / leaf_size of them, twice as many nodes less the root's own id) and is used up to the last id; later ones
+          // (a quarter of that) may leave a few ids unused at the subtree's end.  If the ids are nearly out, the exact count
+          // is asked for.
+          const int need = want - have;
+          const int sure = 2 * (len / leaf_size) - 2;
+          int range = s.id_end == 0 ? sure : (sure / 4) & ~1;
+          range = range > need ? range : need;
+          int first = range > need ? try_alloc_nodes(a, range) : -1;
+          if (first < 0) {
+            range = need;
+            first = alloc_nodes(a, need);
+          }
+          if (first < 0) {
+            s.idbase = -1;
+          } else {
+            s.idsplit = have;
+            s.idbase2 = first;
+            s.id_next = first + need;
+            s.id_end = first + range;
+          }
+        }
       }
       __syncthreads();
-      const int idbase = s.idbase;
-      if (idbase < 0) break;
+      const LevelIds ids{s.idbase, s.idsplit, s.idbase2};
+      if (ids.base < 0) break;
       nint += nc;
       ++nlev;
       const int depth = root_depth + nlev - 1;  // of this level's nodes (nlev counts this level already)
-      if (nc == 1) nodes_by_groups<kSubWaves>(a, s, b, cur, nc, idbase, tid, leaf_size, depth);
-      else if (nc == 2) nodes_by_groups<kSubWaves / 2>(a, s, b, cur, nc, idbase, tid, leaf_size, depth);
-      else if (nc <= 4) nodes_by_groups<kSubWaves / 4>(a, s, b, cur, nc, idbase, tid, leaf_size, depth);
+      if (nc == 1) nodes_by_groups<kSubWaves>(a, s, b, cur, nc, ids, tid, leaf_size, depth);
+      else if (nc == 2) nodes_by_groups<kSubWaves / 2>(a, s, b, cur, nc, ids, tid, leaf_size, depth);
+      else if (nc <= 4) nodes_by_groups<kSubWaves / 4>(a, s, b, cur, nc, ids, tid, leaf_size, depth);
       else
         for (int e = wave; e < nc; e += kSubWaves)  // a wave per node
-          node_in_lds(a, s, b, s.lb[cur][e], s.ll[cur][e], s.lg[cur][e], idbase + 2 * e, lane, cur ^ 1, leaf_size, depth);
+          node_in_lds(a, s, b, s.lb[cur][e], s.ll[cur][e], s.lg[cur][e], ids.pair_first(e), lane, cur ^ 1, leaf_size, depth);
       __syncthreads();
       if (tid == 0) s.lcount[cur] = 0;
       cur ^= 1;
@@ -373,6 +394,10 @@ __global__ __launch_bounds__(kSubWaves * 64) void bvh_subtrees(BvhPtrs a, const 
       if (nlev == 2) NB_STAMP(2)
       if (nlev == 3) NB_STAMP(3)
     }
+    // A subtree that stopped early (no ids left, or degenerate input: the fallback flag is up) leaves the nodes of `cur` unsplit
+    // and unlisted.  Neither leaves nor parents, nobody below gives them a size, but the upward passes and the numbering add
+    // their sizes up: one node each, not what an earlier build left in the record.
+    for (int e = tid; e < s.lcount[cur]; e += kSubWaves * 64) a.nsize[s.lg[cur][e]] = 1;
     if (tid == 0) {
       s.loff[nlev] = nint;
       if (s.depth_max > 0) atomicMax(&a.flags[kBvhMaxDepth], s.depth_max);
