@@ -38,10 +38,11 @@
  *     books them (`counter` may be NULL).
  *   Params.  nbody_default_params' values at creation; clamp and arith are used, the rest is kept and ignored.
  *   Not offered: f64 on this handle (nbody_ensemble64_* below is the double-precision sibling); worlds of different sizes on
- *     this handle (nbody_ragged_* at the end of this file steps them together); a per-world delta or clamp; tree methods;
+ *     this handle (nbody_ragged_* at the end of this file steps them together); tree methods;
  *     tracers on this handle (nbody_restricted_* at the end of this file); several devices; asynchronous snapshots and delta streams
  *     on a copy stream (the synchronous streams are nbody_deltas_* and the frames nbody_frames_*, both at the end of this
- *     file); hipGraph replay.  The library reads no environment variable for any of this.
+ *     file); hipGraph replay.  The library reads no environment variable for any of this.  (A time step, a clamp and a number
+ *     of steps per world: nbody_sweep_* at the end of this file.)
  * Arrays are world-major, [n_worlds][n_bodies] rows, pos / vel interleaved x,y; weight may be NULL (all 1); an upload replaces
  * the previous ensemble, whatever its shape. */
 typedef struct nbody_ensemble nbody_ensemble;
@@ -115,7 +116,7 @@ int nbody_ensemble64_accel(nbody_ensemble64* e, double* acc_xy);                
  *     its (contiguous) blocks in that launch, the number of launches, and per launch (arrays of NBODY_RAGGED_MAX_LAUNCHES, zero
  *     past n_launches) the dynamic LDS and the number of blocks.  It is pure host code: no device, no handle, every output
  *     pointer may be NULL; sizes outside the limits give NBODY_ERR_INVALID and nothing is written.
- *   Not offered on this handle: f64 (nbody_ragged64_* below is the double-precision sibling), a per-world delta or clamp,
+ *   Not offered on this handle: f64 (nbody_ragged64_* below is the double-precision sibling),
  *     tracers (nbody_rr_* at the end of this file steps worlds of different sizes with tracers of their own), tree methods,
  *     several devices, and what the ensemble above does not offer either. */
 #define NBODY_RAGGED_MAX_LAUNCHES 6
@@ -344,7 +345,7 @@ int nbody_restricted64_tracers_accel(nbody_restricted64* e, double* acc_xy);    
  *   Errors.  There is no CPU path: nbody_rr_create fails with NBODY_ERR_NO_DEVICE without a gfx950 device.  A NULL handle gives
  *     NBODY_ERR_INVALID (0 from nbody_rr_num_worlds / _num_rows / _num_tracer_rows); nbody_rr_last_error(NULL): the last failed
  *     nbody_rr_create or nbody_rr_plan on this thread, in a slot of its own.
- *   Not offered on this handle: f64 (nbody_rr64_* below is the double-precision sibling); a per-world delta or clamp; tree methods; several
+ *   Not offered on this handle: f64 (nbody_rr64_* below is the double-precision sibling); tree methods; several
  *     devices; asynchronous snapshots and delta streams on a copy stream (the synchronous streams are nbody_deltas_rr and the
  *     frames nbody_frames_rr, both at the end of this file); hipGraph replay.  The library reads no environment variable for any
  *     of this. */
@@ -539,5 +540,61 @@ int nbody_deltas_rr(nbody_rr* e, uint32_t flags, uint8_t* out, size_t cap, size_
 int nbody_deltas_rr64(nbody_rr64* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* offsets_out,
                       uint64_t* step_out);
 size_t nbody_deltas_bound(int64_t n_segments, const int64_t* rows /*[n_segments], each >= 0*/, int is_f64);
+
+/* ---- sweeps of an ensemble: a time step, a clamp and a number of steps per world ---------------------------------
+ * What the ensembles are for — a time-step convergence study, a softening sweep — for all eight handles above: *_update steps
+ * every world by one delta under one params.clamp, so a study over either was one handle per value again.  A sweep is an update
+ * in which world k steps by delta[k] under clamp[k] and takes steps[k] steps: a convergence study steps world k with delta_k =
+ * T / steps_k, so the worlds need different step counts to reach the same end time.
+ *   The prefix.  nbody_sweep_<handle>: the names under each handle's own prefix, under nbody_frames_ and under nbody_deltas_
+ *     are closed sets, so these eight have a prefix of their own.
+ *   Arguments.  delta, clamp and steps are host arrays of n_worlds elements, read during the call only.  The call is stateless:
+ *     nothing of a sweep stays in the handle (params are neither read back nor changed), so uploads, set_params, frames and
+ *     delta streams need no new rule.
+ *       delta[k]   required.  World k's time step, used as *_update's delta is (v += a*dt; x += v*dt, multiply then add, no
+ *                  contraction).  Any value is taken, as *_update takes any.  double on the f64 handles.
+ *       clamp[k]   may be NULL: every world uses params.clamp.  float on all eight handles, as params.clamp is; widened to double
+ *                  on the f64 handles.
+ *       steps[k]   may be NULL: every world takes n_steps steps.  World k takes the first steps[k] of the call's n_steps steps and
+ *                  then stands still: its positions and velocities (and its tracers') keep their bits exactly, whatever they are
+ *                  (-0.0, NaN payloads, infinities).  0 <= steps[k] <= n_steps.
+ *   Per-world contract.  World k's bits are those of a handle of the same kind holding world k alone, with params.clamp =
+ *     clamp[k], stepped by *_update(delta[k], steps[k]) — under the handle's arith, for bodies and tracers.  So the handles'
+ *     promises carry over world by world: EXACT is bit-identical to the CPU restatement's update_direct of that world with its
+ *     own delta, clamp and nsteps (tracers: its direct_accel at the tracers plus the Euler step); FAST and AUTO are bit-identical
+ *     to that world alone on the same kind of handle.
+ *   Independence.  As every handle states it, and: a world's bits do not depend on the other worlds' delta, clamp or steps, nor
+ *     on n_steps beyond steps[k], nor on how a sweep is split over calls (steps split accordingly).
+ *   Route.  The tests that turn a whole handle EXACT for its clamp are taken per world, on the device, by the blocks of that
+ *     world: on the f32 handles a world whose clamp[k] is below 2^-19, or NaN, takes EXACT for the call (under AUTO, and under
+ *     FAST asked for by name); on the f64 handles a world takes FAST only under arith FAST with clamp[k] > 0.  Its neighbours keep
+ *     their FAST bits.  With clamp given, params.clamp decides nothing.  arith EXACT sends every world to EXACT; the per-step
+ *     decision of AUTO on a world's positions and the per-tracer exception in a FAST world are what they were.
+ *   Calls.  Synchronous: n_steps steps enqueued back to back on the handle's stream, one synchronisation at the end, nothing
+ *     read back in between.  The launches per step are those of *_update (1; 2 with tracers; at most 6 ragged; at most 12 ragged
+ *     restricted), whatever steps[] holds.  The seconds are booked under sum_gravity, as *_update books them.
+ *   Step count.  The handle's count of steps (nbody_deltas_*) advances by n_steps: it counts the handle's launches.  A world's
+ *     stream header after a sweep therefore carries the handle's count, not the number of steps that world has itself taken.
+ *   Refusals.  NBODY_ERR_INVALID before anything is allocated or enqueued, the message beginning with the handle's word
+ *     ("ensemble", "ragged", "restricted", "ragged restricted") and naming "sweep": nothing uploaded; delta NULL; n_steps < 0; a
+ *     steps[k] outside [0, n_steps] (the message names the world).  n_steps == 0 after those checks is a no-op.  A NULL handle
+ *     gives NBODY_ERR_INVALID without a message.
+ *   Not offered: a per-world arith; per-world parameters for *_accel (it keeps params.clamp); a device-pointer variant; hipGraph
+ *     replay of a sweep; anything for nbody_ctx contexts. */
+int nbody_sweep_ensemble(nbody_ensemble* e, const float* delta, const float* clamp, const int32_t* steps, int n_steps,
+                         nbody_counting* counter);
+int nbody_sweep_ensemble64(nbody_ensemble64* e, const double* delta, const float* clamp, const int32_t* steps, int n_steps,
+                           nbody_counting* counter);
+int nbody_sweep_ragged(nbody_ragged* e, const float* delta, const float* clamp, const int32_t* steps, int n_steps,
+                       nbody_counting* counter);
+int nbody_sweep_ragged64(nbody_ragged64* e, const double* delta, const float* clamp, const int32_t* steps, int n_steps,
+                         nbody_counting* counter);
+int nbody_sweep_restricted(nbody_restricted* e, const float* delta, const float* clamp, const int32_t* steps, int n_steps,
+                           nbody_counting* counter);
+int nbody_sweep_restricted64(nbody_restricted64* e, const double* delta, const float* clamp, const int32_t* steps, int n_steps,
+                             nbody_counting* counter);
+int nbody_sweep_rr(nbody_rr* e, const float* delta, const float* clamp, const int32_t* steps, int n_steps, nbody_counting* counter);
+int nbody_sweep_rr64(nbody_rr64* e, const double* delta, const float* clamp, const int32_t* steps, int n_steps,
+                     nbody_counting* counter);
 
 #endif /* NBODY_ENSEMBLE_H */

@@ -212,6 +212,10 @@ _SIGS = {
     **{"nbody_deltas_" + h: (C.c_int, [_vp, C.c_uint32, _vp, _sz, C.POINTER(_sz), _vp, C.POINTER(C.c_uint64)])
        for h in ("ensemble", "ensemble64", "ragged", "ragged64", "restricted", "restricted64", "rr", "rr64")},
     "nbody_deltas_bound": (_sz, [_i64, _vp, C.c_int]),
+    # nbody_sweep_<handle>: delta[n_worlds] in the handle's precision, clamp[n_worlds] float on all eight, steps[n_worlds] int32
+    **{"nbody_sweep_" + h: (C.c_int, [_vp, C.POINTER(_f64 if h.endswith("64") else _f32), C.POINTER(_f32), C.POINTER(C.c_int32), _i32,
+                                      C.POINTER(Counting)])
+       for h in ("ensemble", "ensemble64", "ragged", "ragged64", "restricted", "restricted64", "rr", "rr64")},
     "nbody_accel_tree_f32": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_accel_tree_f64": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_tree_info": (C.c_int, [_vp, C.POINTER(TreeView)]),
@@ -988,6 +992,16 @@ class _EnsembleHandleBase:
         acc = np.zeros((b, n, 2), self._dtype)
         self._check(self._call("_accel" + self._suffix, _ptr(acc)))
         return acc
+
+    def sweep(self, delta, clamp, steps, n_steps, counter: "Counting | None" = None):
+        """nbody_sweep_<handle>: delta [worlds] of the handle's dtype, clamp float32[worlds] or None, steps int32[worlds] or None,
+        all contiguous (ensemble.py's `sweep` checks and casts them)."""
+        def typed(a, ctype):
+            return None if a is None else a.ctypes.data_as(C.POINTER(ctype))
+        name = "nbody_sweep_" + self._prefix[len("nbody_"):]
+        real = C.c_double if self._dtype == np.float64 else C.c_float
+        self._check(getattr(self.lib, name)(self.h, typed(delta, real), typed(clamp, C.c_float), typed(steps, C.c_int32), int(n_steps),
+                                            C.byref(counter) if counter is not None else None))
 
     _frames_tracers = False   # the handle's nbody_frames_* call takes with_tracers
 

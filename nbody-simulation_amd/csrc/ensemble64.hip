@@ -31,3 +31,8 @@ NB_API int nbody_deltas_ensemble64(nbody_ensemble64* e, uint32_t flags, uint8_t*
                                    uint64_t* step_out) {
   return ens_deltas<EnsF64>(e, flags, out, cap, bytes_out, offsets_out, step_out);
 }
+// (a sweep — a time step, a clamp and a number of steps per world, include/nbody_ensemble.h: likewise a prefix of its own)
+NB_API int nbody_sweep_ensemble64(nbody_ensemble64* e, const double* delta, const float* clamp, const int32_t* steps, int n_steps,
+                                  nbody_counting* counter) {
+  return ens_sweep<EnsF64>(e, delta, clamp, steps, n_steps, counter);
+}

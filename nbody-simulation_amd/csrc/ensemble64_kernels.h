@@ -23,6 +23,13 @@
 
 namespace nbody {
 
+// Sweeps (nbody_sweep_*) in f64: a world's own time step, clamp (the caller's float, widened) and number of steps.  One entry
+// per world, 24 bytes, read once per block by scalar loads.
+struct Ens64SweepWorld {
+  double delta, clamp;
+  int32_t steps, pad;
+};
+
 struct Ensemble64Args {
   const double2* pos_in = nullptr;   // [n_worlds][n_bodies], read by every block of the world
   const uint32_t* weight = nullptr;  // the mass is `weight as f64`
@@ -33,6 +40,10 @@ struct Ensemble64Args {
   unsigned tiles = 1;                // blocks per world
   double delta = 0.0, clamp = 0.0;
   int fast = 0;                      // FAST where the world's positions allow it; 0: every world EXACT
+  // a sweep's launches only, as in EnsembleArgs
+  const Ens64SweepWorld* sweep = nullptr;
+  const uint32_t* item_world = nullptr;
+  int step = 0;
 };
 
 // kEns64TermBlock, ensemble64_padded and ensemble64_lds_bytes come from ensemble_shape.h (plain C++: the ragged plan uses them).

@@ -78,30 +78,64 @@ __device__ __forceinline__ void ens64_world_tile(const Ensemble64Args& a, const 
   if (live && part == 0) ens_integrate(a, row0 + t, p.x, p.y, ax[0], ay[0]);
 }
 
+// Sweeps (nbody_sweep_*), as ensemble_kernels.hip states them: the world's entry by scalar loads once per block; a finished world
+// carries its tile of pos_in over to pos_out as raw bits and returns before the staging and its barriers; otherwise delta, clamp
+// and the route are the world's own in a copy of the arguments — direct_fast_f64's test on the world's clamp: FAST only with a
+// clamp > 0 (a NaN fails it), for every block of the world and of its tracers.  The plain launches are the SWEEP = false
+// instantiations.  No static LDS in either.
 template <int SPLIT>
+__device__ __forceinline__ void ens64_carry_tile(const Ensemble64Args& a, const int n, const size_t row0, const unsigned tile) {
+  constexpr int TPB = kEnsembleBlock / SPLIT;
+  const int t = (int)tile * TPB + (int)threadIdx.x;
+  if ((int)threadIdx.x >= TPB || t >= n) return;
+  const uint4* in = reinterpret_cast<const uint4*>(a.pos_in);
+  uint4* out = reinterpret_cast<uint4*>(a.pos_out);
+  out[row0 + t] = in[row0 + t];
+}
+
+template <int SPLIT, bool SWEEP>
+__device__ __forceinline__ void ens64_step_block(const Ensemble64Args& a, const int n, const size_t row0, const unsigned tile,
+                                                 const unsigned world) {
+  if constexpr (SWEEP) {
+    Ensemble64Args b = a;
+    if (!ens64_sweep_args(b, world)) {
+      ens64_carry_tile<SPLIT>(a, n, row0, tile);
+      return;
+    }
+    ens64_world_tile<SPLIT>(b, n, row0, tile);
+  } else {
+    ens64_world_tile<SPLIT>(a, n, row0, tile);
+  }
+}
+
+template <int SPLIT, bool SWEEP>
 __global__ __launch_bounds__(kEnsembleBlock) void ensemble64_step(const Ensemble64Args a) {
   const int n = a.n_bodies;
   const unsigned world = blockIdx.x / a.tiles, tile = blockIdx.x - world * a.tiles;
-  ens64_world_tile<SPLIT>(a, n, (size_t)world * (size_t)n, tile);
+  ens64_step_block<SPLIT, SWEEP>(a, n, (size_t)world * (size_t)n, tile, world);
 }
 
 // Ragged: the block's work item {row0, n | tile << 16} is the same in every lane (its address is a function of blockIdx.x
 // alone, and readfirstlane says so to the compiler), so the switch on the world's lane split is taken by the whole block — the
 // barriers of the staging and the butterfly of FAST see every thread.  No static LDS here either.
+// Under a sweep the item's world comes from a.item_world, a table beside the items'.
+template <bool SWEEP>
 __global__ __launch_bounds__(kEnsembleBlock) void ensemble64_step_ragged(const Ensemble64Args a, const uint2* __restrict__ items) {
   const uint2 item = items[blockIdx.x];
   const size_t row0 = (size_t)(unsigned)__builtin_amdgcn_readfirstlane(item.x);
   const unsigned packed = __builtin_amdgcn_readfirstlane(item.y);
   const int n = (int)(packed & 0xffffu);
   const unsigned tile = packed >> 16;
+  unsigned world = 0;
+  if constexpr (SWEEP) world = __builtin_amdgcn_readfirstlane(a.item_world[blockIdx.x]);
   switch (ensemble_split(n)) {
-    case 1: ens64_world_tile<1>(a, n, row0, tile); break;
-    case 2: ens64_world_tile<2>(a, n, row0, tile); break;
-    case 4: ens64_world_tile<4>(a, n, row0, tile); break;
-    case 8: ens64_world_tile<8>(a, n, row0, tile); break;
-    case 16: ens64_world_tile<16>(a, n, row0, tile); break;
-    case 32: ens64_world_tile<32>(a, n, row0, tile); break;
-    default: ens64_world_tile<64>(a, n, row0, tile); break;
+    case 1: ens64_step_block<1, SWEEP>(a, n, row0, tile, world); break;
+    case 2: ens64_step_block<2, SWEEP>(a, n, row0, tile, world); break;
+    case 4: ens64_step_block<4, SWEEP>(a, n, row0, tile, world); break;
+    case 8: ens64_step_block<8, SWEEP>(a, n, row0, tile, world); break;
+    case 16: ens64_step_block<16, SWEEP>(a, n, row0, tile, world); break;
+    case 32: ens64_step_block<32, SWEEP>(a, n, row0, tile, world); break;
+    default: ens64_step_block<64, SWEEP>(a, n, row0, tile, world); break;
   }
 }
 
@@ -121,17 +155,26 @@ hipError_t ens64_raise_lds_limit(const void* kernel, std::atomic<bool>* raised) 
 
 hipError_t launch_ensemble64_step(hipStream_t s, int64_t n_worlds, Ensemble64Args a) {
   if (n_worlds < 1 || a.n_bodies < 1 || a.n_bodies > kEnsembleMaxBodies || n_worlds * a.n_bodies > kEnsembleMaxRows) return hipErrorInvalidValue;
+  if (a.sweep && (!a.pos_out || !a.vel)) return hipErrorInvalidValue;  // (a sweep is a step: a finished world writes pos_out)
   const int split = ensemble_split(a.n_bodies);
   const int tpb = kEnsembleBlock / split;
   a.tiles = (unsigned)((a.n_bodies + tpb - 1) / tpb);
   const dim3 grid((unsigned)(n_worlds * a.tiles));  // <= 2^26 blocks
   const size_t lds = ensemble64_lds_bytes(a.n_bodies);
   if (lds > 65536) {
-    static std::atomic<bool> raised[64];
-    const hipError_t h = ens64_raise_lds_limit(reinterpret_cast<const void*>(&ensemble64_step<1>), raised);
+    static std::atomic<bool> raised[64], raised_sweep[64];  // (each instantiation is a function of its own)
+    const hipError_t h = a.sweep ? ens64_raise_lds_limit(reinterpret_cast<const void*>(&ensemble64_step<1, true>), raised_sweep)
+                                 : ens64_raise_lds_limit(reinterpret_cast<const void*>(&ensemble64_step<1, false>), raised);
     if (h != hipSuccess) return h;
   }
-#define NB_ENS64_GO(S) hipLaunchKernelGGL(ensemble64_step<S>, grid, dim3(kEnsembleBlock), lds, s, a)
+#define NB_ENS64_GO(S)                                                                    \
+  do {                                                                                  \
+    if (a.sweep) {                                                                      \
+      hipLaunchKernelGGL((ensemble64_step<S, true>), grid, dim3(kEnsembleBlock), lds, s, a);  \
+    } else {                                                                            \
+      hipLaunchKernelGGL((ensemble64_step<S, false>), grid, dim3(kEnsembleBlock), lds, s, a); \
+    }                                                                                   \
+  } while (0)
   switch (split) {
     case 1: NB_ENS64_GO(1); break;
     case 2: NB_ENS64_GO(2); break;
@@ -147,12 +190,18 @@ hipError_t launch_ensemble64_step(hipStream_t s, int64_t n_worlds, Ensemble64Arg
 
 hipError_t launch_ensemble64_step_ragged(hipStream_t s, int64_t blocks, size_t lds_bytes, const uint2* items, Ensemble64Args a) {
   if (blocks < 1 || blocks > kEnsembleMaxRows || !items || lds_bytes > ensemble64_lds_bytes(kEnsembleMaxBodies)) return hipErrorInvalidValue;
+  if (a.sweep && (!a.item_world || !a.pos_out || !a.vel)) return hipErrorInvalidValue;
   if (lds_bytes > 65536) {  // its own function, so its own limit: the uniform kernel's raised one does not cover it
-    static std::atomic<bool> raised[64];
-    const hipError_t h = ens64_raise_lds_limit(reinterpret_cast<const void*>(&ensemble64_step_ragged), raised);
+    static std::atomic<bool> raised[64], raised_sweep[64];
+    const hipError_t h = a.sweep ? ens64_raise_lds_limit(reinterpret_cast<const void*>(&ensemble64_step_ragged<true>), raised_sweep)
+                                 : ens64_raise_lds_limit(reinterpret_cast<const void*>(&ensemble64_step_ragged<false>), raised);
     if (h != hipSuccess) return h;
   }
-  hipLaunchKernelGGL(ensemble64_step_ragged, dim3((unsigned)blocks), dim3(kEnsembleBlock), lds_bytes, s, a, items);
+  if (a.sweep) {
+    hipLaunchKernelGGL(ensemble64_step_ragged<true>, dim3((unsigned)blocks), dim3(kEnsembleBlock), lds_bytes, s, a, items);
+  } else {
+    hipLaunchKernelGGL(ensemble64_step_ragged<false>, dim3((unsigned)blocks), dim3(kEnsembleBlock), lds_bytes, s, a, items);
+  }
   return hipGetLastError();
 }
 

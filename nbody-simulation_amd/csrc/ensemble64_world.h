@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ensemble64_kernels.h"
 #include "ensemble_device.h"
 #include "ensemble_shape.h"
 #include "fast_domain.h"
@@ -73,6 +74,19 @@ __device__ __forceinline__ int ens64_stage_world(const Ens64WorldLds& w, const d
     __syncthreads();
   }
   return hazard;
+}
+
+// Sweeps (nbody_sweep_*): the arguments of a block of world `world` (the same in every lane, so its entry arrives by scalar
+// loads) -> false where the world has taken its steps of this call and the block has nothing to compute; otherwise delta and
+// clamp become the world's own, and so does the route: direct_fast_f64's test on the world's clamp — FAST only with a clamp > 0
+// (a NaN fails it).  The bodies' and the tracers' blocks of a world read the same entry and agree.
+__device__ __forceinline__ bool ens64_sweep_args(Ensemble64Args& a, const unsigned world) {
+  const Ens64SweepWorld sw = a.sweep[__builtin_amdgcn_readfirstlane(world)];  // (says "uniform" to the compiler)
+  if (a.step >= sw.steps) return false;
+  a.delta = sw.delta;
+  a.clamp = sw.clamp;
+  a.fast = a.fast && sw.clamp > 0.0 ? 1 : 0;
+  return true;
 }
 
 // EXACT: one chain of IEEE additions for one target, from zero.  The terms of a block of kEns64TermBlock sources are evaluated

@@ -8,6 +8,9 @@
 //   kWho                           the word that every other message of the handle begins with ("ensemble", "ragged", "restricted", "ragged restricted");
 //   stage(weight, rows, tmp)       -> the rows Mass values to upload (tmp is theirs to fill);
 //   route(args, mass, params)      the masses and the arithmetic of a launch, from the handle's parameters;
+//   SweepWorld, sweep_world(delta, clamp, steps), sweep_route(args, params)
+//                                  sweeps (ens_sweep_with): a world's entry of the kernels' table, and the call-wide arithmetic
+//                                  where every world brings a clamp of its own (params.arith alone: the clamp's test is the kernels');
 //   launch(stream, n_worlds, args) one step, or one force evaluation, of all worlds.
 // A handle is a struct of its own derived from EnsembleState<P>: the C header declares distinct opaque types.
 // The ragged handle (ragged_driver.h: worlds of different sizes, several launches per step) is built from the same parts: the
@@ -19,6 +22,8 @@
 // drivers hand it their row ranges in a FrameRows and nothing else.
 // Delta streams (nbody_deltas_*, ensemble_deltas.h) are ens_deltas below for every handle in the same way: the other drivers hand
 // it their sizes, counts and tracer positions in a DeltaRows.  The state counts its steps (`updates`) for the streams' headers.
+// Sweeps (nbody_sweep_*: a time step, a clamp and a number of steps per world) are ens_sweep_with below for every handle: the
+// other drivers supply the launches of a step, as they do for ens_update_with.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -89,6 +94,11 @@ template <class P> struct EnsembleState {
   // have them (and so with the bodies too: an upload of bodies removes the tracers).
   uint64_t updates = 0;
   DeltaSeq dbodies, dtracers;
+  // sweeps (ens_sweep_with): the table of the worlds' entries of the call in flight, on the host and on the device.  Scratch:
+  // grown on demand, rewritten by every call, nothing of a sweep outlives it.  Freed with the arrays above.
+  std::vector<typename P::SweepWorld> sweep_host;
+  typename P::SweepWorld* sweep_dev = nullptr;
+  size_t sweep_dev_bytes = 0;
 };
 
 template <class P> thread_local std::string g_ens_create_error;  // one per precision: what a failed create left for its thread
@@ -111,6 +121,8 @@ template <class P> void ens_free(EnsembleState<P>* e) {
   free_dev(e->frame_rgba); free_dev(e->frame_work); free_dev(e->frame_table);
   e->frame_rgba_bytes = e->frame_work_bytes = 0;
   e->frame_table_valid = false;
+  free_dev(e->sweep_dev);
+  e->sweep_dev_bytes = 0;
   e->dbodies.release();
   e->dtracers.release();
   e->n_worlds = e->n_bodies = e->rows = 0;
@@ -250,6 +262,8 @@ template <class P> int ens_download(EnsembleState<P>* e, typename P::Real* pos, 
   return NBODY_OK;
 }
 
+template <class P, class B> int ens_frame_buffer(EnsembleState<P>* e, B*& p, size_t& bytes, size_t need);  // (below: a grown device buffer)
+
 // n_steps steps; `launch(args)` enqueues one step (or one force evaluation) of every world on e->stream and returns a hipError_t.
 template <class P, class Launch>
 int ens_update_with(EnsembleState<P>* e, typename P::Real delta, int n_steps, nbody_counting* counter, Launch launch) {
@@ -278,6 +292,56 @@ int ens_update_with(EnsembleState<P>* e, typename P::Real delta, int n_steps, nb
 
 template <class P> int ens_update(EnsembleState<P>* e, typename P::Real delta, int n_steps, nbody_counting* counter) {
   return ens_update_with(e, delta, n_steps, counter, [e](const typename P::Args& a) { return P::launch(e->stream, e->n_worlds, a); });
+}
+
+// A sweep: n_steps steps in which world k steps by delta[k] under clamp[k] (NULL: params.clamp in every world) and takes the
+// first steps[k] of them (NULL: all), then stands still; `launch(args)` as in ens_update_with.  Every refusal comes before
+// anything is allocated or enqueued.  The three arrays are read here, into the table the kernels read: the call keeps nothing.
+// Every launch steps the handle's count and flips the position buffers for all worlds, finished or not: a finished world's
+// blocks carry its positions over (ensemble_kernels.hip, "Sweeps").
+template <class P, class Launch>
+int ens_sweep_with(EnsembleState<P>* e, const typename P::Real* delta, const float* clamp, const int32_t* steps, int n_steps,
+                   nbody_counting* counter, Launch launch) {
+  if (!e) return NBODY_ERR_INVALID;
+  const std::string who = std::string(P::kWho) + " sweep: ";
+  if (!e->n_worlds) return ens_fail(e, NBODY_ERR_INVALID, who + "nothing uploaded");
+  if (!delta) return ens_fail(e, NBODY_ERR_INVALID, who + "delta is NULL");
+  if (n_steps < 0) return ens_fail(e, NBODY_ERR_INVALID, who + "n_steps < 0");
+  if (steps)
+    for (int64_t k = 0; k < e->n_worlds; ++k)
+      if (steps[k] < 0 || steps[k] > n_steps)
+        return ens_fail(e, NBODY_ERR_INVALID, who + "steps[" + std::to_string(k) + "] = " + std::to_string(steps[k]) + " of world " +
+                                                  std::to_string(k) + " is outside 0 .. n_steps = " + std::to_string(n_steps));
+  if (n_steps == 0) return NBODY_OK;
+  ENS_HIPCHK(e, hipSetDevice(e->device));
+  const double t_begin = now_s();
+  const size_t n = (size_t)e->n_worlds, bytes = n * sizeof(typename P::SweepWorld);
+  e->sweep_host.resize(n);  // (the handle's: the copy below may still read it when an error returns early)
+  for (size_t k = 0; k < n; ++k) e->sweep_host[k] = P::sweep_world(delta[k], clamp ? clamp[k] : e->params.clamp, steps ? steps[k] : n_steps);
+  if (int rc = ens_frame_buffer(e, e->sweep_dev, e->sweep_dev_bytes, bytes)) return rc;
+  ENS_HIPCHK(e, hipMemcpyAsync(e->sweep_dev, e->sweep_host.data(), bytes, hipMemcpyHostToDevice, e->stream));
+  for (int step = 0; step < n_steps; ++step) {
+    typename P::Args a = ens_args(e);
+    if (clamp) P::sweep_route(a, e->params);
+    a.pos_out = e->pos[1 - e->cur];
+    a.vel = e->vel;
+    a.sweep = e->sweep_dev;
+    a.step = step;
+    ENS_HIPCHK(e, launch(a));
+    e->cur = 1 - e->cur;
+    ++e->updates;
+  }
+  ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
+  const double dt = now_s() - t_begin;  // booked as an update's seconds are
+  e->counting.sum_gravity += dt;
+  if (counter) counter->sum_gravity += dt;
+  return NBODY_OK;
+}
+
+template <class P>
+int ens_sweep(EnsembleState<P>* e, const typename P::Real* delta, const float* clamp, const int32_t* steps, int n_steps, nbody_counting* counter) {
+  return ens_sweep_with(e, delta, clamp, steps, n_steps, counter,
+                        [e](const typename P::Args& a) { return P::launch(e->stream, e->n_worlds, a); });
 }
 
 template <class P, class Launch> int ens_accel_with(EnsembleState<P>* e, typename P::Real* acc_xy, Launch launch) {

@@ -24,6 +24,9 @@ struct EnsF32 {
     a.clamp = p.clamp;
     a.arith = direct_arith_f32(p.arith, p.clamp);  // a clamp below kFastClampFloor (or NaN): every world EXACT
   }
+  using SweepWorld = EnsSweepWorld;
+  static EnsSweepWorld sweep_world(float delta, float clamp, int32_t steps) { return EnsSweepWorld{delta, clamp, steps, 0}; }
+  static void sweep_route(EnsembleArgs& a, const nbody_params& p) { a.arith = p.arith; }  // (direct_arith_f32's clamp test: per world, in the kernel)
   static hipError_t launch(hipStream_t s, int64_t n_worlds, const EnsembleArgs& a) { return launch_ensemble_step(s, n_worlds, a); }
 };
 

@@ -26,6 +26,9 @@ struct EnsF64 {
     a.clamp = (double)p.clamp;  // the f32 parameter widened, as the f64 context's direct step does
     a.fast = direct_fast_f64(p.arith, a.clamp) ? 1 : 0;  // opt-in, and a clamp that is not > 0 (or NaN): every world EXACT
   }
+  using SweepWorld = Ens64SweepWorld;
+  static Ens64SweepWorld sweep_world(double delta, float clamp, int32_t steps) { return Ens64SweepWorld{delta, (double)clamp, steps, 0}; }
+  static void sweep_route(Ensemble64Args& a, const nbody_params& p) { a.fast = p.arith == NBODY_ARITH_FAST ? 1 : 0; }  // (direct_fast_f64's clamp test: per world, in the kernel)
   static hipError_t launch(hipStream_t s, int64_t n_worlds, const Ensemble64Args& a) { return launch_ensemble64_step(s, n_worlds, a); }
 };
 

@@ -17,6 +17,13 @@
 
 namespace nbody {
 
+// Sweeps (nbody_sweep_*): what a world reads of its own where a call gives every world a time step, a clamp and a number of
+// steps.  One entry per world, 16 bytes, read once per block by scalar loads (the world's index is the same in every lane).
+struct EnsSweepWorld {
+  float delta, clamp;
+  int32_t steps, pad;
+};
+
 struct EnsembleArgs {
   const float2* pos_in = nullptr;  // [n_worlds][n_bodies], read by every block of the world
   const float* mass = nullptr;     // `weight as f32`
@@ -27,9 +34,16 @@ struct EnsembleArgs {
   unsigned tiles = 1;              // blocks per world
   float delta = 0.f, clamp = 0.f;
   int arith = 0;                   // nbody_arith; AUTO decides per world in the kernel
+  // a sweep's launches only (the plain kernels read none of them): every world's entry, the step of the call that this
+  // launch is, and — ragged launches — the world of every work item of this launch
+  const EnsSweepWorld* sweep = nullptr;
+  const uint32_t* item_world = nullptr;
+  int step = 0;
 };
 
-// One step (or, without vel / pos_out, one force evaluation) of all n_worlds worlds on `s`.
+// One step (or, without vel / pos_out, one force evaluation) of all n_worlds worlds on `s`.  With a.sweep the launch is a second
+// instantiation of the same kernel (ensemble_kernels.hip, "Sweeps"): world k takes delta and clamp from its entry, turns EXACT
+// where direct_arith_f32 would turn a handle with that clamp EXACT, and once a.step >= steps it only carries its positions over.
 hipError_t launch_ensemble_step(hipStream_t s, int64_t n_worlds, EnsembleArgs a);
 
 // Ragged ensembles (nbody_ragged_*): worlds of different sizes.  A block is one work item (world, tile) of the table that

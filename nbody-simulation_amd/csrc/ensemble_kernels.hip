@@ -71,29 +71,69 @@ __device__ __forceinline__ void ens_world_tile(const EnsembleArgs& a, const int 
   if (live && part == 0) ens_integrate(a, row0 + t, px[0], py[0], sx, sy);
 }
 
+// Sweeps (nbody_sweep_*): the same block body under the world's own parameters.  The world's entry is read once per block; its
+// index is the same in every lane, so the entry arrives by scalar loads and everything decided from it is decided block-wide:
+//   finished (a.step >= steps)  the positions are double-buffered and the handle flips the buffers once per launch for all
+//                               worlds, so the block carries its own tile of pos_in over to pos_out as raw bits and returns
+//                               before anything is staged and before any barrier.  Velocities are not touched.
+//   route                       the clamp test of direct_arith_f32, taken here on the world's clamp: a world whose clamp is
+//                               below kFastClampFloor (or NaN) is EXACT for the call, in every one of its blocks (and in its
+//                               tracers' blocks, which take the same test on the same entry); its neighbours are not asked.
+//   delta, clamp                replace the launch's in a copy of the arguments: ens_world_tile runs as it is.
+// (ens_sweep_args of ensemble_world.h is the entry's reading, shared with the tracers' kernels.)
+// The plain launches are the SWEEP = false instantiations: they read nothing of this and compile to what they were.
 template <int SPLIT>
+__device__ __forceinline__ void ens_carry_tile(const EnsembleArgs& a, const int n, const size_t row0, const unsigned tile) {
+  constexpr int TPB = kEnsembleBlock / SPLIT;
+  const int t = (int)tile * TPB + (int)threadIdx.x;
+  if ((int)threadIdx.x >= TPB || t >= n) return;
+  const unsigned long long* in = reinterpret_cast<const unsigned long long*>(a.pos_in);
+  unsigned long long* out = reinterpret_cast<unsigned long long*>(a.pos_out);
+  out[row0 + t] = in[row0 + t];
+}
+
+template <int SPLIT, bool SWEEP>
+__device__ __forceinline__ void ens_step_block(const EnsembleArgs& a, const int n, const size_t row0, const unsigned tile, const unsigned world) {
+  if constexpr (SWEEP) {
+    EnsembleArgs b = a;
+    if (!ens_sweep_args(b, world)) {
+      ens_carry_tile<SPLIT>(a, n, row0, tile);
+      return;
+    }
+    ens_world_tile<SPLIT>(b, n, row0, tile);
+  } else {
+    ens_world_tile<SPLIT>(a, n, row0, tile);
+  }
+}
+
+template <int SPLIT, bool SWEEP>
 __global__ __launch_bounds__(kEnsembleBlock) void ensemble_step(const EnsembleArgs a) {
   const int n = a.n_bodies;
   const unsigned world = blockIdx.x / a.tiles, tile = blockIdx.x - world * a.tiles;
-  ens_world_tile<SPLIT>(a, n, (size_t)world * (size_t)n, tile);
+  ens_step_block<SPLIT, SWEEP>(a, n, (size_t)world * (size_t)n, tile, world);
 }
 
 // Ragged: the block's work item {row0, n | tile << 16} is the same in every lane (a scalar load), so the switch on the
 // world's lane split is taken by the whole block — the barrier of the staging and the butterfly of FAST see every thread.
+// Under a sweep the item's world comes from a.item_world, a table beside the items' (their layout has no room for it), by the
+// same kind of load.
+template <bool SWEEP>
 __global__ __launch_bounds__(kEnsembleBlock) void ensemble_step_ragged(const EnsembleArgs a, const uint2* __restrict__ items) {
   const uint2 item = items[blockIdx.x];
   const size_t row0 = (size_t)(unsigned)__builtin_amdgcn_readfirstlane(item.x);
   const unsigned packed = __builtin_amdgcn_readfirstlane(item.y);
   const int n = (int)(packed & 0xffffu);
   const unsigned tile = packed >> 16;
+  unsigned world = 0;
+  if constexpr (SWEEP) world = __builtin_amdgcn_readfirstlane(a.item_world[blockIdx.x]);
   switch (ensemble_split(n)) {
-    case 1: ens_world_tile<1>(a, n, row0, tile); break;
-    case 2: ens_world_tile<2>(a, n, row0, tile); break;
-    case 4: ens_world_tile<4>(a, n, row0, tile); break;
-    case 8: ens_world_tile<8>(a, n, row0, tile); break;
-    case 16: ens_world_tile<16>(a, n, row0, tile); break;
-    case 32: ens_world_tile<32>(a, n, row0, tile); break;
-    default: ens_world_tile<64>(a, n, row0, tile); break;
+    case 1: ens_step_block<1, SWEEP>(a, n, row0, tile, world); break;
+    case 2: ens_step_block<2, SWEEP>(a, n, row0, tile, world); break;
+    case 4: ens_step_block<4, SWEEP>(a, n, row0, tile, world); break;
+    case 8: ens_step_block<8, SWEEP>(a, n, row0, tile, world); break;
+    case 16: ens_step_block<16, SWEEP>(a, n, row0, tile, world); break;
+    case 32: ens_step_block<32, SWEEP>(a, n, row0, tile, world); break;
+    default: ens_step_block<64, SWEEP>(a, n, row0, tile, world); break;
   }
 }
 
@@ -101,12 +141,20 @@ __global__ __launch_bounds__(kEnsembleBlock) void ensemble_step_ragged(const Ens
 
 hipError_t launch_ensemble_step(hipStream_t s, int64_t n_worlds, EnsembleArgs a) {
   if (n_worlds < 1 || a.n_bodies < 1 || a.n_bodies > kEnsembleMaxBodies || n_worlds * a.n_bodies > kEnsembleMaxRows) return hipErrorInvalidValue;
+  if (a.sweep && (!a.pos_out || !a.vel)) return hipErrorInvalidValue;  // (a sweep is a step: a finished world writes pos_out)
   const int split = ensemble_split(a.n_bodies);
   const int tpb = kEnsembleBlock / split;
   a.tiles = (unsigned)((a.n_bodies + tpb - 1) / tpb);
   const dim3 grid((unsigned)(n_worlds * a.tiles));  // <= 2^26 blocks
   const size_t lds = ensemble_lds_bytes(a.n_bodies);
-#define NB_ENS_GO(S) hipLaunchKernelGGL(ensemble_step<S>, grid, dim3(kEnsembleBlock), lds, s, a)
+#define NB_ENS_GO(S)                                                                    \
+  do {                                                                                  \
+    if (a.sweep) {                                                                      \
+      hipLaunchKernelGGL((ensemble_step<S, true>), grid, dim3(kEnsembleBlock), lds, s, a);  \
+    } else {                                                                            \
+      hipLaunchKernelGGL((ensemble_step<S, false>), grid, dim3(kEnsembleBlock), lds, s, a); \
+    }                                                                                   \
+  } while (0)
   switch (split) {
     case 1: NB_ENS_GO(1); break;
     case 2: NB_ENS_GO(2); break;
@@ -122,7 +170,12 @@ hipError_t launch_ensemble_step(hipStream_t s, int64_t n_worlds, EnsembleArgs a)
 
 hipError_t launch_ensemble_step_ragged(hipStream_t s, int64_t blocks, size_t lds_bytes, const uint2* items, EnsembleArgs a) {
   if (blocks < 1 || blocks > kEnsembleMaxRows || !items || lds_bytes > ensemble_lds_bytes(kEnsembleMaxBodies)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(ensemble_step_ragged, dim3((unsigned)blocks), dim3(kEnsembleBlock), lds_bytes, s, a, items);
+  if (a.sweep && (!a.item_world || !a.pos_out || !a.vel)) return hipErrorInvalidValue;
+  if (a.sweep) {
+    hipLaunchKernelGGL(ensemble_step_ragged<true>, dim3((unsigned)blocks), dim3(kEnsembleBlock), lds_bytes, s, a, items);
+  } else {
+    hipLaunchKernelGGL(ensemble_step_ragged<false>, dim3((unsigned)blocks), dim3(kEnsembleBlock), lds_bytes, s, a, items);
+  }
   return hipGetLastError();
 }
 

@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/nbody_hip.h"
+#include "ensemble_kernels.h"
 #include "ensemble_shape.h"
 #include "fast_domain.h"
 #include "pair.h"
@@ -72,6 +74,19 @@ __device__ __forceinline__ int ens_stage_world(const EnsWorldLds& w, const float
     w.massf[s] = m;
   }
   return __syncthreads_or(decide ? bad : 0);
+}
+
+// Sweeps (nbody_sweep_*): the arguments of a block of world `world` (the same in every lane, so its entry arrives by scalar
+// loads) -> false where the world has taken its steps of this call and the block has nothing to compute; otherwise delta and
+// clamp become the world's own, and so does the route: direct_arith_f32's test on the world's clamp — below kFastClampFloor, or
+// NaN, the world is EXACT for the call.  The bodies' and the tracers' blocks of a world read the same entry and agree.
+__device__ __forceinline__ bool ens_sweep_args(EnsembleArgs& a, const unsigned world) {
+  const EnsSweepWorld sw = a.sweep[__builtin_amdgcn_readfirstlane(world)];  // (says "uniform" to the compiler)
+  if (a.step >= sw.steps) return false;
+  a.delta = sw.delta;
+  a.clamp = sw.clamp;
+  if (a.arith != NBODY_ARITH_EXACT && !(sw.clamp >= kFastClampFloor)) a.arith = NBODY_ARITH_EXACT;
+  return true;
 }
 
 // EXACT: one ascending-j chain of pair_as_written<float> per target, from zero.

@@ -50,3 +50,9 @@ NB_API int nbody_ragged_plan(int64_t n_worlds, const int64_t* n_bodies, int32_t*
   // (a refusal is read with nbody_ragged_last_error(NULL))
   return ragged_show_plan<RagF32>(n_worlds, n_bodies, launch_of_world, first_block_of_world, n_launches, lds_bytes_of_launch, blocks_of_launch);
 }
+
+// (a sweep — a time step, a clamp and a number of steps per world, include/nbody_ensemble.h: a prefix of its own)
+NB_API int nbody_sweep_ragged(nbody_ragged* e, const float* delta, const float* clamp, const int32_t* steps, int n_steps,
+                              nbody_counting* counter) {
+  return ragged_sweep<RagF32>(e, delta, clamp, steps, n_steps, counter);
+}

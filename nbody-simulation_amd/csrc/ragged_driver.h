@@ -18,13 +18,16 @@ template <class P> struct RaggedState : EnsembleState<P> {
   RaggedPlan plan;
   int64_t first_item[kRaggedMaxLaunches] = {};
   uint2* items = nullptr;                     // the plan's work items on the device, launch after launch
-  ~RaggedState() { free_dev(items); }         // (ens_destroy has made the device current and drained the stream)
+  uint32_t* item_world = nullptr;             // beside them, the world of every item (a sweep's launches read it)
+  ~RaggedState() { free_dev(items); free_dev(item_world); }  // (ens_destroy has made the device current and drained the stream)
 };
 
 // Every launch of the plan, in order.
 template <class P> hipError_t ragged_launch_all(const RaggedState<P>* e, const typename P::Args& a) {
+  typename P::Args b = a;
   for (int l = 0; l < e->plan.n_launches; ++l) {
-    const hipError_t h = P::launch_items(e->stream, e->plan.blocks[l], (size_t)e->plan.lds_bytes[l], e->items + e->first_item[l], a);
+    b.item_world = e->item_world + e->first_item[l];
+    const hipError_t h = P::launch_items(e->stream, e->plan.blocks[l], (size_t)e->plan.lds_bytes[l], e->items + e->first_item[l], b);
     if (h != hipSuccess) return h;
   }
   return hipSuccess;
@@ -47,16 +50,21 @@ int ragged_upload(RaggedState<P>* e, int64_t n_worlds, const int64_t* n_bodies, 
   if (const int rc = ragged_plan(n_worlds, n_bodies, &plan, nullptr, nullptr, P::lds_bytes)) return ens_fail<P>(e, NBODY_ERR_INVALID, ragged_plan_error(rc));
   if (!pos || !vel) return ens_fail<P>(e, NBODY_ERR_INVALID, "ragged upload: pos_xy or vel_xy is NULL");
   std::vector<RaggedItem> items((size_t)plan.total_blocks);
+  std::vector<uint32_t> item_world(items.size());
   int64_t first_item[kRaggedMaxLaunches];
-  ragged_items(n_worlds, n_bodies, plan, items.data(), first_item);
+  ragged_items(n_worlds, n_bodies, plan, items.data(), first_item, item_world.data());
   if (const int rc = ens_store_rows<P>(e, plan.rows, pos, vel, weight)) return rc;  // (frees the previous arrays first)
   free_dev(e->items);
+  free_dev(e->item_world);
   hipError_t h = hipMalloc((void**)&e->items, items.size() * sizeof(RaggedItem));
+  if (h == hipSuccess) h = hipMalloc((void**)&e->item_world, item_world.size() * sizeof(uint32_t));
   if (h == hipSuccess) h = hipMemcpyAsync(e->items, items.data(), items.size() * sizeof(RaggedItem), hipMemcpyHostToDevice, e->stream);
+  if (h == hipSuccess) h = hipMemcpyAsync(e->item_world, item_world.data(), item_world.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream);
   if (h == hipSuccess) h = hipStreamSynchronize(e->stream);
   if (h != hipSuccess) {
     ens_free<P>(e);
     free_dev(e->items);
+    free_dev(e->item_world);
     return ens_fail_hip<P>(e, h, "upload of the work items");
   }
   e->sizes.assign(n_bodies, n_bodies + n_worlds);
@@ -68,6 +76,10 @@ int ragged_upload(RaggedState<P>* e, int64_t n_worlds, const int64_t* n_bodies, 
 
 template <class P> int ragged_update(RaggedState<P>* e, typename P::Real delta, int n_steps, nbody_counting* counter) {
   return ens_update_with<P>(e, delta, n_steps, counter, [e](const typename P::Args& a) { return ragged_launch_all<P>(e, a); });
+}
+template <class P>
+int ragged_sweep(RaggedState<P>* e, const typename P::Real* delta, const float* clamp, const int32_t* steps, int n_steps, nbody_counting* counter) {
+  return ens_sweep_with<P>(e, delta, clamp, steps, n_steps, counter, [e](const typename P::Args& a) { return ragged_launch_all<P>(e, a); });
 }
 template <class P> int ragged_accel(RaggedState<P>* e, typename P::Real* acc_xy) {
   return ens_accel_with<P>(e, acc_xy, [e](const typename P::Args& a) { return ragged_launch_all<P>(e, a); });

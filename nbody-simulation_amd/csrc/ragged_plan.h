@@ -91,8 +91,10 @@ inline int ragged_plan(int64_t n_worlds, const int64_t* n_bodies, RaggedPlan* pl
 }
 
 // The work items of a valid plan, launch after launch: launch l's items are items[first_item[l] .. first_item[l] + blocks[l]).
-// `items` has plan.total_blocks elements, `first_item` kRaggedMaxLaunches.
-inline void ragged_items(int64_t n_worlds, const int64_t* n_bodies, const RaggedPlan& plan, RaggedItem* items, int64_t* first_item) {
+// `items` has plan.total_blocks elements, `first_item` kRaggedMaxLaunches.  An item's layout has no room for its world: where
+// `world_of_item` is given (plan.total_blocks elements) it receives the world of every item, in the items' order.
+inline void ragged_items(int64_t n_worlds, const int64_t* n_bodies, const RaggedPlan& plan, RaggedItem* items, int64_t* first_item,
+                         uint32_t* world_of_item = nullptr) {
   int64_t next[kRaggedMaxLaunches] = {}, at = 0;
   for (int l = 0; l < kRaggedMaxLaunches; ++l) {
     first_item[l] = next[l] = l < plan.n_launches ? at : 0;
@@ -103,7 +105,10 @@ inline void ragged_items(int64_t n_worlds, const int64_t* n_bodies, const Ragged
     const int n = (int)n_bodies[k];
     const int l = plan.launch_of_class[ragged_class(n)];
     const int tiles = ragged_tiles(n);
-    for (int t = 0; t < tiles; ++t) items[next[l]++] = RaggedItem{(uint32_t)row0, (uint32_t)n | ((uint32_t)t << 16)};
+    for (int t = 0; t < tiles; ++t) {
+      if (world_of_item) world_of_item[next[l]] = (uint32_t)k;
+      items[next[l]++] = RaggedItem{(uint32_t)row0, (uint32_t)n | ((uint32_t)t << 16)};
+    }
     row0 += n;
   }
 }

@@ -47,3 +47,8 @@ NB_API int nbody_deltas_restricted(nbody_restricted* e, uint32_t flags, uint8_t*
                                    uint64_t* step_out) {
   return rst_deltas<RstF32>(e, flags, out, cap, bytes_out, offsets_out, step_out);
 }
+// (a sweep — a time step, a clamp and a number of steps per world, include/nbody_ensemble.h: likewise a prefix of its own)
+NB_API int nbody_sweep_restricted(nbody_restricted* e, const float* delta, const float* clamp, const int32_t* steps, int n_steps,
+                                  nbody_counting* counter) {
+  return rst_sweep<RstF32>(e, delta, clamp, steps, n_steps, counter);
+}

@@ -47,3 +47,8 @@ NB_API int nbody_deltas_restricted64(nbody_restricted64* e, uint32_t flags, uint
                                      uint64_t* offsets_out, uint64_t* step_out) {
   return rst_deltas<Rst64>(e, flags, out, cap, bytes_out, offsets_out, step_out);
 }
+// (a sweep — a time step, a clamp and a number of steps per world, include/nbody_ensemble.h: likewise a prefix of its own)
+NB_API int nbody_sweep_restricted64(nbody_restricted64* e, const double* delta, const float* clamp, const int32_t* steps, int n_steps,
+                                    nbody_counting* counter) {
+  return rst_sweep<Rst64>(e, delta, clamp, steps, n_steps, counter);
+}

@@ -37,6 +37,8 @@ struct Restricted64Args {
 // One step (or, without tvel, one force evaluation) of the tracers of all n_worlds worlds on `s`.  Of `bodies` pos_in, weight,
 // n_bodies, delta, clamp and fast are read: what the bodies' launch of the same step is given.  A launch that cannot be made
 // comes back as hipErrorInvalidValue.
+// With bodies.sweep (a sweep's launch: tvel is required) world k's delta, clamp and route are its entry's, and its blocks return at
+// once when bodies.step >= its steps (ens_sweep_args / ens64_sweep_args).
 hipError_t launch_restricted64_tracers(hipStream_t s, int64_t n_worlds, const Ensemble64Args& bodies, Restricted64Args t);
 
 }  // namespace nbody

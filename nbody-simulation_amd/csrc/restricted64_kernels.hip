@@ -22,10 +22,16 @@
 namespace nbody {
 namespace {
 
-template <int R>
-__global__ __launch_bounds__(kEnsembleBlock) void restricted64_tracers(const Ensemble64Args b, const Restricted64Args t) {
-  const int n = b.n_bodies;
+// SWEEP (nbody_sweep_*): the world's own delta, clamp and route from its entry (ens64_sweep_args); the tracers are updated in place, so
+// the blocks of a world that has taken its steps return at once, before the staging and its barrier.
+template <int R, bool SWEEP>
+__global__ __launch_bounds__(kEnsembleBlock) void restricted64_tracers(const Ensemble64Args b0, const Restricted64Args t) {
   const unsigned world = blockIdx.x / t.tiles, tile = blockIdx.x - world * t.tiles;
+  Ensemble64Args b = b0;
+  if constexpr (SWEEP) {
+    if (!ens64_sweep_args(b, world)) return;
+  }
+  const int n = b.n_bodies;
   constexpr int64_t per_block = (int64_t)kEnsembleBlock * R;
   const int64_t first = (int64_t)tile * per_block;  // the tile's first tracer among its world's
   const int64_t left = t.n_tracers - first;
@@ -46,11 +52,18 @@ hipError_t launch_restricted64_tracers(hipStream_t s, int64_t n_worlds, const En
   const dim3 grid((unsigned)(n_worlds * t.tiles));  // <= 2^26 blocks: n_worlds * n_tracers <= 2^26
   const size_t lds = ensemble64_lds_bytes(bodies.n_bodies);
   if (lds > 65536) {  // its own function, so its own limit: the bodies' kernels' raised ones do not cover it
-    static std::atomic<bool> raised[64];
-    const hipError_t h = ens64_raise_lds_limit(reinterpret_cast<const void*>(&restricted64_tracers<kRestricted64PerLane>), raised);
+    static std::atomic<bool> raised[64], raised_sweep[64];
+    const hipError_t h =
+        bodies.sweep ? ens64_raise_lds_limit(reinterpret_cast<const void*>(&restricted64_tracers<kRestricted64PerLane, true>), raised_sweep)
+                     : ens64_raise_lds_limit(reinterpret_cast<const void*>(&restricted64_tracers<kRestricted64PerLane, false>), raised);
     if (h != hipSuccess) return h;
   }
-  hipLaunchKernelGGL(restricted64_tracers<kRestricted64PerLane>, grid, dim3(kEnsembleBlock), lds, s, bodies, t);
+  if (bodies.sweep) {
+    if (!t.tvel) return hipErrorInvalidValue;  // (a sweep is a step)
+    hipLaunchKernelGGL((restricted64_tracers<kRestricted64PerLane, true>), grid, dim3(kEnsembleBlock), lds, s, bodies, t);
+  } else {
+    hipLaunchKernelGGL((restricted64_tracers<kRestricted64PerLane, false>), grid, dim3(kEnsembleBlock), lds, s, bodies, t);
+  }
   return hipGetLastError();
 }
 

@@ -90,14 +90,23 @@ template <class P> int rst_tracers_download(RestrictedState<P>* e, typename P::R
   return NBODY_OK;
 }
 
+// One step of the bodies and then of the tracers, both given `a`.
+template <class P> hipError_t rst_launch_step(RestrictedState<P>* e, const typename P::Args& a) {
+  hipError_t h = P::launch(e->stream, e->n_worlds, a);
+  if (h != hipSuccess || !e->n_tracers) return h;
+  typename P::Tracers t = rst_tracers(e);
+  t.tvel = e->tvel;
+  return P::launch_tracers(e->stream, e->n_worlds, a, t);  // a.pos_in: what the bodies' launch above reads
+}
+
 template <class P> int rst_update(RestrictedState<P>* e, typename P::Real delta, int n_steps, nbody_counting* counter) {
-  return ens_update_with<P>(e, delta, n_steps, counter, [e](const typename P::Args& a) {
-    hipError_t h = P::launch(e->stream, e->n_worlds, a);
-    if (h != hipSuccess || !e->n_tracers) return h;
-    typename P::Tracers t = rst_tracers(e);
-    t.tvel = e->tvel;
-    return P::launch_tracers(e->stream, e->n_worlds, a, t);  // a.pos_in: what the bodies' launch above reads
-  });
+  return ens_update_with<P>(e, delta, n_steps, counter, [e](const typename P::Args& a) { return rst_launch_step<P>(e, a); });
+}
+
+// A sweep: the tracers of world k follow its delta, clamp and steps (both launches read the same table).
+template <class P>
+int rst_sweep(RestrictedState<P>* e, const typename P::Real* delta, const float* clamp, const int32_t* steps, int n_steps, nbody_counting* counter) {
+  return ens_sweep_with<P>(e, delta, clamp, steps, n_steps, counter, [e](const typename P::Args& a) { return rst_launch_step<P>(e, a); });
 }
 
 template <class P> int rst_accel(RestrictedState<P>* e, typename P::Real* acc_xy) { return ens_accel<P>(e, acc_xy); }

@@ -34,6 +34,8 @@ struct RestrictedArgs {
 
 // One step (or, without tvel, one force evaluation) of the tracers of all n_worlds worlds on `s`.  Of `bodies` pos_in, mass,
 // n_bodies, delta, clamp and arith are read: what the bodies' launch of the same step is given.
+// With bodies.sweep (a sweep's launch: tvel is required) world k's delta, clamp and route are its entry's, and its blocks return at
+// once when bodies.step >= its steps (ens_sweep_args / ens64_sweep_args).
 hipError_t launch_restricted_tracers(hipStream_t s, int64_t n_worlds, const EnsembleArgs& bodies, RestrictedArgs t);
 
 }  // namespace nbody

@@ -22,10 +22,18 @@
 namespace nbody {
 namespace {
 
-template <int R>
-__global__ __launch_bounds__(kEnsembleBlock) void restricted_tracers(const EnsembleArgs b, const RestrictedArgs t) {
-  const int n = b.n_bodies;
+// SWEEP (nbody_sweep_*): the world's own delta, clamp and route from its entry (ens_sweep_args); the tracers are updated in place, so
+// the blocks of a world that has taken its steps return at once, before the staging and its barrier.
+// (Left to itself the sweep's instantiation is scheduled into 100 VGPRs, 4 waves per SIMD, from the same instructions that take 58
+// in the plain one: it is told to stay at 8 waves, and does without scratch.  The plain instantiation's bound is the default.)
+template <int R, bool SWEEP>
+__global__ __launch_bounds__(kEnsembleBlock) __attribute__((amdgpu_waves_per_eu(SWEEP ? 8 : 1))) void restricted_tracers(const EnsembleArgs b0, const RestrictedArgs t) {
   const unsigned world = blockIdx.x / t.tiles, tile = blockIdx.x - world * t.tiles;
+  EnsembleArgs b = b0;
+  if constexpr (SWEEP) {
+    if (!ens_sweep_args(b, world)) return;
+  }
+  const int n = b.n_bodies;
   constexpr int64_t per_block = (int64_t)kEnsembleBlock * R;
   const int64_t first = (int64_t)tile * per_block;  // the tile's first tracer among its world's
   const int64_t left = t.n_tracers - first;
@@ -44,7 +52,12 @@ hipError_t launch_restricted_tracers(hipStream_t s, int64_t n_worlds, const Ense
   constexpr int64_t per_block = (int64_t)kEnsembleBlock * kRestrictedPerLane;
   t.tiles = (unsigned)((t.n_tracers + per_block - 1) / per_block);
   const dim3 grid((unsigned)(n_worlds * t.tiles));  // <= 2^26 blocks: n_worlds * n_tracers <= 2^26
-  hipLaunchKernelGGL(restricted_tracers<kRestrictedPerLane>, grid, dim3(kEnsembleBlock), ensemble_lds_bytes(bodies.n_bodies), s, bodies, t);
+  if (bodies.sweep) {
+    if (!t.tvel) return hipErrorInvalidValue;  // (a sweep is a step)
+    hipLaunchKernelGGL((restricted_tracers<kRestrictedPerLane, true>), grid, dim3(kEnsembleBlock), ensemble_lds_bytes(bodies.n_bodies), s, bodies, t);
+  } else {
+    hipLaunchKernelGGL((restricted_tracers<kRestrictedPerLane, false>), grid, dim3(kEnsembleBlock), ensemble_lds_bytes(bodies.n_bodies), s, bodies, t);
+  }
   return hipGetLastError();
 }
 

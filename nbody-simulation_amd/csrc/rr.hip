@@ -68,3 +68,9 @@ NB_API int nbody_rr_plan(int64_t n_worlds, const int64_t* n_bodies, const int64_
   return rr_show_plan<RrF32>(n_worlds, n_bodies, n_tracers, launch_of_world, first_block_of_world, n_launches, lds_bytes_of_launch,
                              blocks_of_launch);
 }
+
+// (a sweep — a time step, a clamp and a number of steps per world, include/nbody_ensemble.h: a prefix of its own)
+NB_API int nbody_sweep_rr(nbody_rr* e, const float* delta, const float* clamp, const int32_t* steps, int n_steps,
+                          nbody_counting* counter) {
+  return rr_sweep<RrF32>(e, delta, clamp, steps, n_steps, counter);
+}

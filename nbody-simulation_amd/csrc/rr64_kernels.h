@@ -28,6 +28,8 @@ struct Rr64TracerArgs {
 // world among them (above 64 KB this kernel's own dynamic-LDS limit is raised, once per device).  Of `bodies` pos_in, weight,
 // delta, clamp and fast are read: what the bodies' launches of the same step are given.
 // Refused: blocks < 1 or > 2^26, a NULL table or NULL arrays, lds_bytes above ensemble64_lds_bytes(4096).
+// With bodies.sweep (a sweep's launch: tvel is required) world k's delta, clamp and route are its entry's, and its blocks return at
+// once when bodies.step >= its steps (ens_sweep_args / ens64_sweep_args); the world of every item comes from bodies.item_world.
 hipError_t launch_rr64_tracers(hipStream_t s, int64_t blocks, size_t lds_bytes, const uint4* items, const Ensemble64Args& bodies,
                                const Rr64TracerArgs& t);
 

@@ -22,13 +22,14 @@ template <class P> struct RrState : RaggedState<P> {
   RrPlan tplan;
   int64_t tfirst_item[kRaggedMaxLaunches] = {};
   uint4* titems = nullptr;      // the tracers' work items on the device, launch after launch
+  uint32_t* titem_world = nullptr;  // beside them, the world of every item (a sweep's launches read it)
   int64_t tracer_rows = 0;      // 0: no tracers
   typename P::Vec2* tpos = nullptr;
   typename P::Vec2* tvel = nullptr;
   typename P::Vec2* tacc = nullptr;
   ~RrState() { drop_tracers(); }  // (ens_destroy has made the device current and drained the stream)
   void drop_tracers() {
-    free_dev(tpos); free_dev(tvel); free_dev(tacc); free_dev(titems);
+    free_dev(tpos); free_dev(tvel); free_dev(tacc); free_dev(titems); free_dev(titem_world);
     counts.clear();
     tplan = RrPlan();
     tracer_rows = 0;
@@ -58,8 +59,10 @@ inline const char* rr_plan_error(int rc) {
 
 // Every launch of the tracers' plan, in order.
 template <class P> hipError_t rr_launch_tracers(const RrState<P>* e, const typename P::Args& a, const typename P::Tracers& t) {
+  typename P::Args b = a;
   for (int l = 0; l < e->tplan.n_launches; ++l) {
-    const hipError_t h = P::launch_tracer_items(e->stream, e->tplan.blocks[l], (size_t)e->tplan.lds_bytes[l], e->titems + e->tfirst_item[l], a, t);
+    b.item_world = e->titem_world + e->tfirst_item[l];
+    const hipError_t h = P::launch_tracer_items(e->stream, e->tplan.blocks[l], (size_t)e->tplan.lds_bytes[l], e->titems + e->tfirst_item[l], b, t);
     if (h != hipSuccess) return h;
   }
   return hipSuccess;
@@ -91,15 +94,18 @@ int rr_tracers_upload(RrState<P>* e, int64_t n_worlds, const int64_t* n_tracers,
   e->drop_tracers();
   if (plan.tracer_rows == 0) return NBODY_OK;
   std::vector<RrItem> items((size_t)plan.total_blocks);
+  std::vector<uint32_t> item_world(items.size());
   int64_t first_item[kRaggedMaxLaunches];
-  rr_items(n_worlds, e->sizes.data(), n_tracers, plan, items.data(), first_item);
+  rr_items(n_worlds, e->sizes.data(), n_tracers, plan, items.data(), first_item, item_world.data());
   const size_t bytes = (size_t)plan.tracer_rows * sizeof(typename P::Vec2);
   hipError_t h = hipMalloc((void**)&e->tpos, bytes);
   if (h == hipSuccess) h = hipMalloc((void**)&e->tvel, bytes);
   if (h == hipSuccess) h = hipMalloc((void**)&e->titems, items.size() * sizeof(RrItem));
+  if (h == hipSuccess) h = hipMalloc((void**)&e->titem_world, item_world.size() * sizeof(uint32_t));
   if (h == hipSuccess) h = hipMemcpyAsync(e->tpos, pos, bytes, hipMemcpyHostToDevice, e->stream);
   if (h == hipSuccess) h = hipMemcpyAsync(e->tvel, vel, bytes, hipMemcpyHostToDevice, e->stream);
   if (h == hipSuccess) h = hipMemcpyAsync(e->titems, items.data(), items.size() * sizeof(RrItem), hipMemcpyHostToDevice, e->stream);
+  if (h == hipSuccess) h = hipMemcpyAsync(e->titem_world, item_world.data(), item_world.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream);
   if (h == hipSuccess) h = hipStreamSynchronize(e->stream);
   if (h != hipSuccess) {
     e->drop_tracers();
@@ -124,15 +130,24 @@ template <class P> int rr_tracers_download(RrState<P>* e, typename P::Real* pos,
   return NBODY_OK;
 }
 
+// One step: the bodies' launches and then the tracers', all given `a`.
+template <class P> hipError_t rr_launch_step(RrState<P>* e, const typename P::Args& a) {
+  const hipError_t h = ragged_launch_all<P>(e, a);
+  if (h != hipSuccess || !e->tracer_rows) return h;
+  typename P::Tracers t;
+  t.tpos = e->tpos;
+  t.tvel = e->tvel;
+  return rr_launch_tracers<P>(e, a, t);  // a.pos_in: what the bodies' launches above read
+}
+
 template <class P> int rr_update(RrState<P>* e, typename P::Real delta, int n_steps, nbody_counting* counter) {
-  return ens_update_with<P>(e, delta, n_steps, counter, [e](const typename P::Args& a) {
-    const hipError_t h = ragged_launch_all<P>(e, a);
-    if (h != hipSuccess || !e->tracer_rows) return h;
-    typename P::Tracers t;
-    t.tpos = e->tpos;
-    t.tvel = e->tvel;
-    return rr_launch_tracers<P>(e, a, t);  // a.pos_in: what the bodies' launches above read
-  });
+  return ens_update_with<P>(e, delta, n_steps, counter, [e](const typename P::Args& a) { return rr_launch_step<P>(e, a); });
+}
+
+// A sweep: the tracers of world k follow its delta, clamp and steps (every launch reads the same table).
+template <class P>
+int rr_sweep(RrState<P>* e, const typename P::Real* delta, const float* clamp, const int32_t* steps, int n_steps, nbody_counting* counter) {
+  return ens_sweep_with<P>(e, delta, clamp, steps, n_steps, counter, [e](const typename P::Args& a) { return rr_launch_step<P>(e, a); });
 }
 
 template <class P> int rr_accel(RrState<P>* e, typename P::Real* acc_xy) { return ragged_accel<P>(e, acc_xy); }

@@ -26,6 +26,8 @@ struct RrTracerArgs {
 // One launch of the tracers' plan on `s`: `blocks` work items from `items`, `lds_bytes` = ensemble_lds_bytes of the largest world
 // among them.  Of `bodies` pos_in, mass, delta, clamp and arith are read: what the bodies' launches of the same step are given.
 // Refused: blocks < 1 or > 2^26, a NULL table or NULL arrays, lds_bytes above ensemble_lds_bytes(4096).
+// With bodies.sweep (a sweep's launch: tvel is required) world k's delta, clamp and route are its entry's, and its blocks return at
+// once when bodies.step >= its steps (ens_sweep_args / ens64_sweep_args); the world of every item comes from bodies.item_world.
 hipError_t launch_rr_tracers(hipStream_t s, int64_t blocks, size_t lds_bytes, const uint4* items, const EnsembleArgs& bodies,
                              const RrTracerArgs& t);
 

@@ -19,8 +19,14 @@ namespace {
 
 // The block's work item {body_row0, n, tracer_row0, count} is the same in every lane (a scalar load), so n and count are
 // uniform: the barrier of the staging sees every thread.  Dynamic LDS is the launch's; the kernel uses no other.
-template <int R>
-__global__ __launch_bounds__(kEnsembleBlock) void rr_tracers(const EnsembleArgs b, const RrTracerArgs t, const uint4* __restrict__ items) {
+// SWEEP (nbody_sweep_*): the item's world from b0.item_world, a table beside the items' (by the same kind of load), and with it
+// the world's own delta, clamp and route (ens_sweep_args); the blocks of a world that has taken its steps return at once.
+template <int R, bool SWEEP>
+__global__ __launch_bounds__(kEnsembleBlock) void rr_tracers(const EnsembleArgs b0, const RrTracerArgs t, const uint4* __restrict__ items) {
+  EnsembleArgs b = b0;
+  if constexpr (SWEEP) {
+    if (!ens_sweep_args(b, (unsigned)__builtin_amdgcn_readfirstlane(b0.item_world[blockIdx.x]))) return;
+  }
   const uint4 item = items[blockIdx.x];
   const size_t body_row0 = (size_t)(unsigned)__builtin_amdgcn_readfirstlane(item.x);
   const int n = (int)__builtin_amdgcn_readfirstlane(item.y);
@@ -38,7 +44,12 @@ hipError_t launch_rr_tracers(hipStream_t s, int64_t blocks, size_t lds_bytes, co
   if (blocks < 1 || blocks > kEnsembleMaxRows || !items || lds_bytes > ensemble_lds_bytes(kEnsembleMaxBodies) || !t.tpos ||
       !bodies.pos_in || !bodies.mass)
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL(rr_tracers<kRestrictedPerLane>, dim3((unsigned)blocks), dim3(kEnsembleBlock), lds_bytes, s, bodies, t, items);
+  if (bodies.sweep) {
+    if (!bodies.item_world || !t.tvel) return hipErrorInvalidValue;  // (a sweep is a step)
+    hipLaunchKernelGGL((rr_tracers<kRestrictedPerLane, true>), dim3((unsigned)blocks), dim3(kEnsembleBlock), lds_bytes, s, bodies, t, items);
+  } else {
+    hipLaunchKernelGGL((rr_tracers<kRestrictedPerLane, false>), dim3((unsigned)blocks), dim3(kEnsembleBlock), lds_bytes, s, bodies, t, items);
+  }
   return hipGetLastError();
 }
 

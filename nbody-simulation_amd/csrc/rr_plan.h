@@ -89,9 +89,10 @@ inline int rr_plan(int64_t n_worlds, const int64_t* n_bodies, const int64_t* n_t
 }
 
 // The work items of a valid plan, launch after launch: launch l's items are items[first_item[l] .. first_item[l] + blocks[l]).
-// `items` has plan.total_blocks elements, `first_item` kRaggedMaxLaunches.
+// `items` has plan.total_blocks elements, `first_item` kRaggedMaxLaunches; `world_of_item`, where given, receives the world of
+// every item in the items' order, as ragged_items' does.
 inline void rr_items(int64_t n_worlds, const int64_t* n_bodies, const int64_t* n_tracers, const RrPlan& plan, RrItem* items,
-                     int64_t* first_item) {
+                     int64_t* first_item, uint32_t* world_of_item = nullptr) {
   int64_t next[kRaggedMaxLaunches] = {}, at = 0;
   for (int l = 0; l < kRaggedMaxLaunches; ++l) {
     first_item[l] = next[l] = l < plan.n_launches ? at : 0;
@@ -104,6 +105,7 @@ inline void rr_items(int64_t n_worlds, const int64_t* n_bodies, const int64_t* n
       const int l = plan.launch_of_class[ragged_class(n)];
       for (int64_t done = 0; done < m; done += kRrTile) {
         const int64_t count = m - done < kRrTile ? m - done : kRrTile;
+        if (world_of_item) world_of_item[next[l]] = (uint32_t)k;
         items[next[l]++] = RrItem{(uint32_t)body_row0, (uint32_t)n, (uint32_t)(tracer_row0 + done), (uint32_t)count};
       }
     }

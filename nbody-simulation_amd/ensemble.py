@@ -40,6 +40,11 @@ Every class has `deltas()` (nbody_deltas_*) too: one lossless NBD1 delta stream 
 `World` holding that world alone hands out through delta_begin / delta_end — the classes with tracers take `tracers=True` for
 the tracers' sequence — and `DeltasDecoder(n_worlds)` is the receiving side, one `DeltaDecoder` per world.  Snapshots of an
 ensemble are not offered: `particles()` hands the rows out whole.
+
+Every class has `sweep(delta, clamp=None, steps=None)` (nbody_sweep_*): an update in which world k steps by delta[k] under
+clamp[k] and takes steps[k] steps, then stands still bit for bit — a time-step convergence study or a softening sweep in one
+handle.  World k's bits are those of the same class holding world k alone with that clamp, stepped by update(delta[k],
+n_steps=steps[k]).
 """
 from __future__ import annotations
 
@@ -58,6 +63,54 @@ def _streams(handle, tracers, key):
     """handle.deltas(...) cut into one bytes object per world."""
     buf, off, step = handle.deltas(tracers, key)
     return [buf[int(off[k]):int(off[k + 1])].tobytes() for k in range(off.shape[0] - 1)], step
+
+
+def _checked_sweep(who, b, dtype, delta, clamp, steps, n_steps):
+    """The arguments of `sweep` for b worlds -> (delta dtype[b], clamp float32[b] or None, steps int32[b] or None, n_steps),
+    contiguous; ValueError naming `who` and the argument for anything else.  n_steps defaults to max(steps), or 1 without steps."""
+    def per_world(name, a, to):
+        a = np.asarray(a)
+        if a.ndim != 1 or a.shape[0] != b:
+            raise ValueError(f"{who}.sweep: {name} must hold one value per world ({b} worlds), got shape {a.shape}")
+        if a.dtype.kind not in "fiu":
+            raise ValueError(f"{who}.sweep: {name} must be numbers, got {a.dtype}")
+        return a if to is None else np.ascontiguousarray(a, dtype=to)
+    if delta is None:
+        raise ValueError(f"{who}.sweep: delta is required, one time step per world")
+    delta = per_world("delta", delta, dtype)
+    if clamp is not None:
+        clamp = per_world("clamp", clamp, np.float32)
+    if n_steps is not None:
+        if isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer)) or not 0 <= int(n_steps) < 1 << 31:
+            raise ValueError(f"{who}.sweep: n_steps must be an integer 0 .. 2^31 - 1, got {n_steps!r}")
+        n_steps = int(n_steps)
+    if steps is not None:
+        steps = per_world("steps", steps, None)
+        if steps.dtype.kind == "f":
+            if not (np.isfinite(steps).all() and (steps == np.floor(steps)).all()):
+                raise ValueError(f"{who}.sweep: steps must be whole numbers")
+        top = int(steps.max()) if n_steps is None else n_steps
+        if top >= 1 << 31:
+            raise ValueError(f"{who}.sweep: steps must be below 2^31")
+        bad = np.flatnonzero((steps < 0) | (steps > top))
+        if bad.size:
+            k = int(bad[0])
+            raise ValueError(f"{who}.sweep: steps[{k}] = {steps[k]} of world {k} is outside 0 .. n_steps = {top}")
+        steps, n_steps = np.ascontiguousarray(steps, dtype=np.int32), top
+    return delta, clamp, steps, 1 if n_steps is None else n_steps
+
+
+class _Sweep:
+    """`sweep` for every ensemble class: the class keeps `_n_worlds` and `_dtype`, its handle has `sweep`."""
+
+    def sweep(self, delta, clamp=None, steps=None, counter: Counting | None = None, n_steps=None):
+        """An update with a time step, a clamp and a number of steps per world (nbody_sweep_*): delta [B] (required), clamp [B]
+        or None (the constructor's clamp in every world), steps [B] integers or None (every world takes n_steps).  World k takes
+        the first steps[k] of the call's n_steps steps — n_steps defaults to max(steps), or 1 without steps — and then stands
+        still bit for bit; its bits are those of this class holding world k alone with clamp[k], stepped by update(delta[k],
+        n_steps=steps[k]).  The arguments are checked here, with ValueError, before the library is touched."""
+        args = _checked_sweep(type(self).__name__, self._n_worlds, self._dtype, delta, clamp, steps, n_steps)
+        self.h.sweep(*args, counter)
 
 
 def _checked(position, velocity, weight, dtype=np.float32, who=None, other=None):
@@ -98,7 +151,7 @@ def _checked(position, velocity, weight, dtype=np.float32, who=None, other=None)
     return b, n, np.ascontiguousarray(position), np.ascontiguousarray(velocity), weight
 
 
-class _EnsembleBase:
+class _EnsembleBase(_Sweep):
     """What Ensemble, Ensemble64 and the restricted ensembles share; each names its dtype and makes its own kind of handle."""
     _dtype = None
 
@@ -118,6 +171,7 @@ class _EnsembleBase:
 
     def _upload(self, b, n, position, velocity, weight):
         self.h.upload(b, n, position, velocity, weight)
+        self._n_worlds = b
         self._weight = np.ones((b, n), np.uint32) if weight is None else weight.copy()
 
     def upload(self, position, velocity, weight=None):
@@ -344,7 +398,7 @@ def _checked_ragged(positions, velocities, weights, dtype=np.float32, who=None, 
     return np.asarray(sizes, np.int64), position, velocity, weight
 
 
-class _RaggedBase:
+class _RaggedBase(_Sweep):
     """What RaggedEnsemble and RaggedEnsemble64 share; each names its dtype, makes its own kind of handle and has its own
     constructor."""
     _dtype = None
@@ -364,6 +418,7 @@ class _RaggedBase:
 
     def _upload(self, sizes, position, velocity, weight):
         self.h.upload(sizes, position, velocity, weight)
+        self._n_worlds = int(sizes.shape[0])
         self._sizes = sizes
         self._cuts = np.cumsum(sizes)[:-1]
         self._weight = np.ones(int(sizes.sum()), np.uint32) if weight is None else weight.copy()
