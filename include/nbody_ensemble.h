@@ -42,7 +42,8 @@
  *     tracers on this handle (nbody_restricted_* at the end of this file); several devices; asynchronous snapshots and delta streams
  *     on a copy stream (the synchronous streams are nbody_deltas_* and the frames nbody_frames_*, both at the end of this
  *     file); hipGraph replay.  The library reads no environment variable for any of this.  (A time step, a clamp and a number
- *     of steps per world: nbody_sweep_* at the end of this file.)
+ *     of steps per world: nbody_sweep_* at the end of this file.  A record per world of what a study ends in — moments, extent,
+ *     separations: nbody_summary_* at the end of this file.)
  * Arrays are world-major, [n_worlds][n_bodies] rows, pos / vel interleaved x,y; weight may be NULL (all 1); an upload replaces
  * the previous ensemble, whatever its shape. */
 typedef struct nbody_ensemble nbody_ensemble;
@@ -596,5 +597,89 @@ int nbody_sweep_restricted64(nbody_restricted64* e, const double* delta, const f
 int nbody_sweep_rr(nbody_rr* e, const float* delta, const float* clamp, const int32_t* steps, int n_steps, nbody_counting* counter);
 int nbody_sweep_rr64(nbody_rr64* e, const double* delta, const float* clamp, const int32_t* steps, int n_steps,
                      nbody_counting* counter);
+
+/* ---- summaries of an ensemble: per-world moments, extent and separations from one call ---------------------------
+ * What a study over many worlds ends in, for all eight handles above, without a download of all rows and a host loop: a
+ * convergence study wants how far world k is from the finest world, a seed ensemble how fast neighbouring trajectories separate,
+ * a stability map how many tracers of each world are still inside the frame, and anyone watching a long run the centre of mass,
+ * the momentum, the kinetic sum, the extent and whether anything went non-finite.  A segment is one world's bodies or one
+ * world's tracers (NBODY_SUMMARY_TRACERS); its record is a function of its own rows — and, for the separation, of the rows of
+ * the world ref[k] names — bit for bit, whatever the number of worlds, the world's index or the other worlds hold.
+ *   The prefix.  nbody_summary_<handle>, and nbody_summary_of_f32 / _of_f64: the names under each handle's own prefix, under
+ *     nbody_frames_, nbody_deltas_ and nbody_sweep_ are closed sets, so these ten have a prefix of their own.
+ *   Arithmetic.  Everything is double on all eight handles.  A row's x, y, vx, vy are widened to double (exact).  w is the
+ *     double of what the handle holds: `weight as f32` on the f32 handles, the u32 weight on the f64 handles, 1 for a tracer.
+ *     Every *, + and - written below is one IEEE double operation in the written grouping; nothing is fused.
+ *   counted.  The rows whose x, y, vx, vy are all finite; only these enter the fields from mass to sum_wv2.
+ *   mass.  The sum of w over counted rows: integers of at most 2^32 over at most 2^26 rows, exact, hence order-free.
+ *   min_x, min_y, max_x, max_y, max_speed2.  Over counted rows, ordered by value with -0.0 below +0.0, hence order-free;
+ *     max_speed2 is the largest vx*vx + vy*vy.  With counted == 0 the minima are +inf, the maxima -inf and max_speed2 +0.0.
+ *   in_bounds.  The rows with y < H && x < H && y >= 0 && x >= 0 for H = height (within_bounds, main.rs:224-226), by position
+ *     alone, counted or not: the rows draw() and nbody_frames_* would paint.  height == 0 gives 0.
+ *   sum_wx, sum_wy, sum_wvx, sum_wvy, sum_wv2.  The sums over counted rows of w*x, w*y, w*vx, w*vy and w*(vx*vx + vy*vy): centre
+ *     of mass = (sum_wx, sum_wy) / mass, momentum, twice the kinetic sum.
+ *   Separation.  ref[k] = j >= 0 names a world of the same handle with the same number of rows in the addressed segment (ref[k]
+ *     == k is allowed).  Every row r counted in both worlds gives dx = x_k - x_j, dy = y_k - y_j, d2 = dx*dx + dy*dy; sep_rows
+ *     counts these rows, sep_max2 is the largest d2 and sep_sum2 their sum, d2 in row r's slot of the order below.  ref == NULL
+ *     or ref[k] == -1 gives 0, +0.0 and +0.0.
+ *   The order of the six sums (sum_wx .. sum_wv2, sep_sum2).  A function of the row index alone.  A segment is cut into chunks
+ *     of 4096 rows.  In chunk c, chain l (0 <= l < 256) starts at +0.0 and adds the terms of rows 4096 c + l + 256 i for i = 0 ..
+ *     15 ascending; a row past the end, or one that does not contribute, adds nothing.  Then for s = 128, 64, .., 1: P[l] = P[l] +
+ *     P[l + s] for l < s, and the chunk's value is P[0].  The segment's value is chunk 0's value plus chunk 1's and so on,
+ *     ascending.  Bodies are always one chunk.  A sum that overflows and turns into NaN is a NaN; its sign and payload are not
+ *     promised (an x86 host and the device make different default NaNs).
+ *   Calls.  Synchronous, on the handle's stream.  They read the current rows and write nothing of the state: stepping with
+ *     summaries in between gives the bits of stepping alone.  One launch for the bodies; for the tracers one, and a second
+ *     where a world has more than 4096 of them, whatever the number of worlds; no floating-point atomics; nothing is read
+ *     back before the end.  The device scratch belongs to the handle,
+ *     is grown on demand and is freed with its other arrays.  out: host memory, one record per world.
+ *   Tracers.  NBODY_SUMMARY_TRACERS on a restricted handle that holds no tracers gives records with rows == 0 (counts 0, mass
+ *     and sums +0.0, minima +inf, maxima -inf), as does a world of an nbody_rr handle without tracers.
+ *   nbody_summary_of_f32 / _of_f64.  Pure host code, no device, no handle: one segment's record by the contract above — the CPU
+ *     statement of it, the same bits.  weight NULL: every w is 1; for f32, w is `(double)(float)weight`.  ref_pos_xy NULL: no
+ *     separation; with it ref_vel_xy is required (it says which reference rows are counted).  They refuse rows < 0, out NULL,
+ *     NULL arrays with rows > 0, and a ref_pos_xy without a ref_vel_xy, with NBODY_ERR_INVALID and no message.
+ *   Refusals.  NBODY_ERR_INVALID before anything is allocated or launched, the message beginning with the handle's word
+ *     ("ensemble", "ragged", "restricted", "ragged restricted") and naming "summary": nothing uploaded; out NULL; unknown flag
+ *     bits; NBODY_SUMMARY_TRACERS on one of the four handles that have no tracer calls; height > 2^24; a ref[k] outside
+ *     [-1, n_worlds) (the message names the world); on the ragged handles a ref[k] whose segment has another number of rows
+ *     than world k's (the message names the world).  A NULL handle gives NBODY_ERR_INVALID without a message.
+ *   Not offered: a velocity or phase-space separation; a potential energy (the reference's pair law, main.rs:234-253, is not the
+ *     gradient of the Newtonian potential, so there is no energy this step conserves); a device-pointer variant; anything for
+ *     nbody_ctx contexts. */
+typedef struct nbody_world_summary { /* 17 fields of 8 bytes, no padding: 136 bytes */
+  int64_t rows;      /* rows of the segment: the world's bodies, or its tracers */
+  int64_t counted;   /* rows whose x, y, vx, vy are all finite; only these enter the fields from mass to sum_wv2 */
+  int64_t in_bounds; /* rows whose position passes within_bounds (main.rs:224-226) under `height`, by position alone */
+  int64_t sep_rows;  /* rows counted both here and in the reference world */
+  double mass;       /* sum of w over counted rows */
+  double min_x, min_y, max_x, max_y; /* over counted rows */
+  double max_speed2; /* max over counted rows of vx*vx + vy*vy */
+  double sum_wx, sum_wy;   /* centre of mass = these / mass */
+  double sum_wvx, sum_wvy; /* momentum */
+  double sum_wv2;    /* sum of w*(vx*vx + vy*vy): twice the kinetic sum */
+  double sep_max2, sep_sum2; /* max and sum of squared distances to the reference world's rows */
+} nbody_world_summary;
+#define NBODY_SUMMARY_TRACERS 1u /* the tracers' segment, not the bodies' */
+int nbody_summary_ensemble(nbody_ensemble* e, uint32_t flags, uint32_t height, const int32_t* ref /*[n_worlds] or NULL*/,
+                           nbody_world_summary* out /*[n_worlds]*/);
+int nbody_summary_ensemble64(nbody_ensemble64* e, uint32_t flags, uint32_t height, const int32_t* ref /*[n_worlds] or NULL*/,
+                             nbody_world_summary* out /*[n_worlds]*/);
+int nbody_summary_ragged(nbody_ragged* e, uint32_t flags, uint32_t height, const int32_t* ref /*[n_worlds] or NULL*/,
+                         nbody_world_summary* out /*[n_worlds]*/);
+int nbody_summary_ragged64(nbody_ragged64* e, uint32_t flags, uint32_t height, const int32_t* ref /*[n_worlds] or NULL*/,
+                           nbody_world_summary* out /*[n_worlds]*/);
+int nbody_summary_restricted(nbody_restricted* e, uint32_t flags, uint32_t height, const int32_t* ref /*[n_worlds] or NULL*/,
+                             nbody_world_summary* out /*[n_worlds]*/);
+int nbody_summary_restricted64(nbody_restricted64* e, uint32_t flags, uint32_t height, const int32_t* ref /*[n_worlds] or NULL*/,
+                               nbody_world_summary* out /*[n_worlds]*/);
+int nbody_summary_rr(nbody_rr* e, uint32_t flags, uint32_t height, const int32_t* ref /*[n_worlds] or NULL*/,
+                     nbody_world_summary* out /*[n_worlds]*/);
+int nbody_summary_rr64(nbody_rr64* e, uint32_t flags, uint32_t height, const int32_t* ref /*[n_worlds] or NULL*/,
+                       nbody_world_summary* out /*[n_worlds]*/);
+int nbody_summary_of_f32(int64_t rows, const float* pos_xy, const float* vel_xy, const uint32_t* weight /*NULL: all 1*/,
+                         const float* ref_pos_xy /*NULL: none*/, const float* ref_vel_xy, uint32_t height, nbody_world_summary* out);
+int nbody_summary_of_f64(int64_t rows, const double* pos_xy, const double* vel_xy, const uint32_t* weight /*NULL: all 1*/,
+                         const double* ref_pos_xy /*NULL: none*/, const double* ref_vel_xy, uint32_t height, nbody_world_summary* out);
 
 #endif /* NBODY_ENSEMBLE_H */

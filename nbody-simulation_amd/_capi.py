@@ -19,6 +19,11 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "nbody_hip.h")
 
 ABI_VERSION = 3   # NBODY_ABI_VERSION of include/nbody_hip.h (tests/test_capi_host.py checks the two agree)
 DELTAS_TRACERS, DELTAS_KEY = 1, 2   # NBODY_DELTAS_* of include/nbody_ensemble.h: the flags of nbody_deltas_<handle>
+SUMMARY_TRACERS = 1                 # NBODY_SUMMARY_TRACERS: the flag of nbody_summary_<handle>
+# nbody_world_summary of include/nbody_ensemble.h: 17 fields of 8 bytes, no padding
+SUMMARY_DTYPE = np.dtype([(name, np.int64) for name in ("rows", "counted", "in_bounds", "sep_rows")] +
+                         [(name, np.float64) for name in ("mass", "min_x", "min_y", "max_x", "max_y", "max_speed2", "sum_wx", "sum_wy",
+                                                          "sum_wvx", "sum_wvy", "sum_wv2", "sep_max2", "sep_sum2")])
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_DEGENERATE, ERR_NOMEM = 0, -1, -2, -3, -4, -5
 ARITH_AUTO, ARITH_FAST, ARITH_EXACT = 0, 1, 2
 ORDER_AS_WRITTEN, ORDER_CONSISTENT = 0, 1
@@ -216,6 +221,11 @@ _SIGS = {
     **{"nbody_sweep_" + h: (C.c_int, [_vp, C.POINTER(_f64 if h.endswith("64") else _f32), C.POINTER(_f32), C.POINTER(C.c_int32), _i32,
                                       C.POINTER(Counting)])
        for h in ("ensemble", "ensemble64", "ragged", "ragged64", "restricted", "restricted64", "rr", "rr64")},
+    # nbody_summary_<handle>: flags, height, ref int32[n_worlds] or NULL, out nbody_world_summary[n_worlds] (SUMMARY_DTYPE)
+    **{"nbody_summary_" + h: (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), _vp])
+       for h in ("ensemble", "ensemble64", "ragged", "ragged64", "restricted", "restricted64", "rr", "rr64")},
+    "nbody_summary_of_f32": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp]),
+    "nbody_summary_of_f64": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp]),
     "nbody_accel_tree_f32": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_accel_tree_f64": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_tree_info": (C.c_int, [_vp, C.POINTER(TreeView)]),
@@ -1015,6 +1025,15 @@ class _EnsembleHandleBase:
         name = "nbody_frames_" + self._prefix[len("nbody_"):]
         args = (height, render_px, 1 if tracers else 0) if self._frames_tracers else (height, render_px)
         self._check(getattr(self.lib, name)(self.h, *args, _ptr(out)))
+        return out
+
+    def summary(self, height, ref, tracers=False):
+        """nbody_summary_<handle>: one record per world of the current rows (tracers=True: of the tracers' segments) ->
+        SUMMARY_DTYPE[worlds].  ref: int32[worlds], contiguous, or None (ensemble.py's `summary` checks and casts it)."""
+        out = np.zeros(self.shape[0], SUMMARY_DTYPE)
+        name = "nbody_summary_" + self._prefix[len("nbody_"):]
+        self._check(getattr(self.lib, name)(self.h, SUMMARY_TRACERS if tracers else 0, int(height),
+                                            None if ref is None else ref.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(out)))
         return out
 
     def _delta_rows(self, tracers):

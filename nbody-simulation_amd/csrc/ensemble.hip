@@ -36,3 +36,7 @@ NB_API int nbody_sweep_ensemble(nbody_ensemble* e, const float* delta, const flo
                                 nbody_counting* counter) {
   return ens_sweep<EnsF32>(e, delta, clamp, steps, n_steps, counter);
 }
+// (a record per world — moments, extent, separations, ensemble_summary.h: likewise a prefix of its own)
+NB_API int nbody_summary_ensemble(nbody_ensemble* e, uint32_t flags, uint32_t height, const int32_t* ref, nbody_world_summary* out) {
+  return ens_summary<EnsF32>(e, flags, height, ref, out);
+}

@@ -24,6 +24,8 @@
 // it their sizes, counts and tracer positions in a DeltaRows.  The state counts its steps (`updates`) for the streams' headers.
 // Sweeps (nbody_sweep_*: a time step, a clamp and a number of steps per world) are ens_sweep_with below for every handle: the
 // other drivers supply the launches of a step, as they do for ens_update_with.
+// Summaries (nbody_summary_*, ensemble_summary.h) are ens_summary below for every handle: the other drivers hand it their sizes,
+// counts and tracer arrays in a SummaryRows; a ragged handle's row ranges are the frames' table.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -36,6 +38,7 @@
 #include "ensemble_deltas.h"
 #include "ensemble_frames.h"
 #include "ensemble_kernels.h"
+#include "ensemble_summary.h"
 
 namespace nbody {
 
@@ -99,6 +102,15 @@ template <class P> struct EnsembleState {
   std::vector<typename P::SweepWorld> sweep_host;
   typename P::SweepWorld* sweep_dev = nullptr;
   size_t sweep_dev_bytes = 0;
+  // summaries (ens_summary): the records, the chunk records of segments of several chunks and the call's ref[], all device
+  // scratch grown on demand; beside the frames' table (and valid with it) the first chunk of every world's tracers, for a ragged
+  // handle.  Freed with the arrays above.
+  nbody_world_summary* summary_out = nullptr;
+  nbody_world_summary* summary_chunks = nullptr;
+  int32_t* summary_ref = nullptr;
+  size_t summary_out_bytes = 0, summary_chunks_bytes = 0, summary_ref_bytes = 0;
+  uint32_t* summary_chunk_base = nullptr;
+  int64_t summary_tracer_chunks = 0;
 };
 
 template <class P> thread_local std::string g_ens_create_error;  // one per precision: what a failed create left for its thread
@@ -123,6 +135,9 @@ template <class P> void ens_free(EnsembleState<P>* e) {
   e->frame_table_valid = false;
   free_dev(e->sweep_dev);
   e->sweep_dev_bytes = 0;
+  free_dev(e->summary_out); free_dev(e->summary_chunks); free_dev(e->summary_ref); free_dev(e->summary_chunk_base);
+  e->summary_out_bytes = e->summary_chunks_bytes = e->summary_ref_bytes = 0;
+  e->summary_tracer_chunks = 0;
   e->dbodies.release();
   e->dtracers.release();
   e->n_worlds = e->n_bodies = e->rows = 0;
@@ -383,6 +398,34 @@ template <class P, class B> int ens_frame_buffer(EnsembleState<P>* e, B*& p, siz
   return NBODY_OK;
 }
 
+// A ragged handle's table of row ranges on the device (sizes: the bodies per world; counts: the tracers per world, or NULL: none),
+// uploaded by the first frames or summary call after an upload of bodies or tracers.  Beside it, for the summaries, the first
+// chunk of every world's tracers among the chunks of all worlds' tracers, and their total.
+template <class P> int ens_frame_table(EnsembleState<P>* e, const int64_t* sizes, const int64_t* counts) {
+  if (e->frame_table_valid) return NBODY_OK;
+  const size_t n = (size_t)e->n_worlds;
+  std::vector<FrameWorld> table(n);
+  std::vector<uint32_t> chunk_base(n + 1);
+  int64_t row0 = 0, trow0 = 0, chunk0 = 0;
+  for (size_t k = 0; k < n; ++k) {
+    const int64_t m = counts ? counts[k] : 0;
+    table[k] = FrameWorld{(uint32_t)row0, (uint32_t)sizes[k], (uint32_t)trow0, (uint32_t)m};  // (each sum <= 2^26)
+    chunk_base[k] = (uint32_t)chunk0;                                                          // (<= 2^26 worlds + 2^14 full chunks)
+    row0 += sizes[k];
+    trow0 += m;
+    chunk0 += summary_chunks((uint32_t)m);
+  }
+  chunk_base[n] = (uint32_t)chunk0;
+  if (!e->frame_table) ENS_HIPCHK(e, hipMalloc((void**)&e->frame_table, n * sizeof(FrameWorld)));
+  if (!e->summary_chunk_base) ENS_HIPCHK(e, hipMalloc((void**)&e->summary_chunk_base, (n + 1) * sizeof(uint32_t)));
+  ENS_HIPCHK(e, hipMemcpyAsync(e->frame_table, table.data(), n * sizeof(FrameWorld), hipMemcpyHostToDevice, e->stream));
+  ENS_HIPCHK(e, hipMemcpyAsync(e->summary_chunk_base, chunk_base.data(), (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+  ENS_HIPCHK(e, hipStreamSynchronize(e->stream));  // (the vectors go out of scope)
+  e->summary_tracer_chunks = chunk0;
+  e->frame_table_valid = true;
+  return NBODY_OK;
+}
+
 // rgba_out: [n_worlds][render_px][render_px][4] bytes.  Synchronous, on the handle's stream; reads pos[cur], writes no state.
 // Every refusal comes before anything is allocated or launched.
 template <class P>
@@ -411,20 +454,8 @@ int ens_frames(EnsembleState<P>* e, uint32_t height, uint32_t render_px, uint8_t
   if (int rc = ens_frame_buffer(e, e->frame_rgba, e->frame_rgba_bytes, (size_t)(e->n_worlds * npix) * 4)) return rc;
   if (!lds)
     if (int rc = ens_frame_buffer(e, e->frame_work, e->frame_work_bytes, (size_t)(e->n_worlds * npix) * 2 * sizeof(uint32_t))) return rc;
-  if (rows.sizes && !e->frame_table_valid) {
-    std::vector<FrameWorld> table((size_t)e->n_worlds);
-    int64_t row0 = 0, trow0 = 0;
-    for (int64_t k = 0; k < e->n_worlds; ++k) {
-      const int64_t m = rows.counts ? rows.counts[k] : 0;
-      table[(size_t)k] = FrameWorld{(uint32_t)row0, (uint32_t)rows.sizes[k], (uint32_t)trow0, (uint32_t)m};  // (each sum <= 2^26)
-      row0 += rows.sizes[k];
-      trow0 += m;
-    }
-    if (!e->frame_table) ENS_HIPCHK(e, hipMalloc((void**)&e->frame_table, table.size() * sizeof(FrameWorld)));
-    ENS_HIPCHK(e, hipMemcpyAsync(e->frame_table, table.data(), table.size() * sizeof(FrameWorld), hipMemcpyHostToDevice, e->stream));
-    ENS_HIPCHK(e, hipStreamSynchronize(e->stream));  // (`table` goes out of scope)
-    e->frame_table_valid = true;
-  }
+  if (rows.sizes)
+    if (int rc = ens_frame_table(e, rows.sizes, rows.counts)) return rc;
   FrameArgs a;
   a.pos = e->pos[e->cur];
   a.vel = e->vel;
@@ -571,6 +602,79 @@ int ens_deltas(EnsembleState<P>* e, uint32_t flags, uint8_t* out, size_t cap, si
   if (step_out) *step_out = e->updates;
   q.cur = (q.cur + 1) % 3;  // the oldest keys are overwritten next time
   q.have = a.have < 2 ? a.have + 1 : 2;
+  return NBODY_OK;
+}
+
+// ---- summaries: one nbody_world_summary per world (ensemble_summary.h) of the current rows, into host memory
+// What a handle tells ens_summary about its rows, beyond the bodies of worlds of one size.
+template <class P> struct SummaryRows {
+  const int64_t* sizes = nullptr;         // worlds of different sizes: the bodies per world; NULL: e->n_bodies in every world
+  const int64_t* counts = nullptr;        // with sizes: the tracers per world, or NULL: none
+  int64_t n_tracers = 0;                  // without sizes: the tracers per world
+  const typename P::Vec2* tpos = nullptr; // the tracers (NULL where the handle holds none)
+  const typename P::Vec2* tvel = nullptr;
+  bool tracer_calls = false;              // the handle has tracer calls at all: NBODY_SUMMARY_TRACERS is its to ask
+};
+
+// out: [n_worlds] records.  Synchronous, on the handle's stream; reads pos[cur], vel, the masses or the tracers, writes no state.
+// Every refusal comes before anything is allocated or launched.  One launch for the bodies, two for the tracers where a world
+// has more than 4096 of them; the only loops over worlds are the check of ref[] and, once per upload, a ragged handle's table.
+template <class P>
+int ens_summary(EnsembleState<P>* e, uint32_t flags, uint32_t height, const int32_t* ref, nbody_world_summary* out,
+                const SummaryRows<P>& rows = SummaryRows<P>()) {
+  if (!e) return NBODY_ERR_INVALID;
+  const std::string who = std::string(P::kWho) + " summary: ";
+  if (!e->n_worlds) return ens_fail(e, NBODY_ERR_INVALID, who + "nothing uploaded");
+  if (!out) return ens_fail(e, NBODY_ERR_INVALID, who + "out is NULL");
+  if (flags & ~NBODY_SUMMARY_TRACERS) return ens_fail(e, NBODY_ERR_INVALID, who + "unknown flag bits");
+  const bool tracers = (flags & NBODY_SUMMARY_TRACERS) != 0;
+  if (tracers && !rows.tracer_calls) return ens_fail(e, NBODY_ERR_INVALID, who + "NBODY_SUMMARY_TRACERS on a handle without tracers");
+  if (height > kSummaryMaxHeight) return ens_fail(e, NBODY_ERR_INVALID, who + "height must be <= 2^24");
+  const auto seg_rows = [&](int64_t k) { return tracers ? (rows.counts ? rows.counts[k] : 0) : rows.sizes[k]; };  // (ragged handles)
+  if (ref)
+    for (int64_t k = 0; k < e->n_worlds; ++k) {
+      const int64_t j = ref[k];
+      if (j >= -1 && j < e->n_worlds && !(rows.sizes && j >= 0 && seg_rows(j) != seg_rows(k))) continue;
+      const std::string which = "ref[" + std::to_string(k) + "] = " + std::to_string(j) + " of world " + std::to_string(k);
+      if (j < -1 || j >= e->n_worlds)
+        return ens_fail(e, NBODY_ERR_INVALID, who + which + " is outside -1 .. n_worlds - 1 = " + std::to_string(e->n_worlds - 1));
+      return ens_fail(e, NBODY_ERR_INVALID, who + which + " names a world of " + std::to_string(seg_rows(j)) + " rows, world " +
+                                                  std::to_string(k) + " has " + std::to_string(seg_rows(k)));
+    }
+
+  ENS_HIPCHK(e, hipSetDevice(e->device));
+  const size_t n = (size_t)e->n_worlds;
+  int64_t n_chunks = e->n_worlds;
+  if (rows.sizes) {
+    if (int rc = ens_frame_table(e, rows.sizes, rows.counts)) return rc;
+    if (tracers) n_chunks = e->summary_tracer_chunks;
+  } else {
+    n_chunks = e->n_worlds * (int64_t)summary_chunks((uint32_t)(tracers ? rows.n_tracers : e->n_bodies));
+  }
+  if (int rc = ens_frame_buffer(e, e->summary_out, e->summary_out_bytes, n * sizeof(nbody_world_summary))) return rc;
+  if (n_chunks > e->n_worlds)
+    if (int rc = ens_frame_buffer(e, e->summary_chunks, e->summary_chunks_bytes, (size_t)n_chunks * sizeof(nbody_world_summary))) return rc;
+  if (ref) {
+    if (int rc = ens_frame_buffer(e, e->summary_ref, e->summary_ref_bytes, n * sizeof(int32_t))) return rc;
+    ENS_HIPCHK(e, hipMemcpyAsync(e->summary_ref, ref, n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+  }
+  SummaryArgs a;
+  a.pos = e->pos[e->cur];
+  a.vel = e->vel;
+  a.mass = e->mass;
+  a.tpos = rows.tpos;
+  a.tvel = rows.tvel;
+  a.table = rows.sizes ? e->frame_table : nullptr;
+  a.chunk_base = rows.sizes ? e->summary_chunk_base : nullptr;
+  a.ref = ref ? e->summary_ref : nullptr;
+  a.n_bodies = (uint32_t)e->n_bodies;
+  a.n_tracers = (uint32_t)rows.n_tracers;
+  a.n_worlds = (uint32_t)e->n_worlds;
+  a.height = height;
+  a.tracers = tracers ? 1u : 0u;
+  ENS_HIPCHK(e, launch_ensemble_summary<typename P::Real>(e->stream, a, n_chunks, e->summary_chunks, e->summary_out));
+  ENS_HIPCHK(e, hipMemcpyAsync(out, e->summary_out, n * sizeof(nbody_world_summary), hipMemcpyDeviceToHost, e->stream));
+  ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
   return NBODY_OK;
 }
 

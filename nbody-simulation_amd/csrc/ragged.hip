@@ -56,3 +56,7 @@ NB_API int nbody_sweep_ragged(nbody_ragged* e, const float* delta, const float* 
                               nbody_counting* counter) {
   return ragged_sweep<RagF32>(e, delta, clamp, steps, n_steps, counter);
 }
+// (a record per world — moments, extent, separations, ensemble_summary.h: likewise a prefix of its own)
+NB_API int nbody_summary_ragged(nbody_ragged* e, uint32_t flags, uint32_t height, const int32_t* ref, nbody_world_summary* out) {
+  return ragged_summary<RagF32>(e, flags, height, ref, out);
+}

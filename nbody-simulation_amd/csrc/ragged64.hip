@@ -53,3 +53,7 @@ NB_API int nbody_sweep_ragged64(nbody_ragged64* e, const double* delta, const fl
                                 nbody_counting* counter) {
   return ragged_sweep<RagF64>(e, delta, clamp, steps, n_steps, counter);
 }
+// (a record per world — moments, extent, separations, ensemble_summary.h: likewise a prefix of its own)
+NB_API int nbody_summary_ragged64(nbody_ragged64* e, uint32_t flags, uint32_t height, const int32_t* ref, nbody_world_summary* out) {
+  return ragged_summary<RagF64>(e, flags, height, ref, out);
+}

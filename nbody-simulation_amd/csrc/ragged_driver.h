@@ -102,6 +102,14 @@ int ragged_deltas(RaggedState<P>* e, uint32_t flags, uint8_t* out, size_t cap, s
   return ens_deltas<P>(e, flags, out, cap, bytes_out, offsets_out, step_out, rows);
 }
 
+// Summaries: the ensemble's, over segments of these sizes.
+template <class P> int ragged_summary(RaggedState<P>* e, uint32_t flags, uint32_t height, const int32_t* ref, nbody_world_summary* out) {
+  if (!e) return NBODY_ERR_INVALID;
+  SummaryRows<P> rows;
+  rows.sizes = e->sizes.data();
+  return ens_summary<P>(e, flags, height, ref, out, rows);
+}
+
 template <class P> int ragged_sizes(const RaggedState<P>* e, int64_t* n_bodies_out) {
   if (!e || !n_bodies_out) return NBODY_ERR_INVALID;
   for (int64_t k = 0; k < e->n_worlds; ++k) n_bodies_out[k] = e->sizes[(size_t)k];

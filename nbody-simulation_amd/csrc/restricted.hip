@@ -52,3 +52,7 @@ NB_API int nbody_sweep_restricted(nbody_restricted* e, const float* delta, const
                                   nbody_counting* counter) {
   return rst_sweep<RstF32>(e, delta, clamp, steps, n_steps, counter);
 }
+// (a record per world — moments, extent, separations, ensemble_summary.h: likewise a prefix of its own)
+NB_API int nbody_summary_restricted(nbody_restricted* e, uint32_t flags, uint32_t height, const int32_t* ref, nbody_world_summary* out) {
+  return rst_summary<RstF32>(e, flags, height, ref, out);
+}

@@ -52,3 +52,7 @@ NB_API int nbody_sweep_restricted64(nbody_restricted64* e, const double* delta, 
                                     nbody_counting* counter) {
   return rst_sweep<Rst64>(e, delta, clamp, steps, n_steps, counter);
 }
+// (a record per world — moments, extent, separations, ensemble_summary.h: likewise a prefix of its own)
+NB_API int nbody_summary_restricted64(nbody_restricted64* e, uint32_t flags, uint32_t height, const int32_t* ref, nbody_world_summary* out) {
+  return rst_summary<Rst64>(e, flags, height, ref, out);
+}

@@ -150,6 +150,17 @@ int rst_deltas(RestrictedState<P>* e, uint32_t flags, uint8_t* out, size_t cap, 
   return ens_deltas<P>(e, flags, out, cap, bytes_out, offsets_out, step_out, rows);
 }
 
+// Summaries: the ensemble's, of the bodies or of the tracers (without tracers: every world's record has rows == 0).
+template <class P> int rst_summary(RestrictedState<P>* e, uint32_t flags, uint32_t height, const int32_t* ref, nbody_world_summary* out) {
+  if (!e) return NBODY_ERR_INVALID;
+  SummaryRows<P> rows;
+  rows.n_tracers = e->n_tracers;
+  rows.tpos = e->tpos;
+  rows.tvel = e->tvel;
+  rows.tracer_calls = true;
+  return ens_summary<P>(e, flags, height, ref, out, rows);
+}
+
 template <class P> int64_t rst_num_tracers(const RestrictedState<P>* e) { return e ? e->n_tracers : 0; }
 
 #undef RST_HIPCHK

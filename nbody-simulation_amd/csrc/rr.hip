@@ -74,3 +74,7 @@ NB_API int nbody_sweep_rr(nbody_rr* e, const float* delta, const float* clamp, c
                           nbody_counting* counter) {
   return rr_sweep<RrF32>(e, delta, clamp, steps, n_steps, counter);
 }
+// (a record per world — moments, extent, separations, ensemble_summary.h: likewise a prefix of its own)
+NB_API int nbody_summary_rr(nbody_rr* e, uint32_t flags, uint32_t height, const int32_t* ref, nbody_world_summary* out) {
+  return rr_summary<RrF32>(e, flags, height, ref, out);
+}

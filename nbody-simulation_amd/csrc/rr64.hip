@@ -75,3 +75,7 @@ NB_API int nbody_sweep_rr64(nbody_rr64* e, const double* delta, const float* cla
                             nbody_counting* counter) {
   return rr_sweep<RrF64>(e, delta, clamp, steps, n_steps, counter);
 }
+// (a record per world — moments, extent, separations, ensemble_summary.h: likewise a prefix of its own)
+NB_API int nbody_summary_rr64(nbody_rr64* e, uint32_t flags, uint32_t height, const int32_t* ref, nbody_world_summary* out) {
+  return rr_summary<RrF64>(e, flags, height, ref, out);
+}

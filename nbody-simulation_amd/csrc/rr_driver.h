@@ -194,6 +194,18 @@ int rr_deltas(RrState<P>* e, uint32_t flags, uint8_t* out, size_t cap, size_t* b
   return ens_deltas<P>(e, flags, out, cap, bytes_out, offsets_out, step_out, rows);
 }
 
+// Summaries: the ensemble's, over segments of these sizes or these counts (a world without tracers: a record with rows == 0).
+template <class P> int rr_summary(RrState<P>* e, uint32_t flags, uint32_t height, const int32_t* ref, nbody_world_summary* out) {
+  if (!e) return NBODY_ERR_INVALID;
+  SummaryRows<P> rows;
+  rows.sizes = e->sizes.data();
+  if (e->tracer_rows) rows.counts = e->counts.data();
+  rows.tpos = e->tpos;
+  rows.tvel = e->tvel;
+  rows.tracer_calls = true;
+  return ens_summary<P>(e, flags, height, ref, out, rows);
+}
+
 // The sizes and the tracer counts of every world; either output may be NULL.  Without tracers every count is 0.
 template <class P> int rr_sizes(const RrState<P>* e, int64_t* n_bodies_out, int64_t* n_tracers_out) {
   if (!e) return NBODY_ERR_INVALID;

@@ -45,6 +45,12 @@ Every class has `sweep(delta, clamp=None, steps=None)` (nbody_sweep_*): an updat
 clamp[k] and takes steps[k] steps, then stands still bit for bit — a time-step convergence study or a softening sweep in one
 handle.  World k's bits are those of the same class holding world k alone with that clamp, stepped by update(delta[k],
 n_steps=steps[k]).
+
+Every class has `summary(height=0, ref=None)` (nbody_summary_*) as well: one record per world — rows, finite rows, rows inside the
+frame, mass, extent, largest squared speed, the weighted sums behind centre of mass, momentum and kinetic sum, and the squared
+separations from the world ref[k] names — as an array of `SUMMARY_DTYPE`, computed on the device from the current rows, every
+field a stated function of the world's own rows bit for bit; the classes with tracers take `tracers=True` for the
+tracers' segments.  `summary_of(pos, vel, weight, ref, height)` is the same contract in host code, for one segment.
 """
 from __future__ import annotations
 
@@ -100,6 +106,89 @@ def _checked_sweep(who, b, dtype, delta, clamp, steps, n_steps):
     return delta, clamp, steps, 1 if n_steps is None else n_steps
 
 
+SUMMARY_DTYPE = _capi.SUMMARY_DTYPE
+MAX_HEIGHT = 1 << 24       # of a summary's frame, as the frames'
+
+
+def _checked_summary(who, b, height, ref):
+    """The arguments of `summary` for b worlds -> (height, ref int32[b] contiguous or None); ValueError naming `who` and the
+    argument for anything else."""
+    if isinstance(height, bool) or not isinstance(height, (int, np.integer)) or not 0 <= int(height) <= MAX_HEIGHT:
+        raise ValueError(f"{who}.summary: height must be an integer 0 .. 2^24, got {height!r}")
+    if ref is not None:
+        ref = np.asarray(ref)
+        if ref.ndim != 1 or ref.shape[0] != b:
+            raise ValueError(f"{who}.summary: ref must hold one world index per world ({b} worlds), got shape {ref.shape}")
+        if ref.dtype.kind not in "iu":
+            raise ValueError(f"{who}.summary: ref must be integers (-1: no reference), got {ref.dtype}")
+        bad = np.flatnonzero((ref < -1) | (ref >= b))
+        if bad.size:
+            k = int(bad[0])
+            raise ValueError(f"{who}.summary: ref[{k}] = {ref[k]} of world {k} is outside -1 .. {b - 1}")
+        ref = np.ascontiguousarray(ref, dtype=np.int32)
+    return int(height), ref
+
+
+def summary_of(pos, vel, weight=None, ref=None, height=0):
+    """One segment's summary record in host code (nbody_summary_of_f32 / _of_f64 by the arrays' dtype; no GPU needed): pos, vel
+    [rows, 2] float32 or float64, weight [rows] integers or None (all 1), ref None or a pair (position[rows, 2], velocity[rows, 2])
+    of the reference world's rows -> a `SUMMARY_DTYPE` scalar, the bits `summary()` gives for a world holding these rows."""
+    pos, vel = np.asarray(pos), np.asarray(vel)
+    if pos.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError(f"summary_of: pos must be float32 or float64, got {pos.dtype}")
+    if pos.ndim != 2 or pos.shape[1] != 2:
+        raise ValueError(f"summary_of: pos must be [rows, 2], got {pos.shape}")
+    rows = pos.shape[0]
+
+    def same(name, a):
+        a = np.asarray(a)
+        if a.dtype != pos.dtype or a.shape != pos.shape:
+            raise ValueError(f"summary_of: {name} must be {pos.dtype} {pos.shape} as pos is, got {a.dtype} {a.shape}")
+        return np.ascontiguousarray(a)
+    pos, vel = np.ascontiguousarray(pos), same("vel", vel)
+    if weight is not None:
+        weight = np.asarray(weight)
+        if weight.shape != (rows,) or weight.dtype.kind not in "ui":
+            raise ValueError(f"summary_of: weight must be integers [rows] = {(rows,)}, got {weight.dtype} {weight.shape}")
+        weight = np.ascontiguousarray(weight, dtype=np.uint32)
+    rp = rv = None
+    if ref is not None:
+        if not isinstance(ref, (tuple, list)) or len(ref) != 2:
+            raise ValueError("summary_of: ref must be None or a pair (position[rows, 2], velocity[rows, 2])")
+        rp, rv = same("ref position", ref[0]), same("ref velocity", ref[1])
+    height, _ = _checked_summary("summary_of", 0, height, None)
+    out = np.zeros(1, SUMMARY_DTYPE)
+    call = getattr(_capi.load(), "nbody_summary_of_f32" if pos.dtype == np.float32 else "nbody_summary_of_f64")
+    rc = call(rows, _capi._ptr(pos), _capi._ptr(vel), _capi._ptr(weight), _capi._ptr(rp), _capi._ptr(rv), height, _capi._ptr(out))
+    if rc != _capi.OK:
+        raise _capi.NBodyError(rc, "summary_of: refused")
+    return out[0]
+
+
+class _Summary:
+    """`summary` for the ensemble classes without tracers: the class keeps `_n_worlds`, its handle has `summary`."""
+
+    def summary(self, height=0, ref=None):
+        """-> SUMMARY_DTYPE[B]: one record per world of its bodies' current rows (nbody_summary_*), bit for bit `summary_of` of
+        that world's rows.  height: the frame of `in_bounds` (0: none).  ref: None, or one world index per world (-1: none) — the
+        world whose rows sep_rows, sep_max2 and sep_sum2 are measured from.  The arguments are checked here, with ValueError,
+        before the library is touched; the state is untouched."""
+        height, ref = _checked_summary(type(self).__name__, self._n_worlds, height, ref)
+        return self.h.summary(height, ref)
+
+
+class _SummaryWithTracers:
+    """`summary` for the ensemble classes with tracers."""
+
+    def summary(self, height=0, ref=None, tracers=False):
+        """-> SUMMARY_DTYPE[B]: one record per world of its bodies' current rows or, with tracers=True, of its tracers' (w = 1; a
+        world without tracers: rows == 0), bit for bit `summary_of` of those rows.  height: the frame of `in_bounds` (0: none).
+        ref: None, or one world index per world (-1: none).  The arguments are checked here, with ValueError, before the library
+        is touched; the state is untouched."""
+        height, ref = _checked_summary(type(self).__name__, self._n_worlds, height, ref)
+        return self.h.summary(height, ref, bool(tracers))
+
+
 class _Sweep:
     """`sweep` for every ensemble class: the class keeps `_n_worlds` and `_dtype`, its handle has `sweep`."""
 
@@ -151,7 +240,7 @@ def _checked(position, velocity, weight, dtype=np.float32, who=None, other=None)
     return b, n, np.ascontiguousarray(position), np.ascontiguousarray(velocity), weight
 
 
-class _EnsembleBase(_Sweep):
+class _EnsembleBase(_Summary, _Sweep):
     """What Ensemble, Ensemble64 and the restricted ensembles share; each names its dtype and makes its own kind of handle."""
     _dtype = None
 
@@ -270,7 +359,7 @@ def _checked_tracers(tracers, b, who="RestrictedEnsemble", dtype=np.float32):
     return m, np.ascontiguousarray(tp), np.ascontiguousarray(tv)
 
 
-class _RestrictedBase(_EnsembleBase):
+class _RestrictedBase(_SummaryWithTracers, _EnsembleBase):
     """What RestrictedEnsemble and RestrictedEnsemble64 share: the tracers beside the bodies.  Each names its dtype, makes its own
     kind of handle and says which class takes the other dtype."""
     _other = None
@@ -398,7 +487,7 @@ def _checked_ragged(positions, velocities, weights, dtype=np.float32, who=None, 
     return np.asarray(sizes, np.int64), position, velocity, weight
 
 
-class _RaggedBase(_Sweep):
+class _RaggedBase(_Summary, _Sweep):
     """What RaggedEnsemble and RaggedEnsemble64 share; each names its dtype, makes its own kind of handle and has its own
     constructor."""
     _dtype = None
@@ -538,7 +627,7 @@ def _checked_rr_tracers(tracers, sizes, who="RaggedRestrictedEnsemble", dtype=np
     return counts, np.ascontiguousarray(np.concatenate(tps)), np.ascontiguousarray(np.concatenate(tvs))
 
 
-class RaggedRestrictedEnsemble(_RaggedBase):
+class RaggedRestrictedEnsemble(_SummaryWithTracers, _RaggedBase):
     """Worlds of different sizes, each with tracers of its own, stepped together (nbody_rr_*), float32: positions, velocities
     are sequences of [n_k, 2] arrays, weights a sequence of [n_k] integer arrays or None (all 1), tracers None or a list with one
     entry per world, each None or a pair (position[m_k, 2], velocity[m_k, 2]).  1 .. 4096 bodies per world, at most 2^26 bodies
