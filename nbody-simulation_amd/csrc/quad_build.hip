@@ -59,8 +59,8 @@ __global__ __launch_bounds__(256) void qb_path_keys(const void* pos_, int n, T r
     const T xmid = ox + half, ymid = oy + half;        // :174-175
     const int north = p.y > ymid, west = p.x > xmid;   // :176-177 (strict)
     key = (key << 2) | (uint64_t)((north << 1) + west);
-    ox = west ? ox + half : ox + (T)0.0;               // :183-186
-    oy = north ? oy + half : oy + (T)0.0;
+    ox = west ? ox + half : ox + (T)0.0;               // :183-186 (child 0 would keep a -0.0, which no comparison here
+    oy = north ? oy + half : oy + (T)0.0;              // can tell from +0.0; qb_emit_nodes, which writes offsets out, keeps it)
     h = half;
   }
   keys[i] = key;
@@ -196,8 +196,10 @@ __global__ __launch_bounds__(256) void qb_emit_nodes(const uint64_t* __restrict_
     if (d < l) {  // descend one level along the path
       const int code = (int)((key >> (2 * (kLevels - 1 - d))) & 3);
       const T half = h / (T)2.0;
-      ox = (code & 1) ? ox + half : ox + (T)0.0;
-      oy = (code & 2) ? oy + half : oy + (T)0.0;
+      // child 0 takes the parent's offset as it is (quad_tree.rs:183), the others add 0.0 or half (:184-186): only a -0.0
+      // offset tells the difference, and keeps its sign down the chain of first children
+      ox = (code & 1) ? ox + half : ((code & 2) ? ox + (T)0.0 : ox);
+      oy = (code & 2) ? oy + half : ((code & 1) ? oy + (T)0.0 : oy);
       h = half;
     }
   }

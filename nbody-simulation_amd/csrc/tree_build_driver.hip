@@ -170,8 +170,9 @@ template <class T> int quad_build_device(nbody_ctx* c, State<T>& s) {
   auto& out = s.set[1 - s.cur];
   const T rx = (T)c->params.quad_root_x, ry = (T)c->params.quad_root_y, rh = (T)c->params.quad_root_h;
   // the sorts only look at as many levels as the tree is expected to have: the last quad tree's depth plus three (all 31
-  // the first time, and again whenever that turns out to be too few)
-  int sort_levels = s.quad_depth_hint > 0 ? s.quad_depth_hint + 3 : 31;
+  // the first time, and again whenever that turns out to be too few; never more than the 31 the key holds, which is what
+  // the trace then says)
+  int sort_levels = s.quad_depth_hint > 0 ? std::min(s.quad_depth_hint + 3, 31) : 31;
   int flags[3] = {0, 0, 0};
   for (;;) {
     HIPCHK(c, quad_build_phase_a<T>(c->stream, in.pos, n, rx, ry, rh, s.qb_scratch, L, s.order_dev, sort_levels));
