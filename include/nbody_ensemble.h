@@ -43,7 +43,8 @@
  *     on a copy stream (the synchronous streams are nbody_deltas_* and the frames nbody_frames_*, both at the end of this
  *     file); hipGraph replay.  The library reads no environment variable for any of this.  (A time step, a clamp and a number
  *     of steps per world: nbody_sweep_* at the end of this file.  A record per world of what a study ends in — moments, extent,
- *     separations: nbody_summary_* at the end of this file.)
+ *     separations: nbody_summary_* at the end of this file.  Every target's nearest neighbour and the pairs the clamp
+ *     altered: nbody_encounters_* at the end of this file.)
  * Arrays are world-major, [n_worlds][n_bodies] rows, pos / vel interleaved x,y; weight may be NULL (all 1); an upload replaces
  * the previous ensemble, whatever its shape. */
 typedef struct nbody_ensemble nbody_ensemble;
@@ -681,5 +682,104 @@ int nbody_summary_of_f32(int64_t rows, const float* pos_xy, const float* vel_xy,
                          const float* ref_pos_xy /*NULL: none*/, const float* ref_vel_xy, uint32_t height, nbody_world_summary* out);
 int nbody_summary_of_f64(int64_t rows, const double* pos_xy, const double* vel_xy, const uint32_t* weight /*NULL: all 1*/,
                          const double* ref_pos_xy /*NULL: none*/, const double* ref_vel_xy, uint32_t height, nbody_world_summary* out);
+
+/* ---- encounters of an ensemble: per target its nearest neighbour and its clamped pairs, per world one record --------
+ * What a softening sweep asks — is the clamp deciding the result? — and what a restricted problem asks of every tracer — which
+ * body is nearest, and how near (capture, impact, close fly-by) — for all eight handles above, without a download of all rows and
+ * an O(n^2) loop per world on the host.  The pair law (calculate_gravity, main.rs:234-253) replaces `distance` by the clamp
+ * wherever dx*dx + dy*dy < clamp, and drops a pair wherever |dx| + |dy| is not a normal number; no summary field shows either.
+ * A segment's targets are one world's bodies or, with NBODY_ENCOUNTERS_TRACERS, one world's tracers; its sources are that
+ * world's bodies.
+ *   The prefix.  nbody_encounters_<handle>, and nbody_encounters_of_f32 / _of_f64: a closed set of ten, under a prefix of its own.
+ *   Arithmetic.  The handle's own precision T (float on the f32 handles, double on the f64 ones), with exactly the step's
+ *     expressions: dx = xj - xi, dy = yj - yi, sum = |dx| + |dy|, d2 = dx*dx + dy*dy.  Each operation is one IEEE operation in
+ *     T; nothing is fused.  So d2 is the very `distance` the step compares with its clamp, under any params.arith: an encounter
+ *     report does not depend on arith.
+ *     Live.  A pair is live when `sum` is a normal number; otherwise it is skipped (coincident bodies, subnormal differences,
+ *     non-finite rows).  A live d2 is never NaN or negative: it lies in [+0, +inf], and both ends occur — d2 can underflow to +0
+ *     while `sum` is normal, and overflow to +inf while `sum` is finite.  Both are live pairs: an overflowed d2 = +inf comes with
+ *     nn_index >= 0, "no live pair" with nn_index == -1 and nn_d2 = +inf.
+ *     Close.  A pair is close when it is live and d2 < limit2[k] (widened to double on the f64 handles, as a step widens its
+ *     clamp).  A NaN or zero limit gives no close pair; +inf makes every live pair with a finite d2 close.  limit2 == NULL:
+ *     every world uses params.clamp, and close_pairs is then the number of ordered pairs whose force the clamp altered in a
+ *     step from these rows.
+ *   Fields.  Per target: nn_d2 is the smallest live d2, nn_index the world-local index of the source that attains it, close the
+ *     target's number of close pairs.  Per world: the counts are integer sums over its targets; min_* is the smallest nn_d2 over
+ *     the targets that have a neighbour, min_source that row's nn_index; max_nn_* the largest nn_d2 over the same targets.
+ *     Both doubles are the T values widened (exact).
+ *   Tie rules.  nn_index is the lowest source index that attains nn_d2; min_row and max_nn_row are the lowest row that attains
+ *     the extreme.  With them every output is order-free — minima and maxima with an index rule, and integer counts — so the
+ *     contract is bit for bit, without a tolerance, and the kernel is free to cut the sources into chunks: walking j ascending
+ *     and replacing on a strict `<` gives the lowest index.
+ *   Bodies.  The sources are the world's bodies; j == i is excluded by index, is not a pair and is counted nowhere.  A distinct
+ *     coincident body is a skipped pair.  live_pairs + skipped_pairs == rows * (sources - 1).
+ *   Tracers.  With NBODY_ENCOUNTERS_TRACERS the targets are the world's tracers and the sources all its bodies: live_pairs +
+ *     skipped_pairs == rows * sources.  Tracer-tracer pairs do not exist (tracers are massless).  A restricted handle without
+ *     tracers, or a world of an nbody_rr handle without them, gives rows == 0: zero counts, -1 indices, min_d2 = +inf.
+ *     max_nn_d2 is +0.0 wherever no target has a neighbour.
+ *   Layout.  nn_index, nn_d2 and close are host memory, one entry per target of all worlds, laid out as the handle's
+ *     *_download (for the tracers: *_tracers_download) lays out that segment's rows; each may be NULL.  nn_d2 is float on the
+ *     f32 handles and double on the f64 ones; limit2 is float on all eight, as a sweep's clamp is.
+ *   Independence.  A world's record and rows are a function of its own rows and limit2[k] alone: not of the number of worlds,
+ *     its index, the other worlds, or which of the optional arrays were asked for.
+ *   Calls.  Synchronous, on the handle's stream.  They read the current rows and write nothing of the state: stepping with
+ *     encounter calls in between gives the bits of stepping alone.  Two launches whatever the number of worlds or their sizes:
+ *     one over (world, tile of 256 targets) that evaluates the pairs — the same number of pairs as a step, without a division —
+ *     and one small reduce with a block per world.  No floating-point atomics; nothing is read back before the end.  The device
+ *     scratch belongs to the handle, is grown on demand and is freed with its other arrays.  out: host memory, one per world.
+ *   nbody_encounters_of_f32 / _of_f64.  Pure host code, no device, no handle: one segment by the contract above — the CPU
+ *     statement of it, the same bits.  self != 0: source j is target j itself (the bodies' case; the two arrays may be the same).
+ *     They refuse negative counts, out NULL, a NULL array with a non-zero count, self != 0 with n_targets != n_sources, and
+ *     n_sources > 2^31 - 1, with NBODY_ERR_INVALID and no message.
+ *   Refusals.  NBODY_ERR_INVALID before anything is allocated or launched, the message beginning with the handle's word
+ *     ("ensemble", "ragged", "restricted", "ragged restricted") and naming "encounters": nothing uploaded; out NULL; unknown
+ *     flag bits; NBODY_ENCOUNTERS_TRACERS on one of the four handles that have no tracer calls.  A NULL handle gives
+ *     NBODY_ERR_INVALID without a message.
+ *   Not offered: tracer-tracer pairs; the k nearest for k > 1; the minimum over the steps of a call (that would mean touching
+ *     the step kernels); a device-pointer variant; anything for nbody_ctx contexts. */
+typedef struct nbody_world_encounters { /* 12 fields of 8 bytes, no padding: 96 bytes */
+  int64_t rows;          /* targets of the segment: the world's bodies, or its tracers */
+  int64_t sources;       /* the world's bodies */
+  int64_t live_pairs;    /* ordered (target, source) pairs the law evaluates */
+  int64_t skipped_pairs; /* ordered pairs it drops (for bodies, j == i is not a pair and is not counted) */
+  int64_t close_pairs;   /* live pairs with d2 < limit2 */
+  int64_t close_rows;    /* targets with at least one close pair */
+  int64_t isolated_rows; /* targets with no live pair (nn_index == -1) */
+  int64_t min_row, min_source; /* the closest live pair; -1, -1 where the world has none */
+  double min_d2;         /* its d2, widened; +inf where there is none */
+  int64_t max_nn_row;    /* the target whose nearest neighbour is farthest; -1 where none */
+  double max_nn_d2;      /* its nn_d2, widened; +0.0 where there is none */
+} nbody_world_encounters;
+#define NBODY_ENCOUNTERS_TRACERS 1u /* targets are the world's tracers, sources its bodies */
+int nbody_encounters_ensemble(nbody_ensemble* e, uint32_t flags, const float* limit2 /*[n_worlds] or NULL: params.clamp*/,
+                              nbody_world_encounters* out /*[n_worlds]*/, int32_t* nn_index /*[rows] or NULL*/,
+                              float* nn_d2 /*[rows] or NULL*/, uint32_t* close /*[rows] or NULL*/);
+int nbody_encounters_ensemble64(nbody_ensemble64* e, uint32_t flags, const float* limit2 /*[n_worlds] or NULL: params.clamp*/,
+                                nbody_world_encounters* out /*[n_worlds]*/, int32_t* nn_index /*[rows] or NULL*/,
+                                double* nn_d2 /*[rows] or NULL*/, uint32_t* close /*[rows] or NULL*/);
+int nbody_encounters_ragged(nbody_ragged* e, uint32_t flags, const float* limit2 /*[n_worlds] or NULL: params.clamp*/,
+                            nbody_world_encounters* out /*[n_worlds]*/, int32_t* nn_index /*[rows] or NULL*/,
+                            float* nn_d2 /*[rows] or NULL*/, uint32_t* close /*[rows] or NULL*/);
+int nbody_encounters_ragged64(nbody_ragged64* e, uint32_t flags, const float* limit2 /*[n_worlds] or NULL: params.clamp*/,
+                              nbody_world_encounters* out /*[n_worlds]*/, int32_t* nn_index /*[rows] or NULL*/,
+                              double* nn_d2 /*[rows] or NULL*/, uint32_t* close /*[rows] or NULL*/);
+int nbody_encounters_restricted(nbody_restricted* e, uint32_t flags, const float* limit2 /*[n_worlds] or NULL: params.clamp*/,
+                                nbody_world_encounters* out /*[n_worlds]*/, int32_t* nn_index /*[rows] or NULL*/,
+                                float* nn_d2 /*[rows] or NULL*/, uint32_t* close /*[rows] or NULL*/);
+int nbody_encounters_restricted64(nbody_restricted64* e, uint32_t flags, const float* limit2 /*[n_worlds] or NULL: params.clamp*/,
+                                  nbody_world_encounters* out /*[n_worlds]*/, int32_t* nn_index /*[rows] or NULL*/,
+                                  double* nn_d2 /*[rows] or NULL*/, uint32_t* close /*[rows] or NULL*/);
+int nbody_encounters_rr(nbody_rr* e, uint32_t flags, const float* limit2 /*[n_worlds] or NULL: params.clamp*/,
+                        nbody_world_encounters* out /*[n_worlds]*/, int32_t* nn_index /*[rows] or NULL*/,
+                        float* nn_d2 /*[rows] or NULL*/, uint32_t* close /*[rows] or NULL*/);
+int nbody_encounters_rr64(nbody_rr64* e, uint32_t flags, const float* limit2 /*[n_worlds] or NULL: params.clamp*/,
+                          nbody_world_encounters* out /*[n_worlds]*/, int32_t* nn_index /*[rows] or NULL*/,
+                          double* nn_d2 /*[rows] or NULL*/, uint32_t* close /*[rows] or NULL*/);
+int nbody_encounters_of_f32(int64_t n_targets, const float* target_xy, int64_t n_sources, const float* source_xy, int self,
+                            float limit2, nbody_world_encounters* out, int32_t* nn_index /*[n_targets] or NULL*/,
+                            float* nn_d2 /*[n_targets] or NULL*/, uint32_t* close /*[n_targets] or NULL*/);
+int nbody_encounters_of_f64(int64_t n_targets, const double* target_xy, int64_t n_sources, const double* source_xy, int self,
+                            double limit2, nbody_world_encounters* out, int32_t* nn_index /*[n_targets] or NULL*/,
+                            double* nn_d2 /*[n_targets] or NULL*/, uint32_t* close /*[n_targets] or NULL*/);
 
 #endif /* NBODY_ENSEMBLE_H */

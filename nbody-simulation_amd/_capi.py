@@ -24,6 +24,11 @@ SUMMARY_TRACERS = 1                 # NBODY_SUMMARY_TRACERS: the flag of nbody_s
 SUMMARY_DTYPE = np.dtype([(name, np.int64) for name in ("rows", "counted", "in_bounds", "sep_rows")] +
                          [(name, np.float64) for name in ("mass", "min_x", "min_y", "max_x", "max_y", "max_speed2", "sum_wx", "sum_wy",
                                                           "sum_wvx", "sum_wvy", "sum_wv2", "sep_max2", "sep_sum2")])
+ENCOUNTERS_TRACERS = 1              # NBODY_ENCOUNTERS_TRACERS: the flag of nbody_encounters_<handle>
+# nbody_world_encounters of include/nbody_ensemble.h: 12 fields of 8 bytes, no padding
+ENCOUNTERS_DTYPE = np.dtype([(name, np.int64) for name in ("rows", "sources", "live_pairs", "skipped_pairs", "close_pairs", "close_rows",
+                                                           "isolated_rows", "min_row", "min_source")] +
+                            [("min_d2", np.float64), ("max_nn_row", np.int64), ("max_nn_d2", np.float64)])
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_DEGENERATE, ERR_NOMEM = 0, -1, -2, -3, -4, -5
 ARITH_AUTO, ARITH_FAST, ARITH_EXACT = 0, 1, 2
 ORDER_AS_WRITTEN, ORDER_CONSISTENT = 0, 1
@@ -226,6 +231,12 @@ _SIGS = {
        for h in ("ensemble", "ensemble64", "ragged", "ragged64", "restricted", "restricted64", "rr", "rr64")},
     "nbody_summary_of_f32": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp]),
     "nbody_summary_of_f64": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp]),
+    # nbody_encounters_<handle>: flags, limit2 float32[n_worlds] or NULL, out nbody_world_encounters[n_worlds] (ENCOUNTERS_DTYPE),
+    # nn_index int32[rows], nn_d2 [rows] of the handle's dtype, close uint32[rows], each or NULL
+    **{"nbody_encounters_" + h: (C.c_int, [_vp, C.c_uint32, C.POINTER(_f32), _vp, _vp, _vp, _vp])
+       for h in ("ensemble", "ensemble64", "ragged", "ragged64", "restricted", "restricted64", "rr", "rr64")},
+    "nbody_encounters_of_f32": (C.c_int, [_i64, _vp, _i64, _vp, _i32, _f32, _vp, _vp, _vp, _vp]),
+    "nbody_encounters_of_f64": (C.c_int, [_i64, _vp, _i64, _vp, _i32, _f64, _vp, _vp, _vp, _vp]),
     "nbody_accel_tree_f32": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_accel_tree_f64": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_tree_info": (C.c_int, [_vp, C.POINTER(TreeView)]),
@@ -1036,8 +1047,22 @@ class _EnsembleHandleBase:
                                             None if ref is None else ref.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(out)))
         return out
 
+    def encounters(self, limit2, tracers=False, rows=True):
+        """nbody_encounters_<handle>: per target its nearest source and its clamped pairs, per world one record, of the current
+        rows (tracers=True: the tracers against the bodies) -> (ENCOUNTERS_DTYPE[worlds], nn_index int32[targets], nn_d2
+        [targets] of the handle's dtype, close uint32[targets]), the three per-target arrays flat in the download's order, or None
+        with rows=False.  limit2: float32[worlds], contiguous, or None (ensemble.py's `encounters` checks and casts it)."""
+        out = np.zeros(self.shape[0], ENCOUNTERS_DTYPE)
+        total = int(self._delta_rows(tracers).sum()) if rows else 0
+        index, d2, close = (np.zeros(total, t) for t in (np.int32, self._dtype, np.uint32)) if rows else (None, None, None)
+        name = "nbody_encounters_" + self._prefix[len("nbody_"):]
+        self._check(getattr(self.lib, name)(self.h, ENCOUNTERS_TRACERS if tracers else 0,
+                                            None if limit2 is None else limit2.ctypes.data_as(C.POINTER(C.c_float)), _ptr(out),
+                                            _ptr(index), _ptr(d2), _ptr(close)))
+        return out, index, d2, close
+
     def _delta_rows(self, tracers):
-        """The rows of every segment a deltas() call addresses, int64[worlds]."""
+        """The rows of every segment a deltas() or encounters() call addresses, int64[worlds]."""
         b, n = self.shape
         return np.full(b, getattr(self, "n_tracers", 0) if tracers else n, np.int64)
 

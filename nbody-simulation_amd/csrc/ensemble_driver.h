@@ -26,6 +26,8 @@
 // other drivers supply the launches of a step, as they do for ens_update_with.
 // Summaries (nbody_summary_*, ensemble_summary.h) are ens_summary below for every handle: the other drivers hand it their sizes,
 // counts and tracer arrays in a SummaryRows; a ragged handle's row ranges are the frames' table.
+// Encounters (nbody_encounters_*, ensemble_encounters.h) are ens_encounters below for every handle in the same way, over an
+// EncounterRows.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -36,6 +38,7 @@
 
 #include "driver.h"
 #include "ensemble_deltas.h"
+#include "ensemble_encounters.h"
 #include "ensemble_frames.h"
 #include "ensemble_kernels.h"
 #include "ensemble_summary.h"
@@ -111,6 +114,18 @@ template <class P> struct EnsembleState {
   size_t summary_out_bytes = 0, summary_chunks_bytes = 0, summary_ref_bytes = 0;
   uint32_t* summary_chunk_base = nullptr;
   int64_t summary_tracer_chunks = 0;
+  // encounters (ens_encounters): the records, the four per-target arrays and the call's limit2[], all device scratch grown on
+  // demand; beside the frames' table (and valid with it) the first tile of every world's bodies and of its tracers, for a ragged
+  // handle.  Freed with the arrays above.
+  nbody_world_encounters* enc_out = nullptr;
+  int32_t* enc_index = nullptr;
+  void* enc_d2 = nullptr;
+  uint32_t* enc_close = nullptr;
+  uint32_t* enc_live = nullptr;
+  float* enc_limit = nullptr;
+  size_t enc_out_bytes = 0, enc_index_bytes = 0, enc_d2_bytes = 0, enc_close_bytes = 0, enc_live_bytes = 0, enc_limit_bytes = 0;
+  uint32_t* enc_tile_base = nullptr;  // [2][n_worlds + 1]: the bodies', then the tracers'
+  int64_t enc_body_tiles = 0, enc_tracer_tiles = 0;
 };
 
 template <class P> thread_local std::string g_ens_create_error;  // one per precision: what a failed create left for its thread
@@ -138,6 +153,10 @@ template <class P> void ens_free(EnsembleState<P>* e) {
   free_dev(e->summary_out); free_dev(e->summary_chunks); free_dev(e->summary_ref); free_dev(e->summary_chunk_base);
   e->summary_out_bytes = e->summary_chunks_bytes = e->summary_ref_bytes = 0;
   e->summary_tracer_chunks = 0;
+  free_dev(e->enc_out); free_dev(e->enc_index); free_dev(e->enc_d2); free_dev(e->enc_close); free_dev(e->enc_live); free_dev(e->enc_limit);
+  free_dev(e->enc_tile_base);
+  e->enc_out_bytes = e->enc_index_bytes = e->enc_d2_bytes = e->enc_close_bytes = e->enc_live_bytes = e->enc_limit_bytes = 0;
+  e->enc_body_tiles = e->enc_tracer_tiles = 0;
   e->dbodies.release();
   e->dtracers.release();
   e->n_worlds = e->n_bodies = e->rows = 0;
@@ -399,14 +418,15 @@ template <class P, class B> int ens_frame_buffer(EnsembleState<P>* e, B*& p, siz
 }
 
 // A ragged handle's table of row ranges on the device (sizes: the bodies per world; counts: the tracers per world, or NULL: none),
-// uploaded by the first frames or summary call after an upload of bodies or tracers.  Beside it, for the summaries, the first
-// chunk of every world's tracers among the chunks of all worlds' tracers, and their total.
+// uploaded by the first frames, summary or encounters call after an upload of bodies or tracers.  Beside it, for the summaries,
+// the first chunk of every world's tracers among the chunks of all worlds' tracers, and their total; for the encounters, the first
+// tile of every world's bodies among the tiles of all worlds' bodies, the same for the tracers, and the two totals.
 template <class P> int ens_frame_table(EnsembleState<P>* e, const int64_t* sizes, const int64_t* counts) {
   if (e->frame_table_valid) return NBODY_OK;
   const size_t n = (size_t)e->n_worlds;
   std::vector<FrameWorld> table(n);
-  std::vector<uint32_t> chunk_base(n + 1);
-  int64_t row0 = 0, trow0 = 0, chunk0 = 0;
+  std::vector<uint32_t> chunk_base(n + 1), tile_base(2 * (n + 1));
+  int64_t row0 = 0, trow0 = 0, chunk0 = 0, tile0 = 0, ttile0 = 0;
   for (size_t k = 0; k < n; ++k) {
     const int64_t m = counts ? counts[k] : 0;
     table[k] = FrameWorld{(uint32_t)row0, (uint32_t)sizes[k], (uint32_t)trow0, (uint32_t)m};  // (each sum <= 2^26)
@@ -414,14 +434,24 @@ template <class P> int ens_frame_table(EnsembleState<P>* e, const int64_t* sizes
     row0 += sizes[k];
     trow0 += m;
     chunk0 += summary_chunks((uint32_t)m);
+    tile_base[k] = (uint32_t)tile0;                                                            // (<= 2^26 worlds + 2^18 full tiles)
+    tile_base[n + 1 + k] = (uint32_t)ttile0;
+    tile0 += encounter_tiles((uint32_t)sizes[k]);
+    ttile0 += encounter_tiles((uint32_t)m);
   }
   chunk_base[n] = (uint32_t)chunk0;
+  tile_base[n] = (uint32_t)tile0;
+  tile_base[2 * n + 1] = (uint32_t)ttile0;
   if (!e->frame_table) ENS_HIPCHK(e, hipMalloc((void**)&e->frame_table, n * sizeof(FrameWorld)));
   if (!e->summary_chunk_base) ENS_HIPCHK(e, hipMalloc((void**)&e->summary_chunk_base, (n + 1) * sizeof(uint32_t)));
   ENS_HIPCHK(e, hipMemcpyAsync(e->frame_table, table.data(), n * sizeof(FrameWorld), hipMemcpyHostToDevice, e->stream));
+  if (!e->enc_tile_base) ENS_HIPCHK(e, hipMalloc((void**)&e->enc_tile_base, 2 * (n + 1) * sizeof(uint32_t)));
   ENS_HIPCHK(e, hipMemcpyAsync(e->summary_chunk_base, chunk_base.data(), (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+  ENS_HIPCHK(e, hipMemcpyAsync(e->enc_tile_base, tile_base.data(), 2 * (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
   ENS_HIPCHK(e, hipStreamSynchronize(e->stream));  // (the vectors go out of scope)
   e->summary_tracer_chunks = chunk0;
+  e->enc_body_tiles = tile0;
+  e->enc_tracer_tiles = ttile0;
   e->frame_table_valid = true;
   return NBODY_OK;
 }
@@ -674,6 +704,81 @@ int ens_summary(EnsembleState<P>* e, uint32_t flags, uint32_t height, const int3
   a.tracers = tracers ? 1u : 0u;
   ENS_HIPCHK(e, launch_ensemble_summary<typename P::Real>(e->stream, a, n_chunks, e->summary_chunks, e->summary_out));
   ENS_HIPCHK(e, hipMemcpyAsync(out, e->summary_out, n * sizeof(nbody_world_summary), hipMemcpyDeviceToHost, e->stream));
+  ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
+  return NBODY_OK;
+}
+
+// ---- encounters: per target its nearest source and its clamped pairs, per world one nbody_world_encounters
+// (ensemble_encounters.h) of the current rows, into host memory
+// What a handle tells ens_encounters about its rows, beyond the bodies of worlds of one size.
+template <class P> struct EncounterRows {
+  const int64_t* sizes = nullptr;         // worlds of different sizes: the bodies per world; NULL: e->n_bodies in every world
+  const int64_t* counts = nullptr;        // with sizes: the tracers per world, or NULL: none
+  int64_t n_tracers = 0;                  // without sizes: the tracers per world
+  int64_t tracer_rows = 0;                // with sizes: the tracers of all worlds together
+  const typename P::Vec2* tpos = nullptr; // the tracers (NULL where the handle holds none)
+  bool tracer_calls = false;              // the handle has tracer calls at all: NBODY_ENCOUNTERS_TRACERS is its to ask
+};
+
+// out: [n_worlds] records; nn_index, nn_d2, close: one entry per target of all worlds, each may be NULL.  Synchronous, on the
+// handle's stream; reads pos[cur] and the tracers' positions, writes no state.  Every refusal comes before anything is allocated
+// or launched.  Two launches; no loop over worlds but, once per upload, a ragged handle's table.
+template <class P>
+int ens_encounters(EnsembleState<P>* e, uint32_t flags, const float* limit2, nbody_world_encounters* out, int32_t* nn_index,
+                   typename P::Real* nn_d2, uint32_t* close, const EncounterRows<P>& rows = EncounterRows<P>()) {
+  using Real = typename P::Real;
+  if (!e) return NBODY_ERR_INVALID;
+  const std::string who = std::string(P::kWho) + " encounters: ";
+  if (!e->n_worlds) return ens_fail(e, NBODY_ERR_INVALID, who + "nothing uploaded");
+  if (!out) return ens_fail(e, NBODY_ERR_INVALID, who + "out is NULL");
+  if (flags & ~NBODY_ENCOUNTERS_TRACERS) return ens_fail(e, NBODY_ERR_INVALID, who + "unknown flag bits");
+  const bool tracers = (flags & NBODY_ENCOUNTERS_TRACERS) != 0;
+  if (tracers && !rows.tracer_calls) return ens_fail(e, NBODY_ERR_INVALID, who + "NBODY_ENCOUNTERS_TRACERS on a handle without tracers");
+
+  ENS_HIPCHK(e, hipSetDevice(e->device));
+  const size_t n = (size_t)e->n_worlds;
+  int64_t n_tiles, targets;
+  if (rows.sizes) {
+    if (int rc = ens_frame_table(e, rows.sizes, rows.counts)) return rc;
+    n_tiles = tracers ? e->enc_tracer_tiles : e->enc_body_tiles;
+    targets = tracers ? rows.tracer_rows : e->rows;
+  } else {
+    const int64_t per_world = tracers ? rows.n_tracers : e->n_bodies;
+    n_tiles = e->n_worlds * (int64_t)encounter_tiles((uint32_t)per_world);
+    targets = e->n_worlds * per_world;  // (<= 2^26)
+  }
+  const size_t t = (size_t)targets;
+  if (int rc = ens_frame_buffer(e, e->enc_out, e->enc_out_bytes, n * sizeof(nbody_world_encounters))) return rc;
+  if (t) {
+    if (int rc = ens_frame_buffer(e, e->enc_index, e->enc_index_bytes, t * sizeof(int32_t))) return rc;
+    if (int rc = ens_frame_buffer(e, e->enc_d2, e->enc_d2_bytes, t * sizeof(Real))) return rc;
+    if (int rc = ens_frame_buffer(e, e->enc_close, e->enc_close_bytes, t * sizeof(uint32_t))) return rc;
+    if (int rc = ens_frame_buffer(e, e->enc_live, e->enc_live_bytes, t * sizeof(uint32_t))) return rc;
+  }
+  if (limit2) {
+    if (int rc = ens_frame_buffer(e, e->enc_limit, e->enc_limit_bytes, n * sizeof(float))) return rc;
+    ENS_HIPCHK(e, hipMemcpyAsync(e->enc_limit, limit2, n * sizeof(float), hipMemcpyHostToDevice, e->stream));
+  }
+  EncounterArgs a;
+  a.pos = e->pos[e->cur];
+  a.tpos = rows.tpos;
+  a.table = rows.sizes ? e->frame_table : nullptr;
+  a.tile_base = rows.sizes ? e->enc_tile_base + (tracers ? n + 1 : 0) : nullptr;
+  a.limit2 = limit2 ? e->enc_limit : nullptr;
+  a.limit_all = e->params.clamp;
+  a.n_bodies = (uint32_t)e->n_bodies;
+  a.n_tracers = (uint32_t)rows.n_tracers;
+  a.n_worlds = (uint32_t)e->n_worlds;
+  a.tracers = tracers ? 1u : 0u;
+  a.nn_index = e->enc_index;
+  a.nn_d2 = e->enc_d2;
+  a.close = e->enc_close;
+  a.live = e->enc_live;
+  ENS_HIPCHK(e, launch_ensemble_encounters<Real>(e->stream, a, n_tiles, e->enc_out));
+  ENS_HIPCHK(e, hipMemcpyAsync(out, e->enc_out, n * sizeof(nbody_world_encounters), hipMemcpyDeviceToHost, e->stream));
+  if (t && nn_index) ENS_HIPCHK(e, hipMemcpyAsync(nn_index, e->enc_index, t * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+  if (t && nn_d2) ENS_HIPCHK(e, hipMemcpyAsync(nn_d2, e->enc_d2, t * sizeof(Real), hipMemcpyDeviceToHost, e->stream));
+  if (t && close) ENS_HIPCHK(e, hipMemcpyAsync(close, e->enc_close, t * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
   ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
   return NBODY_OK;
 }

@@ -110,6 +110,16 @@ template <class P> int ragged_summary(RaggedState<P>* e, uint32_t flags, uint32_
   return ens_summary<P>(e, flags, height, ref, out, rows);
 }
 
+// Encounters: the ensemble's, over segments of these sizes.
+template <class P>
+int ragged_encounters(RaggedState<P>* e, uint32_t flags, const float* limit2, nbody_world_encounters* out, int32_t* nn_index,
+                      typename P::Real* nn_d2, uint32_t* close) {
+  if (!e) return NBODY_ERR_INVALID;
+  EncounterRows<P> rows;
+  rows.sizes = e->sizes.data();
+  return ens_encounters<P>(e, flags, limit2, out, nn_index, nn_d2, close, rows);
+}
+
 template <class P> int ragged_sizes(const RaggedState<P>* e, int64_t* n_bodies_out) {
   if (!e || !n_bodies_out) return NBODY_ERR_INVALID;
   for (int64_t k = 0; k < e->n_worlds; ++k) n_bodies_out[k] = e->sizes[(size_t)k];

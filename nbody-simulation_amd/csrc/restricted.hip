@@ -56,3 +56,8 @@ NB_API int nbody_sweep_restricted(nbody_restricted* e, const float* delta, const
 NB_API int nbody_summary_restricted(nbody_restricted* e, uint32_t flags, uint32_t height, const int32_t* ref, nbody_world_summary* out) {
   return rst_summary<RstF32>(e, flags, height, ref, out);
 }
+// (nearest neighbours and clamped pairs per world, ensemble_encounters.h: likewise a prefix of its own)
+NB_API int nbody_encounters_restricted(nbody_restricted* e, uint32_t flags, const float* limit2, nbody_world_encounters* out, int32_t* nn_index, float* nn_d2,
+                                       uint32_t* close) {
+  return rst_encounters<RstF32>(e, flags, limit2, out, nn_index, nn_d2, close);
+}

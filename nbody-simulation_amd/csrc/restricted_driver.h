@@ -161,6 +161,18 @@ template <class P> int rst_summary(RestrictedState<P>* e, uint32_t flags, uint32
   return ens_summary<P>(e, flags, height, ref, out, rows);
 }
 
+// Encounters: the ensemble's, of the bodies or of the tracers against the bodies (without tracers: every world's record has rows == 0).
+template <class P>
+int rst_encounters(RestrictedState<P>* e, uint32_t flags, const float* limit2, nbody_world_encounters* out, int32_t* nn_index,
+                   typename P::Real* nn_d2, uint32_t* close) {
+  if (!e) return NBODY_ERR_INVALID;
+  EncounterRows<P> rows;
+  rows.n_tracers = e->n_tracers;
+  rows.tpos = e->tpos;
+  rows.tracer_calls = true;
+  return ens_encounters<P>(e, flags, limit2, out, nn_index, nn_d2, close, rows);
+}
+
 template <class P> int64_t rst_num_tracers(const RestrictedState<P>* e) { return e ? e->n_tracers : 0; }
 
 #undef RST_HIPCHK

@@ -79,3 +79,8 @@ NB_API int nbody_sweep_rr64(nbody_rr64* e, const double* delta, const float* cla
 NB_API int nbody_summary_rr64(nbody_rr64* e, uint32_t flags, uint32_t height, const int32_t* ref, nbody_world_summary* out) {
   return rr_summary<RrF64>(e, flags, height, ref, out);
 }
+// (nearest neighbours and clamped pairs per world, ensemble_encounters.h: likewise a prefix of its own)
+NB_API int nbody_encounters_rr64(nbody_rr64* e, uint32_t flags, const float* limit2, nbody_world_encounters* out, int32_t* nn_index, double* nn_d2,
+                                 uint32_t* close) {
+  return rr_encounters<RrF64>(e, flags, limit2, out, nn_index, nn_d2, close);
+}

@@ -206,6 +206,20 @@ template <class P> int rr_summary(RrState<P>* e, uint32_t flags, uint32_t height
   return ens_summary<P>(e, flags, height, ref, out, rows);
 }
 
+// Encounters: the ensemble's, over segments of these sizes or these counts (a world without tracers: a record with rows == 0).
+template <class P>
+int rr_encounters(RrState<P>* e, uint32_t flags, const float* limit2, nbody_world_encounters* out, int32_t* nn_index, typename P::Real* nn_d2,
+                  uint32_t* close) {
+  if (!e) return NBODY_ERR_INVALID;
+  EncounterRows<P> rows;
+  rows.sizes = e->sizes.data();
+  if (e->tracer_rows) rows.counts = e->counts.data();
+  rows.tracer_rows = e->tracer_rows;
+  rows.tpos = e->tpos;
+  rows.tracer_calls = true;
+  return ens_encounters<P>(e, flags, limit2, out, nn_index, nn_d2, close, rows);
+}
+
 // The sizes and the tracer counts of every world; either output may be NULL.  Without tracers every count is 0.
 template <class P> int rr_sizes(const RrState<P>* e, int64_t* n_bodies_out, int64_t* n_tracers_out) {
   if (!e) return NBODY_ERR_INVALID;

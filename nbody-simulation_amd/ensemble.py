@@ -51,6 +51,13 @@ frame, mass, extent, largest squared speed, the weighted sums behind centre of m
 separations from the world ref[k] names — as an array of `SUMMARY_DTYPE`, computed on the device from the current rows, every
 field a stated function of the world's own rows bit for bit; the classes with tracers take `tracers=True` for the
 tracers' segments.  `summary_of(pos, vel, weight, ref, height)` is the same contract in host code, for one segment.
+
+Every class has `encounters(limit2=None)` (nbody_encounters_*) too, the quadratic sibling of `summary`: per body its nearest
+neighbour (`nn_index`, `nn_d2`) and the number of its pairs closer than limit2[k] (`close`), and per world a record of
+`ENCOUNTERS_DTYPE` — live, skipped and close pairs, the closest pair, the most isolated body — in the handle's own precision with
+the step's own expressions, so with limit2=None `close_pairs` counts the ordered pairs whose force the clamp altered.  Every
+output is order-free, hence bit for bit; the classes with tracers take `tracers=True` for every tracer's nearest
+body.  `encounters_of(targets, sources, limit2)` is the same contract in host code, for one segment.
 """
 from __future__ import annotations
 
@@ -189,6 +196,94 @@ class _SummaryWithTracers:
         return self.h.summary(height, ref, bool(tracers))
 
 
+ENCOUNTERS_DTYPE = _capi.ENCOUNTERS_DTYPE
+
+
+def _checked_encounters(who, b, limit2, tracers, rows):
+    """The arguments of `encounters` for b worlds -> (limit2 float32[b] contiguous or None, tracers, rows); ValueError naming
+    `who` and the argument for anything else.  NaN and infinite limits are values like any other."""
+    if limit2 is not None:
+        limit2 = np.asarray(limit2)
+        if limit2.ndim != 1 or limit2.shape[0] != b:
+            raise ValueError(f"{who}.encounters: limit2 must hold one squared distance per world ({b} worlds), got shape {limit2.shape}")
+        if limit2.dtype.kind not in "fiu":
+            raise ValueError(f"{who}.encounters: limit2 must be real numbers, got {limit2.dtype}")
+        with np.errstate(over="ignore"):
+            limit2 = np.ascontiguousarray(limit2, dtype=np.float32)
+    for name, flag in (("tracers", tracers), ("rows", rows)):
+        if not isinstance(flag, (bool, np.bool_)):
+            raise ValueError(f"{who}.encounters: {name} must be True or False, got {flag!r}")
+    return limit2, bool(tracers), bool(rows)
+
+
+def encounters_of(targets, sources=None, limit2=0.001):
+    """One segment's encounters in host code (nbody_encounters_of_f32 / _of_f64 by the arrays' dtype; no GPU needed): targets
+    [rows, 2] float32 or float64; sources None — the targets are a world's bodies, each measured against the others — or
+    [n, 2] of the same dtype, a world's bodies around these tracers; limit2 a number, in the arrays' precision -> (record,
+    nn_index int32[rows], nn_d2 [rows], close uint32[rows]): the `ENCOUNTERS_DTYPE` scalar and the rows `encounters()` gives for a
+    world holding these rows."""
+    targets = np.asarray(targets)
+    if targets.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError(f"encounters_of: targets must be float32 or float64, got {targets.dtype}")
+    if targets.ndim != 2 or targets.shape[1] != 2:
+        raise ValueError(f"encounters_of: targets must be [rows, 2], got {targets.shape}")
+    targets = np.ascontiguousarray(targets)
+    own = sources is None
+    if own:
+        sources = targets
+    else:
+        sources = np.asarray(sources)
+        if sources.dtype != targets.dtype or sources.ndim != 2 or sources.shape[1] != 2:
+            raise ValueError(f"encounters_of: sources must be {targets.dtype} [n, 2] as targets are, got {sources.dtype} {sources.shape}")
+        sources = np.ascontiguousarray(sources)
+    if isinstance(limit2, (bool, np.bool_)) or not isinstance(limit2, (int, float, np.integer, np.floating)):
+        raise ValueError(f"encounters_of: limit2 must be a number, got {limit2!r}")
+    rows = targets.shape[0]
+    out = np.zeros(1, ENCOUNTERS_DTYPE)
+    index, d2, close = np.zeros(rows, np.int32), np.zeros(rows, targets.dtype), np.zeros(rows, np.uint32)
+    call = getattr(_capi.load(), "nbody_encounters_of_f32" if targets.dtype == np.float32 else "nbody_encounters_of_f64")
+    with np.errstate(over="ignore"):
+        limit2 = float(targets.dtype.type(limit2))
+    rc = call(rows, _capi._ptr(targets), sources.shape[0], _capi._ptr(sources), 1 if own else 0, limit2, _capi._ptr(out),
+              _capi._ptr(index), _capi._ptr(d2), _capi._ptr(close))
+    if rc != _capi.OK:
+        raise _capi.NBodyError(rc, "encounters_of: refused")
+    return out[0], index, d2, close
+
+
+class _Encounters:
+    """`encounters` for the ensemble classes without tracers: the class keeps `_n_worlds`, its handle has `encounters`; a class of
+    worlds of different sizes keeps `_cuts` (and `_tcuts` for its tracers) and gets per-world lists, as from `particles()`."""
+
+    def _encounters(self, limit2, tracers, rows):
+        limit2, tracers, rows = _checked_encounters(type(self).__name__, self._n_worlds, limit2, tracers, rows)
+        out, *flat = self.h.encounters(limit2, tracers, rows)
+        if not rows:
+            return out, None, None, None
+        if hasattr(self, "_cuts"):
+            return (out, *([w.copy() for w in np.split(a, self._tcuts if tracers else self._cuts)] for a in flat))
+        return (out, *(a.reshape(self._n_worlds, a.size // self._n_worlds) for a in flat))
+
+    def encounters(self, limit2=None, rows=True):
+        """-> (records, nn_index, nn_d2, close): ENCOUNTERS_DTYPE[B], and per body its nearest neighbour's world-local index (-1:
+        none), its squared distance in the class's dtype (+inf: none) and the number of its pairs with d2 < limit2[k] — [B, n]
+        arrays, or per-world lists where the worlds have sizes of their own; None each with rows=False.  limit2: None (the clamp
+        of every world) or one number per world.  Bit for bit `encounters_of` of that world's rows.  The arguments are checked
+        here, with ValueError, before the library is touched; the state is untouched."""
+        return self._encounters(limit2, False, rows)
+
+
+class _EncountersWithTracers(_Encounters):
+    """`encounters` for the ensemble classes with tracers."""
+
+    def encounters(self, limit2=None, tracers=False, rows=True):
+        """-> (records, nn_index, nn_d2, close) as the classes without tracers give them; with tracers=True the targets are every
+        world's tracers and the sources its bodies: per tracer the nearest body ([B, m] arrays or per-world lists; a world
+        without tracers: rows == 0).  The arguments are checked here, with ValueError, before the library is touched; the state
+        is untouched."""
+        return self._encounters(limit2, tracers, rows)
+
+
 class _Sweep:
     """`sweep` for every ensemble class: the class keeps `_n_worlds` and `_dtype`, its handle has `sweep`."""
 
@@ -240,7 +335,7 @@ def _checked(position, velocity, weight, dtype=np.float32, who=None, other=None)
     return b, n, np.ascontiguousarray(position), np.ascontiguousarray(velocity), weight
 
 
-class _EnsembleBase(_Summary, _Sweep):
+class _EnsembleBase(_Encounters, _Summary, _Sweep):
     """What Ensemble, Ensemble64 and the restricted ensembles share; each names its dtype and makes its own kind of handle."""
     _dtype = None
 
@@ -359,7 +454,7 @@ def _checked_tracers(tracers, b, who="RestrictedEnsemble", dtype=np.float32):
     return m, np.ascontiguousarray(tp), np.ascontiguousarray(tv)
 
 
-class _RestrictedBase(_SummaryWithTracers, _EnsembleBase):
+class _RestrictedBase(_EncountersWithTracers, _SummaryWithTracers, _EnsembleBase):
     """What RestrictedEnsemble and RestrictedEnsemble64 share: the tracers beside the bodies.  Each names its dtype, makes its own
     kind of handle and says which class takes the other dtype."""
     _other = None
@@ -487,7 +582,7 @@ def _checked_ragged(positions, velocities, weights, dtype=np.float32, who=None, 
     return np.asarray(sizes, np.int64), position, velocity, weight
 
 
-class _RaggedBase(_Summary, _Sweep):
+class _RaggedBase(_Encounters, _Summary, _Sweep):
     """What RaggedEnsemble and RaggedEnsemble64 share; each names its dtype, makes its own kind of handle and has its own
     constructor."""
     _dtype = None
@@ -627,7 +722,7 @@ def _checked_rr_tracers(tracers, sizes, who="RaggedRestrictedEnsemble", dtype=np
     return counts, np.ascontiguousarray(np.concatenate(tps)), np.ascontiguousarray(np.concatenate(tvs))
 
 
-class RaggedRestrictedEnsemble(_SummaryWithTracers, _RaggedBase):
+class RaggedRestrictedEnsemble(_EncountersWithTracers, _SummaryWithTracers, _RaggedBase):
     """Worlds of different sizes, each with tracers of its own, stepped together (nbody_rr_*), float32: positions, velocities
     are sequences of [n_k, 2] arrays, weights a sequence of [n_k] integer arrays or None (all 1), tracers None or a list with one
     entry per world, each None or a pair (position[m_k, 2], velocity[m_k, 2]).  1 .. 4096 bodies per world, at most 2^26 bodies
