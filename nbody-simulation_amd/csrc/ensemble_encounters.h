@@ -22,7 +22,7 @@
 #include <limits>
 
 #include "../../include/nbody_hip.h"
-#include "ensemble_frames.h"
+#include "ensemble_rows.h"
 
 namespace nbody {
 
@@ -37,7 +37,7 @@ __host__ __device__ inline uint32_t encounter_tiles(uint32_t n) { return (n + (u
 struct EncounterArgs {
   const void* pos = nullptr;    // T2 rows of all worlds (the handle's current buffer): the sources, and the targets of the bodies' call
   const void* tpos = nullptr;   // tracers (may be NULL where no world has one)
-  const FrameWorld* table = nullptr;     // ragged: one per world (device); NULL: uniform
+  const WorldRanges* table = nullptr;     // ragged: one per world (device); NULL: uniform
   const uint32_t* tile_base = nullptr;   // ragged: [n_worlds + 1], the first tile of every world's addressed segment and the total
   const float* limit2 = nullptr;         // [n_worlds] (device) or NULL: limit_all in every world
   float limit_all = 0.0f;

@@ -36,7 +36,8 @@ struct EncounterSeg {
   uint32_t n_src, n_tgt;
 };
 
-// A world's sources and addressed targets: from the table (ragged) or from its index (uniform).
+// A world's sources and addressed targets: from the table (ragged) or from its index (uniform).  Both from one load of the
+// record: world_segment (ensemble_rows.h) once per kind would load it twice.
 __device__ __forceinline__ void encounter_rows(const EncounterArgs& a, uint32_t world, EncounterSeg& s) {
   if (a.table) {
     const uint4 w = reinterpret_cast<const uint4*>(a.table)[world];
@@ -58,14 +59,9 @@ __device__ __forceinline__ EncounterSeg encounter_item(const EncounterArgs& a, u
   if (!a.table) {
     s.world = (uint32_t)(item / a.tiles);
     s.tile = (uint32_t)(item - (uint64_t)s.world * a.tiles);
-  } else {  // the last world whose first tile is not past the item (a world without tiles shares its base with the next: skipped)
-    uint32_t lo = 0, hi = a.n_worlds - 1;
-    while (lo < hi) {
-      const uint32_t mid = lo + (hi - lo + 1) / 2;
-      if (a.tile_base[mid] <= item) lo = mid; else hi = mid - 1;
-    }
-    s.world = lo;
-    s.tile = (uint32_t)(item - a.tile_base[lo]);
+  } else {  // (a world without tiles shares its base with the next: skipped)
+    s.world = world_of_item(a.tile_base, a.n_worlds, item);
+    s.tile = (uint32_t)(item - a.tile_base[s.world]);
   }
   encounter_rows(a, s.world, s);
   return s;

@@ -5,7 +5,8 @@
 // One kernel text over T (float / double) serves every handle.  What differs between the handles is in FrameArgs:
 //   mass     the f32 handles keep `weight as f32`, the f64 handles the u32 weights; frame_heavy() below is one predicate on both;
 //   rows     a uniform handle (n_bodies, n_tracers the same in every world) computes a world's row ranges from its index; a
-//            ragged one reads them from `table`, one FrameWorld per world, which the driver builds from the sizes it holds.
+//            ragged one reads them from `table`, one WorldRanges per world (ensemble_rows.h), which the driver builds from the
+//            sizes it holds.
 //
 // Two routes, chosen by render_px alone (frame_route_lds):
 //   LDS      render_px^2 * 8 <= 81 920 B (render_px <= 101; 81 920 B is the dynamic LDS the f64 ensemble already raises its
@@ -24,6 +25,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "ensemble_rows.h"
+
 namespace nbody {
 
 constexpr size_t kFrameLdsBytes = 81920;            // = ensemble64_lds_bytes(kEnsembleMaxBodies): what ens64_raise_lds_limit raises a kernel to
@@ -33,18 +36,13 @@ constexpr uint32_t kFrameMaxHeight = 1u << 24;      // `height as T` exact in f3
 
 inline bool frame_route_lds(uint32_t render_px) { return (size_t)render_px * render_px * 8 <= kFrameLdsBytes; }
 
-struct FrameWorld {  // a ragged world's rows (16 bytes: the device reads it as one uint4)
-  uint32_t row0, n;  // bodies: rows [row0, row0 + n) of pos / vel / mass
-  uint32_t trow0, m; // tracers: rows [trow0, trow0 + m) of tpos / tvel; m == 0: none
-};
-
 struct FrameArgs {
   const void* pos = nullptr;    // T2 rows of all worlds (the handle's current buffer)
   const void* vel = nullptr;
   const void* mass = nullptr;   // float rows (T = float) or uint32_t rows (T = double)
   const void* tpos = nullptr;   // tracers, or NULL: bodies only
   const void* tvel = nullptr;
-  const FrameWorld* table = nullptr;  // ragged: one per world (device); NULL: uniform
+  const WorldRanges* table = nullptr;  // ragged: one per world (device); NULL: uniform
   uint32_t n_bodies = 0, n_tracers = 0;  // uniform: per world
   uint32_t chunks = 0;          // global route: 256-row chunks per world, of the largest world (set by the launch)
   uint32_t height = 0, render_px = 0;

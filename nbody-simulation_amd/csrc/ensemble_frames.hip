@@ -34,17 +34,17 @@ __device__ __forceinline__ bool frame_heavy(uint32_t weight) { return weight > 1
 __device__ __forceinline__ bool frame_heavy(float mass) { return mass > 10.0f; }
 
 // A world's rows: from the table (ragged) or from its index (uniform).  The same in every lane of a block.
-__device__ __forceinline__ FrameWorld frame_world(const FrameArgs& a, uint32_t world) {
+__device__ __forceinline__ WorldRanges frame_world(const FrameArgs& a, uint32_t world) {
   if (a.table) {
     const uint4 w = reinterpret_cast<const uint4*>(a.table)[world];
-    return FrameWorld{w.x, w.y, w.z, a.tpos ? w.w : 0u};  // (the table keeps the counts; the call says whether they are painted)
+    return WorldRanges{w.x, w.y, w.z, a.tpos ? w.w : 0u};  // (the table keeps the counts; the call says whether they are painted)
   }
-  return FrameWorld{world * a.n_bodies, a.n_bodies, world * a.n_tracers, a.tpos ? a.n_tracers : 0u};  // (rows of all worlds <= 2^26)
+  return WorldRanges{world * a.n_bodies, a.n_bodies, world * a.n_tracers, a.tpos ? a.n_tracers : 0u};  // (rows of all worlds <= 2^26)
 }
 
 // Row r of the world (r < w.n + w.m) splatted into the world's words.  The atomics' results are unused.
 template <class T>
-__device__ __forceinline__ void frame_splat_row(const FrameArgs& a, const FrameWorld& w, uint32_t r, T height, uint32_t cell,
+__device__ __forceinline__ void frame_splat_row(const FrameArgs& a, const WorldRanges& w, uint32_t r, T height, uint32_t cell,
                                                 uint32_t* count, uint32_t* last) {
   using T2 = typename FrameTypes<T>::Vec2;
   using Mass = typename FrameTypes<T>::Mass;
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(kFrameBlock) void ensemble_frames_lds(const FrameAr
   const uint32_t npix = a.render_px * a.render_px, cell = a.height / a.render_px;
   uint32_t* const count = frame_lds;
   uint32_t* const last = frame_lds + npix;
-  const FrameWorld w = frame_world(a, blockIdx.x);
+  const WorldRanges w = frame_world(a, blockIdx.x);
   for (uint32_t i = threadIdx.x; i < 2 * npix; i += kFrameBlock) frame_lds[i] = 0u;
   __syncthreads();
   const uint32_t rows = w.n + w.m;  // bodies first, then tracers: one loop, the rows in order of their index
@@ -96,7 +96,7 @@ template <class T>
 __global__ __launch_bounds__(kFrameBlock) void ensemble_frames_splat(const FrameArgs a, uint32_t* __restrict__ work) {
   const uint32_t npix = a.render_px * a.render_px, cell = a.height / a.render_px;
   const uint32_t world = blockIdx.x / a.chunks, chunk = blockIdx.x - world * a.chunks;
-  const FrameWorld w = frame_world(a, world);
+  const WorldRanges w = frame_world(a, world);
   const uint32_t r = chunk * kFrameBlock + threadIdx.x;
   if (r >= w.n + w.m) return;
   uint32_t* const count = work + (size_t)world * 2 * npix;

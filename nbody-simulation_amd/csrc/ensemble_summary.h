@@ -26,7 +26,7 @@
 #include <limits>
 
 #include "../../include/nbody_hip.h"
-#include "ensemble_frames.h"
+#include "ensemble_rows.h"
 
 namespace nbody {
 
@@ -58,7 +58,7 @@ struct SummaryArgs {
   const void* mass = nullptr;   // float rows (T = float) or uint32_t rows (T = double)
   const void* tpos = nullptr;   // tracers (may be NULL where no world has one)
   const void* tvel = nullptr;
-  const FrameWorld* table = nullptr;      // ragged: one per world (device); NULL: uniform
+  const WorldRanges* table = nullptr;      // ragged: one per world (device); NULL: uniform
   const uint32_t* chunk_base = nullptr;   // ragged, tracers: [n_worlds + 1], the first chunk of every world's tracers and the total
   const int32_t* ref = nullptr;           // [n_worlds] (device) or NULL: no separation
   uint32_t n_bodies = 0, n_tracers = 0;   // uniform: per world

@@ -47,14 +47,7 @@ struct SummarySeg {
 
 // A world's addressed segment: from the table (ragged) or from its index (uniform).
 __device__ __forceinline__ void summary_rows(const SummaryArgs& a, uint32_t world, size_t& row0, uint32_t& n) {
-  if (a.table) {
-    const uint4 w = reinterpret_cast<const uint4*>(a.table)[world];
-    row0 = a.tracers ? w.z : w.x;
-    n = a.tracers ? w.w : w.y;
-  } else {
-    n = a.tracers ? a.n_tracers : a.n_bodies;
-    row0 = (size_t)world * n;  // (rows of all worlds <= 2^26)
-  }
+  world_segment(a.table, a.n_bodies, a.n_tracers, a.tracers, world, row0, n);
 }
 
 // The first chunk record of a world among those of all worlds.
@@ -72,14 +65,9 @@ __device__ __forceinline__ SummarySeg summary_item(const SummaryArgs& a, uint64_
   } else if (!a.chunk_base) {
     s.world = (uint32_t)item;
     s.chunk = 0;
-  } else {  // the last world whose first chunk is not past the item (every world has at least one chunk: the bases ascend strictly)
-    uint32_t lo = 0, hi = a.n_worlds - 1;
-    while (lo < hi) {
-      const uint32_t mid = lo + (hi - lo + 1) / 2;
-      if (a.chunk_base[mid] <= item) lo = mid; else hi = mid - 1;
-    }
-    s.world = lo;
-    s.chunk = (uint32_t)(item - a.chunk_base[lo]);
+  } else {  // (every world has at least one chunk: the bases ascend strictly)
+    s.world = world_of_item(a.chunk_base, a.n_worlds, item);
+    s.chunk = (uint32_t)(item - a.chunk_base[s.world]);
   }
   summary_rows(a, s.world, s.row0, s.n);
   return s;

@@ -34,12 +34,12 @@ NB_API int nbody_ragged64_update(nbody_ragged64* e, double delta, int n_steps, n
 NB_API int nbody_ragged64_accel(nbody_ragged64* e, double* acc_xy) { return ragged_accel<RagF64>(e, acc_xy); }
 // (frames of every world, ensemble_frames.h: a prefix of its own, defined here where the handle is a complete type)
 NB_API int nbody_frames_ragged64(nbody_ragged64* e, uint32_t height, uint32_t render_px, uint8_t* rgba_out) {
-  return ragged_frames<RagF64>(e, height, render_px, rgba_out);
+  return ens_frames<RagF64>(e, height, render_px, rgba_out, ragged_rows<RagF64>(e));
 }
 // (delta streams of every world, ensemble_deltas.h: likewise a prefix of its own)
 NB_API int nbody_deltas_ragged64(nbody_ragged64* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* offsets_out,
                                  uint64_t* step_out) {
-  return ragged_deltas<RagF64>(e, flags, out, cap, bytes_out, offsets_out, step_out);
+  return ens_deltas<RagF64>(e, flags, out, cap, bytes_out, offsets_out, step_out, ragged_rows<RagF64>(e));
 }
 
 NB_API int nbody_ragged64_plan(int64_t n_worlds, const int64_t* n_bodies, int32_t* launch_of_world, int64_t* first_block_of_world,
@@ -55,10 +55,10 @@ NB_API int nbody_sweep_ragged64(nbody_ragged64* e, const double* delta, const fl
 }
 // (a record per world — moments, extent, separations, ensemble_summary.h: likewise a prefix of its own)
 NB_API int nbody_summary_ragged64(nbody_ragged64* e, uint32_t flags, uint32_t height, const int32_t* ref, nbody_world_summary* out) {
-  return ragged_summary<RagF64>(e, flags, height, ref, out);
+  return ens_summary<RagF64>(e, flags, height, ref, out, ragged_rows<RagF64>(e));
 }
 // (nearest neighbours and clamped pairs per world, ensemble_encounters.h: likewise a prefix of its own)
 NB_API int nbody_encounters_ragged64(nbody_ragged64* e, uint32_t flags, const float* limit2, nbody_world_encounters* out, int32_t* nn_index, double* nn_d2,
                                      uint32_t* close) {
-  return ragged_encounters<RagF64>(e, flags, limit2, out, nn_index, nn_d2, close);
+  return ens_encounters<RagF64>(e, flags, limit2, out, nn_index, nn_d2, close, ragged_rows<RagF64>(e));
 }

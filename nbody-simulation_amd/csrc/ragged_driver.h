@@ -85,39 +85,11 @@ template <class P> int ragged_accel(RaggedState<P>* e, typename P::Real* acc_xy)
   return ens_accel_with<P>(e, acc_xy, [e](const typename P::Args& a) { return ragged_launch_all<P>(e, a); });
 }
 
-// Frames: the ensemble's, over the row ranges of these sizes.
-template <class P> int ragged_frames(RaggedState<P>* e, uint32_t height, uint32_t render_px, uint8_t* rgba_out) {
-  if (!e) return NBODY_ERR_INVALID;
-  FrameRows<P> rows;
-  rows.sizes = e->sizes.data();
-  return ens_frames<P>(e, height, render_px, rgba_out, rows);
-}
-
-// Delta streams: the ensemble's, over segments of these sizes.
-template <class P>
-int ragged_deltas(RaggedState<P>* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* offsets_out, uint64_t* step_out) {
-  if (!e) return NBODY_ERR_INVALID;
-  DeltaRows<P> rows;
-  rows.sizes = e->sizes.data();
-  return ens_deltas<P>(e, flags, out, cap, bytes_out, offsets_out, step_out, rows);
-}
-
-// Summaries: the ensemble's, over segments of these sizes.
-template <class P> int ragged_summary(RaggedState<P>* e, uint32_t flags, uint32_t height, const int32_t* ref, nbody_world_summary* out) {
-  if (!e) return NBODY_ERR_INVALID;
-  SummaryRows<P> rows;
-  rows.sizes = e->sizes.data();
-  return ens_summary<P>(e, flags, height, ref, out, rows);
-}
-
-// Encounters: the ensemble's, over segments of these sizes.
-template <class P>
-int ragged_encounters(RaggedState<P>* e, uint32_t flags, const float* limit2, nbody_world_encounters* out, int32_t* nn_index,
-                      typename P::Real* nn_d2, uint32_t* close) {
-  if (!e) return NBODY_ERR_INVALID;
-  EncounterRows<P> rows;
-  rows.sizes = e->sizes.data();
-  return ens_encounters<P>(e, flags, limit2, out, nn_index, nn_d2, close, rows);
+// Where the handle's rows are, for the observers (ensemble_observers.h); of no handle, nothing (they refuse it).
+template <class P> WorldRows<P> ragged_rows(const RaggedState<P>* e) {
+  WorldRows<P> rows;
+  if (e) rows.sizes = e->sizes.data();
+  return rows;
 }
 
 template <class P> int ragged_sizes(const RaggedState<P>* e, int64_t* n_bodies_out) {

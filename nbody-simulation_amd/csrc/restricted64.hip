@@ -40,12 +40,12 @@ NB_API int nbody_restricted64_accel(nbody_restricted64* e, double* acc_xy) { ret
 NB_API int nbody_restricted64_tracers_accel(nbody_restricted64* e, double* acc_xy) { return rst_tracers_accel<Rst64>(e, acc_xy); }
 // (frames of every world, ensemble_frames.h: a prefix of its own, defined here where the handle is a complete type)
 NB_API int nbody_frames_restricted64(nbody_restricted64* e, uint32_t height, uint32_t render_px, int with_tracers, uint8_t* rgba_out) {
-  return rst_frames<Rst64>(e, height, render_px, with_tracers, rgba_out);
+  return ens_frames<Rst64>(e, height, render_px, rgba_out, rst_rows<Rst64>(e), with_tracers != 0);
 }
 // (delta streams of every world, ensemble_deltas.h: likewise a prefix of its own)
 NB_API int nbody_deltas_restricted64(nbody_restricted64* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out,
                                      uint64_t* offsets_out, uint64_t* step_out) {
-  return rst_deltas<Rst64>(e, flags, out, cap, bytes_out, offsets_out, step_out);
+  return ens_deltas<Rst64>(e, flags, out, cap, bytes_out, offsets_out, step_out, rst_rows<Rst64>(e));
 }
 // (a sweep — a time step, a clamp and a number of steps per world, include/nbody_ensemble.h: likewise a prefix of its own)
 NB_API int nbody_sweep_restricted64(nbody_restricted64* e, const double* delta, const float* clamp, const int32_t* steps, int n_steps,
@@ -54,10 +54,10 @@ NB_API int nbody_sweep_restricted64(nbody_restricted64* e, const double* delta, 
 }
 // (a record per world — moments, extent, separations, ensemble_summary.h: likewise a prefix of its own)
 NB_API int nbody_summary_restricted64(nbody_restricted64* e, uint32_t flags, uint32_t height, const int32_t* ref, nbody_world_summary* out) {
-  return rst_summary<Rst64>(e, flags, height, ref, out);
+  return ens_summary<Rst64>(e, flags, height, ref, out, rst_rows<Rst64>(e));
 }
 // (nearest neighbours and clamped pairs per world, ensemble_encounters.h: likewise a prefix of its own)
 NB_API int nbody_encounters_restricted64(nbody_restricted64* e, uint32_t flags, const float* limit2, nbody_world_encounters* out, int32_t* nn_index, double* nn_d2,
                                          uint32_t* close) {
-  return rst_encounters<Rst64>(e, flags, limit2, out, nn_index, nn_d2, close);
+  return ens_encounters<Rst64>(e, flags, limit2, out, nn_index, nn_d2, close, rst_rows<Rst64>(e));
 }

@@ -127,50 +127,17 @@ template <class P> int rst_tracers_accel(RestrictedState<P>* e, typename P::Real
   return NBODY_OK;
 }
 
-// Frames: the ensemble's, with the tracers painted after their world's bodies where they are asked for and there are any.
-template <class P> int rst_frames(RestrictedState<P>* e, uint32_t height, uint32_t render_px, int with_tracers, uint8_t* rgba_out) {
-  if (!e) return NBODY_ERR_INVALID;
-  FrameRows<P> rows;
-  if (with_tracers && e->n_tracers) {
-    rows.n_tracers = e->n_tracers;
-    rows.tpos = e->tpos;
-    rows.tvel = e->tvel;
-  }
-  return ens_frames<P>(e, height, render_px, rgba_out, rows);
-}
-
-// Delta streams: the ensemble's, the bodies' sequence or the tracers' (without tracers: every world's stream is a header of 0 rows).
-template <class P>
-int rst_deltas(RestrictedState<P>* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* offsets_out, uint64_t* step_out) {
-  if (!e) return NBODY_ERR_INVALID;
-  DeltaRows<P> rows;
+// Where the handle's rows are, for the observers (ensemble_observers.h); of no handle, nothing (they refuse it).  Without tracers
+// the tracers' frames are the bodies', every world's tracer stream a header of 0 rows and its tracer records of rows == 0.
+template <class P> WorldRows<P> rst_rows(const RestrictedState<P>* e) {
+  WorldRows<P> rows;
+  rows.has_tracer_calls = true;
+  if (!e) return rows;
   rows.n_tracers = e->n_tracers;
-  rows.tpos = e->tpos;
-  rows.tracer_calls = true;
-  return ens_deltas<P>(e, flags, out, cap, bytes_out, offsets_out, step_out, rows);
-}
-
-// Summaries: the ensemble's, of the bodies or of the tracers (without tracers: every world's record has rows == 0).
-template <class P> int rst_summary(RestrictedState<P>* e, uint32_t flags, uint32_t height, const int32_t* ref, nbody_world_summary* out) {
-  if (!e) return NBODY_ERR_INVALID;
-  SummaryRows<P> rows;
-  rows.n_tracers = e->n_tracers;
+  rows.tracer_rows = e->n_worlds * e->n_tracers;
   rows.tpos = e->tpos;
   rows.tvel = e->tvel;
-  rows.tracer_calls = true;
-  return ens_summary<P>(e, flags, height, ref, out, rows);
-}
-
-// Encounters: the ensemble's, of the bodies or of the tracers against the bodies (without tracers: every world's record has rows == 0).
-template <class P>
-int rst_encounters(RestrictedState<P>* e, uint32_t flags, const float* limit2, nbody_world_encounters* out, int32_t* nn_index,
-                   typename P::Real* nn_d2, uint32_t* close) {
-  if (!e) return NBODY_ERR_INVALID;
-  EncounterRows<P> rows;
-  rows.n_tracers = e->n_tracers;
-  rows.tpos = e->tpos;
-  rows.tracer_calls = true;
-  return ens_encounters<P>(e, flags, limit2, out, nn_index, nn_d2, close, rows);
+  return rows;
 }
 
 template <class P> int64_t rst_num_tracers(const RestrictedState<P>* e) { return e ? e->n_tracers : 0; }

@@ -54,12 +54,12 @@ NB_API int nbody_rr_accel_f32(nbody_rr* e, float* acc_xy) { return rr_accel<RrF3
 NB_API int nbody_rr_tracers_accel_f32(nbody_rr* e, float* acc_xy) { return rr_tracers_accel<RrF32>(e, acc_xy); }
 // (frames of every world, ensemble_frames.h: a prefix of its own, defined here where the handle is a complete type)
 NB_API int nbody_frames_rr(nbody_rr* e, uint32_t height, uint32_t render_px, int with_tracers, uint8_t* rgba_out) {
-  return rr_frames<RrF32>(e, height, render_px, with_tracers, rgba_out);
+  return ens_frames<RrF32>(e, height, render_px, rgba_out, rr_rows<RrF32>(e), with_tracers != 0);
 }
 // (delta streams of every world, ensemble_deltas.h: likewise a prefix of its own)
 NB_API int nbody_deltas_rr(nbody_rr* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* offsets_out,
                            uint64_t* step_out) {
-  return rr_deltas<RrF32>(e, flags, out, cap, bytes_out, offsets_out, step_out);
+  return ens_deltas<RrF32>(e, flags, out, cap, bytes_out, offsets_out, step_out, rr_rows<RrF32>(e));
 }
 
 NB_API int nbody_rr_plan(int64_t n_worlds, const int64_t* n_bodies, const int64_t* n_tracers, int32_t* launch_of_world,
@@ -76,10 +76,10 @@ NB_API int nbody_sweep_rr(nbody_rr* e, const float* delta, const float* clamp, c
 }
 // (a record per world — moments, extent, separations, ensemble_summary.h: likewise a prefix of its own)
 NB_API int nbody_summary_rr(nbody_rr* e, uint32_t flags, uint32_t height, const int32_t* ref, nbody_world_summary* out) {
-  return rr_summary<RrF32>(e, flags, height, ref, out);
+  return ens_summary<RrF32>(e, flags, height, ref, out, rr_rows<RrF32>(e));
 }
 // (nearest neighbours and clamped pairs per world, ensemble_encounters.h: likewise a prefix of its own)
 NB_API int nbody_encounters_rr(nbody_rr* e, uint32_t flags, const float* limit2, nbody_world_encounters* out, int32_t* nn_index, float* nn_d2,
                                uint32_t* close) {
-  return rr_encounters<RrF32>(e, flags, limit2, out, nn_index, nn_d2, close);
+  return ens_encounters<RrF32>(e, flags, limit2, out, nn_index, nn_d2, close, rr_rows<RrF32>(e));
 }

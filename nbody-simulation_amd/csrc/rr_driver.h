@@ -33,8 +33,8 @@ template <class P> struct RrState : RaggedState<P> {
     counts.clear();
     tplan = RrPlan();
     tracer_rows = 0;
-    this->frame_table_valid = false;  // (the frames' table of row ranges holds the counts)
-    this->dtracers.release();         // (the tracers' delta streams start over with the next tracers)
+    this->table.invalidate();  // (the table of row ranges holds the counts)
+    this->dtracers.release();  // (the tracers' delta streams start over with the next tracers)
   }
 };
 
@@ -169,55 +169,19 @@ template <class P> int rr_tracers_accel(RrState<P>* e, typename P::Real* acc_xy)
   return NBODY_OK;
 }
 
-// Frames: the ensemble's, over the row ranges of these sizes and counts; a world without tracers is painted from its bodies.
-template <class P> int rr_frames(RrState<P>* e, uint32_t height, uint32_t render_px, int with_tracers, uint8_t* rgba_out) {
-  if (!e) return NBODY_ERR_INVALID;
-  FrameRows<P> rows;
-  rows.sizes = e->sizes.data();
-  if (e->tracer_rows) rows.counts = e->counts.data();
-  if (with_tracers && e->tracer_rows) {
-    rows.tpos = e->tpos;
-    rows.tvel = e->tvel;
-  }
-  return ens_frames<P>(e, height, render_px, rgba_out, rows);
-}
-
-// Delta streams: the ensemble's, over segments of these sizes or these counts (a world without tracers: a header of 0 rows).
-template <class P>
-int rr_deltas(RrState<P>* e, uint32_t flags, uint8_t* out, size_t cap, size_t* bytes_out, uint64_t* offsets_out, uint64_t* step_out) {
-  if (!e) return NBODY_ERR_INVALID;
-  DeltaRows<P> rows;
-  rows.sizes = e->sizes.data();
-  if (e->tracer_rows) rows.counts = e->counts.data();
-  rows.tpos = e->tpos;
-  rows.tracer_calls = true;
-  return ens_deltas<P>(e, flags, out, cap, bytes_out, offsets_out, step_out, rows);
-}
-
-// Summaries: the ensemble's, over segments of these sizes or these counts (a world without tracers: a record with rows == 0).
-template <class P> int rr_summary(RrState<P>* e, uint32_t flags, uint32_t height, const int32_t* ref, nbody_world_summary* out) {
-  if (!e) return NBODY_ERR_INVALID;
-  SummaryRows<P> rows;
-  rows.sizes = e->sizes.data();
-  if (e->tracer_rows) rows.counts = e->counts.data();
-  rows.tpos = e->tpos;
-  rows.tvel = e->tvel;
-  rows.tracer_calls = true;
-  return ens_summary<P>(e, flags, height, ref, out, rows);
-}
-
-// Encounters: the ensemble's, over segments of these sizes or these counts (a world without tracers: a record with rows == 0).
-template <class P>
-int rr_encounters(RrState<P>* e, uint32_t flags, const float* limit2, nbody_world_encounters* out, int32_t* nn_index, typename P::Real* nn_d2,
-                  uint32_t* close) {
-  if (!e) return NBODY_ERR_INVALID;
-  EncounterRows<P> rows;
+// Where the handle's rows are, for the observers (ensemble_observers.h); of no handle, nothing (they refuse it).  The counts go
+// with the tracers; a world without tracers is painted from its bodies, its tracer stream a header of 0 rows and its tracer
+// records of rows == 0.
+template <class P> WorldRows<P> rr_rows(const RrState<P>* e) {
+  WorldRows<P> rows;
+  rows.has_tracer_calls = true;
+  if (!e) return rows;
   rows.sizes = e->sizes.data();
   if (e->tracer_rows) rows.counts = e->counts.data();
   rows.tracer_rows = e->tracer_rows;
   rows.tpos = e->tpos;
-  rows.tracer_calls = true;
-  return ens_encounters<P>(e, flags, limit2, out, nn_index, nn_d2, close, rows);
+  rows.tvel = e->tvel;
+  return rows;
 }
 
 // The sizes and the tracer counts of every world; either output may be NULL.  Without tracers every count is 0.
