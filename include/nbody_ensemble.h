@@ -735,8 +735,8 @@ int nbody_summary_of_f64(int64_t rows, const double* pos_xy, const double* vel_x
  *     ("ensemble", "ragged", "restricted", "ragged restricted") and naming "encounters": nothing uploaded; out NULL; unknown
  *     flag bits; NBODY_ENCOUNTERS_TRACERS on one of the four handles that have no tracer calls.  A NULL handle gives
  *     NBODY_ERR_INVALID without a message.
- *   Not offered: tracer-tracer pairs; the k nearest for k > 1; the minimum over the steps of a call (that would mean touching
- *     the step kernels); a device-pointer variant; anything for nbody_ctx contexts. */
+ *   Not offered: tracer-tracer pairs; the k nearest for k > 1; a device-pointer variant; anything for nbody_ctx contexts.
+ *     (The minimum over the steps of a call: nbody_watch_* below.) */
 typedef struct nbody_world_encounters { /* 12 fields of 8 bytes, no padding: 96 bytes */
   int64_t rows;          /* targets of the segment: the world's bodies, or its tracers */
   int64_t sources;       /* the world's bodies */
@@ -781,5 +781,135 @@ int nbody_encounters_of_f32(int64_t n_targets, const float* target_xy, int64_t n
 int nbody_encounters_of_f64(int64_t n_targets, const double* target_xy, int64_t n_sources, const double* source_xy, int self,
                             double limit2, nbody_world_encounters* out, int32_t* nn_index /*[n_targets] or NULL*/,
                             double* nn_d2 /*[n_targets] or NULL*/, uint32_t* close /*[n_targets] or NULL*/);
+
+/* ---- a watched run of an ensemble: closest approach, close samples and escape step per target over the steps of a call ----
+ * What a study asks of a run as a whole, for all eight handles above: how close did each tracer get to a body and at which
+ * step, was it captured, when did it leave the frame, did the clamp ever decide a pair.  nbody_encounters_* and nbody_summary_*
+ * answer for the current rows; a loop of update(delta, 1), encounters, download and a fold on the host answers for the run at
+ * several times the run's own cost, with a host synchronisation per step.  A watch is the handle's *_update(delta, n_steps)
+ * with the device sampling every world before, between and after its steps and folding the samples on the device.
+ *   The prefix.  nbody_watch_<handle>: a closed set of eight, under a prefix of its own.
+ *   Samples.  Sample s, 0 <= s <= n_steps, is the state after s steps of this call: the rows an nbody_encounters_* call at that
+ *     point would read (the bodies' current positions, or the tracers').  Sample s is taken when s % stride == 0 (stride >= 1);
+ *     with NBODY_WATCH_RESUME s = 0 is left out, so that a call that continues an earlier one does not look at the boundary
+ *     state twice.  n_steps == 0 is allowed: one sample and no step, or with NBODY_WATCH_RESUME no sample at all.  Sample
+ *     numbers in the outputs are these s — step counts relative to the call — not an index among the taken samples.
+ *   Targets and sources.  As nbody_encounters_* states them: the targets are one world's bodies or, with NBODY_WATCH_TRACERS,
+ *     one world's tracers; the sources are that world's bodies; a body's own row is not a pair.
+ *   Per sample, per target.  (nn_d2, nn_index) of the encounters' contract and nothing else of it, in the same arithmetic word
+ *     for word: the handle's precision T, dx = xj - xi, dy = yj - yi, sum = |dx| + |dy|, d2 = dx*dx + dy*dy, each one IEEE
+ *     operation, nothing fused; a pair is live iff `sum` is a normal number; the lowest source index stands on a tie; the first
+ *     live pair stands even at d2 = +inf.  Derived from them: the target HAS A CLOSE PAIR at s iff nn_index >= 0 and nn_d2 <
+ *     limit2[k] (widened to double on the f64 handles; limit2 == NULL: params.clamp in every world; a NaN or zero limit is
+ *     never close) — the targets with close > 0 in the encounters' report, because a live d2 is never NaN and some pair is
+ *     below the limit exactly when the smallest is.  The target IS OUT at s iff its own position fails within_bounds
+ *     (main.rs:224-226) under `height`: x, y in [0, height); a NaN position is out, and height == 0 makes every row out at the
+ *     first sample.
+ *   Per target over the call.  Arrays of nbody_watch_rows_f32 / _f64, host memory, one entry per target of all worlds, laid
+ *     out as the handle's *_download (for the tracers: *_tracers_download) lays out that segment's rows; `rows` may be NULL
+ *     (records only) and so may each of its arrays.
+ *       min_d2, min_index, min_sample: the sample's (nn_d2, nn_index) with the smallest nn_d2 over the samples at which the
+ *         target had a live pair, and that sample.  A later sample replaces the record on a strict `<` only: the earliest
+ *         sample stands.  The first sample with a live pair stands even at +inf.  A target that never had one: +inf, -1,
+ *         NBODY_WATCH_NEVER.
+ *       first_close: the first sample with a close pair, or NBODY_WATCH_NEVER.  close_samples: how many samples had one.
+ *       first_out: the first sample at which the target was out, or NBODY_WATCH_NEVER (a target that comes back keeps it).
+ *   Per world.  One nbody_world_watch.  samples is the number of samples the call took (a function of n_steps, stride and the
+ *     flags alone, the same in every world, whatever its rows).  min_* is the world's closest approach in the call: the
+ *     smallest min_d2 over its targets that had a live pair; on a tie the earliest sample stands, then the lowest row;
+ *     min_source is that row's min_index, min_d2 the T value widened (exact).  close_rows: targets with any close sample;
+ *     close_row_samples: the sum of close_samples; first_close_sample, first_out_sample: the smallest over the targets;
+ *     out_rows: targets that were out at some sample; isolated_rows: targets that never had a live pair (with samples == 0:
+ *     all of them).
+ *   Order-free.  Every output is an integer count or an extreme under a total order with the tie rules above — (d2, sample,
+ *     row), and the lowest source index within a sample — so the contract is bit for bit, without a tolerance, and the kernels
+ *     are free to cut the sources into chunks and to join in any shape.
+ *   Independence.  A world's record and rows are a function of its own rows, delta, limit2[k], height, stride, n_steps and the
+ *     flags alone: not of the number of worlds, its index, the other worlds, which of the optional arrays were asked for, or
+ *     the launch it falls in on a ragged handle.
+ *   The run is untouched.  After a watch the handle's rows — bodies and tracers, under EXACT, FAST and AUTO — are bit for bit
+ *     those after *_update(delta, n_steps); its step count has advanced by n_steps and its delta-stream sequences are as after
+ *     that update.
+ *   Split over calls.  watch(n1) followed by watch(n2) with NBODY_WATCH_RESUME, n1 % stride == 0, merged as follows with
+ *     the second call's sample numbers shifted by n1 (NBODY_WATCH_NEVER and -1 stay), is watch(n1 + n2) bit for bit.  Per
+ *     target: the second call's (min_d2, min_index, min_sample) replaces the first's iff the second has min_index >= 0 and
+ *     the first has min_index < 0 or the second's min_d2 is strictly smaller; first_close and first_out are the first call's
+ *     unless it has NBODY_WATCH_NEVER; close_samples add.  Per world: rows and sources stay, samples, close_row_samples add;
+ *     min_* is recomputed from the merged rows under (d2, sample, row), close_rows, out_rows and isolated_rows are counted
+ *     over them, the two first_*_sample are their minima.  (The records alone do not merge: close_rows is a count of a union.)
+ *   Calls.  Synchronous, on the handle's stream.  One sampling launch per taken sample, whatever the number of worlds or their
+ *     sizes — the encounters' pair launch with a leaner pair — between the handle's own step launches (1, 2, at most
+ *     NBODY_RAGGED_MAX_LAUNCHES or at most NBODY_RR_MAX_LAUNCHES per step), and one reduce launch at the end that makes the
+ *     records.  Nothing is read back and there is no host synchronisation before the end of the call; no floating-point
+ *     atomics; the first taken sample writes the running rows, so no pass clears them and stale scratch is never read.  The
+ *     device scratch belongs to the handle, is grown on demand and is freed with its other arrays.  The call's seconds are
+ *     booked under sum_gravity, as an update's are (`counter` may be NULL).  out: host memory, one record per world.
+ *   Refusals.  NBODY_ERR_INVALID before anything is allocated or enqueued, the message beginning with the handle's word
+ *     ("ensemble", "ragged", "restricted", "ragged restricted") and naming "watch": nothing uploaded; out NULL; unknown flag
+ *     bits; NBODY_WATCH_TRACERS on one of the four handles that have no tracer calls; n_steps < 0; stride < 1; height > 2^24.
+ *     A NULL handle gives NBODY_ERR_INVALID without a message.  NBODY_WATCH_TRACERS on a restricted handle that holds no
+ *     tracers, or for a world of an nbody_rr handle without them, gives rows == 0 records: zero counts, -1 indices and sample
+ *     numbers, min_d2 = +inf (the steps are taken all the same).
+ *   Not offered: a watched sweep with a delta, a clamp or a number of steps per world (the driver takes the step's launch as a
+ *     callable, so it can come later); tracer-tracer pairs; the k nearest for k > 1; a per-sample history; a device-pointer
+ *     variant; anything for nbody_ctx contexts. */
+typedef struct nbody_world_watch { /* 13 fields of 8 bytes, no padding: 104 bytes */
+  int64_t rows;               /* targets of the segment: the world's bodies, or its tracers */
+  int64_t sources;            /* the world's bodies */
+  int64_t samples;            /* samples the call took */
+  int64_t min_row, min_source, min_sample; /* the closest approach of the call; -1, -1, -1 where the world has none */
+  double min_d2;              /* its d2, widened; +inf where there is none */
+  int64_t close_rows;         /* targets with a close pair at some sample */
+  int64_t close_row_samples;  /* (target, sample) combinations with a close pair */
+  int64_t first_close_sample; /* the first sample at which some target had a close pair; -1 where none */
+  int64_t out_rows;           /* targets that were out at some sample */
+  int64_t first_out_sample;   /* the first sample at which some target was out; -1 where none */
+  int64_t isolated_rows;      /* targets that never had a live pair */
+} nbody_world_watch;
+#define NBODY_WATCH_TRACERS 1u         /* targets are the world's tracers, sources its bodies */
+#define NBODY_WATCH_RESUME 2u          /* the call continues an earlier one: sample 0 is left out */
+#define NBODY_WATCH_NEVER 0xffffffffu  /* a sample number that did not occur */
+typedef struct nbody_watch_rows_f32 { /* per target of all worlds; each may be NULL */
+  float* min_d2;
+  int32_t* min_index;
+  uint32_t *min_sample, *first_close, *close_samples, *first_out;
+} nbody_watch_rows_f32;
+typedef struct nbody_watch_rows_f64 {
+  double* min_d2;
+  int32_t* min_index;
+  uint32_t *min_sample, *first_close, *close_samples, *first_out;
+} nbody_watch_rows_f64;
+int nbody_watch_ensemble(nbody_ensemble* e, uint32_t flags, float delta, int n_steps, int stride,
+                         const float* limit2 /*[n_worlds] or NULL: params.clamp*/, uint32_t height,
+                         nbody_world_watch* out /*[n_worlds]*/, const nbody_watch_rows_f32* rows /*NULL: records only*/,
+                         nbody_counting* counter);
+int nbody_watch_ensemble64(nbody_ensemble64* e, uint32_t flags, double delta, int n_steps, int stride,
+                           const float* limit2 /*[n_worlds] or NULL: params.clamp*/, uint32_t height,
+                           nbody_world_watch* out /*[n_worlds]*/, const nbody_watch_rows_f64* rows /*NULL: records only*/,
+                           nbody_counting* counter);
+int nbody_watch_ragged(nbody_ragged* e, uint32_t flags, float delta, int n_steps, int stride,
+                       const float* limit2 /*[n_worlds] or NULL: params.clamp*/, uint32_t height,
+                       nbody_world_watch* out /*[n_worlds]*/, const nbody_watch_rows_f32* rows /*NULL: records only*/,
+                       nbody_counting* counter);
+int nbody_watch_ragged64(nbody_ragged64* e, uint32_t flags, double delta, int n_steps, int stride,
+                         const float* limit2 /*[n_worlds] or NULL: params.clamp*/, uint32_t height,
+                         nbody_world_watch* out /*[n_worlds]*/, const nbody_watch_rows_f64* rows /*NULL: records only*/,
+                         nbody_counting* counter);
+int nbody_watch_restricted(nbody_restricted* e, uint32_t flags, float delta, int n_steps, int stride,
+                           const float* limit2 /*[n_worlds] or NULL: params.clamp*/, uint32_t height,
+                           nbody_world_watch* out /*[n_worlds]*/, const nbody_watch_rows_f32* rows /*NULL: records only*/,
+                           nbody_counting* counter);
+int nbody_watch_restricted64(nbody_restricted64* e, uint32_t flags, double delta, int n_steps, int stride,
+                             const float* limit2 /*[n_worlds] or NULL: params.clamp*/, uint32_t height,
+                             nbody_world_watch* out /*[n_worlds]*/, const nbody_watch_rows_f64* rows /*NULL: records only*/,
+                             nbody_counting* counter);
+int nbody_watch_rr(nbody_rr* e, uint32_t flags, float delta, int n_steps, int stride,
+                   const float* limit2 /*[n_worlds] or NULL: params.clamp*/, uint32_t height,
+                   nbody_world_watch* out /*[n_worlds]*/, const nbody_watch_rows_f32* rows /*NULL: records only*/,
+                   nbody_counting* counter);
+int nbody_watch_rr64(nbody_rr64* e, uint32_t flags, double delta, int n_steps, int stride,
+                     const float* limit2 /*[n_worlds] or NULL: params.clamp*/, uint32_t height,
+                     nbody_world_watch* out /*[n_worlds]*/, const nbody_watch_rows_f64* rows /*NULL: records only*/,
+                     nbody_counting* counter);
 
 #endif /* NBODY_ENSEMBLE_H */

@@ -29,6 +29,14 @@ ENCOUNTERS_TRACERS = 1              # NBODY_ENCOUNTERS_TRACERS: the flag of nbod
 ENCOUNTERS_DTYPE = np.dtype([(name, np.int64) for name in ("rows", "sources", "live_pairs", "skipped_pairs", "close_pairs", "close_rows",
                                                            "isolated_rows", "min_row", "min_source")] +
                             [("min_d2", np.float64), ("max_nn_row", np.int64), ("max_nn_d2", np.float64)])
+WATCH_TRACERS, WATCH_RESUME = 1, 2   # NBODY_WATCH_*: the flags of nbody_watch_<handle>
+WATCH_NEVER = 0xffffffff             # NBODY_WATCH_NEVER: a sample number that did not occur
+# nbody_world_watch of include/nbody_ensemble.h: 13 fields of 8 bytes, no padding
+WATCH_DTYPE = np.dtype([(name, np.int64) for name in ("rows", "sources", "samples", "min_row", "min_source", "min_sample")] +
+                       [("min_d2", np.float64)] +
+                       [(name, np.int64) for name in ("close_rows", "close_row_samples", "first_close_sample", "out_rows",
+                                                      "first_out_sample", "isolated_rows")])
+WATCH_ROWS = ("min_d2", "min_index", "min_sample", "first_close", "close_samples", "first_out")   # nbody_watch_rows_*, in order
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_DEGENERATE, ERR_NOMEM = 0, -1, -2, -3, -4, -5
 ARITH_AUTO, ARITH_FAST, ARITH_EXACT = 0, 1, 2
 ORDER_AS_WRITTEN, ORDER_CONSISTENT = 0, 1
@@ -51,6 +59,11 @@ class Params(C.Structure):
     _fields_ = [("theta", C.c_float), ("clamp", C.c_float), ("leaf_size", C.c_int32), ("order", C.c_int32),
                 ("arith", C.c_int32), ("quad_root_x", C.c_float), ("quad_root_y", C.c_float),
                 ("quad_root_h", C.c_float)]
+
+
+class WatchRows(C.Structure):
+    """`nbody_watch_rows_f32` / `_f64`: six pointers, the first to the handle's precision; each may be NULL."""
+    _fields_ = [(name, C.c_void_p) for name in ("min_d2", "min_index", "min_sample", "first_close", "close_samples", "first_out")]
 
 
 class TreeView(C.Structure):
@@ -237,6 +250,11 @@ _SIGS = {
        for h in ("ensemble", "ensemble64", "ragged", "ragged64", "restricted", "restricted64", "rr", "rr64")},
     "nbody_encounters_of_f32": (C.c_int, [_i64, _vp, _i64, _vp, _i32, _f32, _vp, _vp, _vp, _vp]),
     "nbody_encounters_of_f64": (C.c_int, [_i64, _vp, _i64, _vp, _i32, _f64, _vp, _vp, _vp, _vp]),
+    # nbody_watch_<handle>: flags, delta in the handle's precision, n_steps, stride, limit2 float32[n_worlds] or NULL, height,
+    # out nbody_world_watch[n_worlds] (WATCH_DTYPE), rows nbody_watch_rows_* (WatchRows) or NULL, counter
+    **{"nbody_watch_" + h: (C.c_int, [_vp, C.c_uint32, _f64 if h.endswith("64") else _f32, _i32, _i32, C.POINTER(_f32), C.c_uint32, _vp,
+                                      C.POINTER(WatchRows), C.POINTER(Counting)])
+       for h in ("ensemble", "ensemble64", "ragged", "ragged64", "restricted", "restricted64", "rr", "rr64")},
     "nbody_accel_tree_f32": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_accel_tree_f64": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_tree_info": (C.c_int, [_vp, C.POINTER(TreeView)]),
@@ -1061,8 +1079,27 @@ class _EnsembleHandleBase:
                                             _ptr(index), _ptr(d2), _ptr(close)))
         return out, index, d2, close
 
+    def watch(self, delta, n_steps, stride, limit2, height, tracers=False, resume=False, rows=True, counter: "Counting | None" = None):
+        """nbody_watch_<handle>: update(delta, n_steps) with every world sampled before, between and after the steps (every
+        `stride`-th sample; resume=True: not sample 0) -> (WATCH_DTYPE[worlds], dict of the six per-target arrays of WATCH_ROWS,
+        flat in the download's order — min_d2 of the handle's dtype, min_index int32, the rest uint32 — or None with rows=False).
+        limit2: float32[worlds], contiguous, or None (ensemble.py's `watch` checks and casts the arguments)."""
+        out = np.zeros(self.shape[0], WATCH_DTYPE)
+        arrays, block = None, None
+        if rows:
+            total = int(self._delta_rows(tracers).sum())
+            arrays = {name: np.zeros(total, self._dtype if name == "min_d2" else np.int32 if name == "min_index" else np.uint32)
+                      for name in WATCH_ROWS}
+            block = WatchRows(*[a.ctypes.data for a in arrays.values()])
+        name = "nbody_watch_" + self._prefix[len("nbody_"):]
+        self._check(getattr(self.lib, name)(self.h, (WATCH_TRACERS if tracers else 0) | (WATCH_RESUME if resume else 0), float(delta),
+                                            int(n_steps), int(stride), None if limit2 is None else limit2.ctypes.data_as(C.POINTER(C.c_float)),
+                                            int(height), _ptr(out), C.byref(block) if block is not None else None,
+                                            C.byref(counter) if counter is not None else None))
+        return out, arrays
+
     def _delta_rows(self, tracers):
-        """The rows of every segment a deltas() or encounters() call addresses, int64[worlds]."""
+        """The rows of every segment a deltas(), encounters() or watch() call addresses, int64[worlds]."""
         b, n = self.shape
         return np.full(b, getattr(self, "n_tracers", 0) if tracers else n, np.int64)
 

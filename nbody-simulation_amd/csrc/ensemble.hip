@@ -45,3 +45,9 @@ NB_API int nbody_encounters_ensemble(nbody_ensemble* e, uint32_t flags, const fl
                                      uint32_t* close) {
   return ens_encounters<EnsF32>(e, flags, limit2, out, nn_index, nn_d2, close);
 }
+// (an update sampled before, between and after its steps, ensemble_watch.h: likewise a prefix of its own)
+NB_API int nbody_watch_ensemble(nbody_ensemble* e, uint32_t flags, float delta, int n_steps, int stride, const float* limit2, uint32_t height,
+                                nbody_world_watch* out, const nbody_watch_rows_f32* rows, nbody_counting* counter) {
+  return ens_watch_with<EnsF32>(e, flags, delta, n_steps, stride, limit2, height, out, rows, counter, WorldRows<EnsF32>(),
+                                [e](const EnsF32::Args& a) { return EnsF32::launch(e->stream, e->n_worlds, a); });
+}

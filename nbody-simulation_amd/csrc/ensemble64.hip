@@ -45,3 +45,9 @@ NB_API int nbody_encounters_ensemble64(nbody_ensemble64* e, uint32_t flags, cons
                                        uint32_t* close) {
   return ens_encounters<EnsF64>(e, flags, limit2, out, nn_index, nn_d2, close);
 }
+// (an update sampled before, between and after its steps, ensemble_watch.h: likewise a prefix of its own)
+NB_API int nbody_watch_ensemble64(nbody_ensemble64* e, uint32_t flags, double delta, int n_steps, int stride, const float* limit2, uint32_t height,
+                                  nbody_world_watch* out, const nbody_watch_rows_f64* rows, nbody_counting* counter) {
+  return ens_watch_with<EnsF64>(e, flags, delta, n_steps, stride, limit2, height, out, rows, counter, WorldRows<EnsF64>(),
+                                [e](const EnsF64::Args& a) { return EnsF64::launch(e->stream, e->n_worlds, a); });
+}

@@ -21,7 +21,7 @@
 // This file: the state (with the scratch of every call, each a DevBuf grown on demand and freed with the rows), create /
 // destroy, params, upload / download, and the stepping calls: update, sweep (nbody_sweep_*: a time step, a clamp and a number of
 // steps per world) and accel.  The calls that read every world's current rows and return something per world — frames, delta
-// streams, summaries, encounters — are ensemble_observers.h, included at the end: one function each for every handle, told where
+// streams, summaries, encounters — and the watched run are ensemble_observers.h, included at the end: one function each for every handle, told where
 // the handle's rows are by one WorldRows.
 #pragma once
 #include <cstring>
@@ -133,6 +133,12 @@ template <class P> struct EnsembleState {
   DevBuf<typename P::Real> enc_d2;
   DevBuf<uint32_t> enc_close, enc_live;
   DevBuf<float> enc_limit;
+  // a watched run (ens_watch_with): the records, the six running rows per target and the call's limit2[]
+  DevBuf<nbody_world_watch> watch_out;
+  DevBuf<typename P::Real> watch_d2;
+  DevBuf<int32_t> watch_index;
+  DevBuf<uint32_t> watch_sample, watch_first_close, watch_close_samples, watch_first_out;
+  DevBuf<float> watch_limit;
 };
 
 template <class P> thread_local std::string g_ens_create_error;  // one per precision: what a failed create left for its thread
@@ -166,6 +172,8 @@ template <class P> void ens_free(EnsembleState<P>* e) {
   e->sweep_dev.release();
   e->summary_out.release(); e->summary_chunks.release(); e->summary_ref.release();
   e->enc_out.release(); e->enc_index.release(); e->enc_d2.release(); e->enc_close.release(); e->enc_live.release(); e->enc_limit.release();
+  e->watch_out.release(); e->watch_d2.release(); e->watch_index.release(); e->watch_sample.release(); e->watch_first_close.release();
+  e->watch_close_samples.release(); e->watch_first_out.release(); e->watch_limit.release();
   e->dbodies.release();
   e->dtracers.release();
   e->n_worlds = e->n_bodies = e->rows = 0;
@@ -305,6 +313,20 @@ template <class P> int ens_download(EnsembleState<P>* e, typename P::Real* pos, 
   return NBODY_OK;
 }
 
+// One step by `delta` enqueued through `launch(args)`: what an update and a watched run (ens_watch_with, ensemble_observers.h)
+// do per step.
+template <class P, class Launch> hipError_t ens_enqueue_step(EnsembleState<P>* e, typename P::Real delta, Launch& launch) {
+  typename P::Args a = ens_args(e);
+  a.pos_out = e->pos[1 - e->cur];
+  a.vel = e->vel;
+  a.delta = delta;
+  const hipError_t h = launch(a);
+  if (h != hipSuccess) return h;
+  e->cur = 1 - e->cur;  // (the launches are in stream order: the next one reads what this one writes)
+  ++e->updates;
+  return hipSuccess;
+}
+
 // n_steps steps; `launch(args)` enqueues one step (or one force evaluation) of every world on e->stream and returns a hipError_t.
 template <class P, class Launch>
 int ens_update_with(EnsembleState<P>* e, typename P::Real delta, int n_steps, nbody_counting* counter, Launch launch) {
@@ -314,15 +336,7 @@ int ens_update_with(EnsembleState<P>* e, typename P::Real delta, int n_steps, nb
   if (n_steps == 0) return NBODY_OK;
   ENS_HIPCHK(e, hipSetDevice(e->device));
   const double t_begin = now_s();
-  for (int step = 0; step < n_steps; ++step) {
-    typename P::Args a = ens_args(e);
-    a.pos_out = e->pos[1 - e->cur];
-    a.vel = e->vel;
-    a.delta = delta;
-    ENS_HIPCHK(e, launch(a));
-    e->cur = 1 - e->cur;  // (the launches are in stream order: the next one reads what this one writes)
-    ++e->updates;
-  }
+  for (int step = 0; step < n_steps; ++step) ENS_HIPCHK(e, ens_enqueue_step(e, delta, launch));
   ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
   // force and integration are one fused kernel: the whole call is booked under sum_gravity, as the direct step books it
   const double dt = now_s() - t_begin;
@@ -406,4 +420,4 @@ template <class P> int ens_accel(EnsembleState<P>* e, typename P::Real* acc_xy) 
 
 }  // namespace nbody
 
-#include "ensemble_observers.h"  // (frames, delta streams, summaries and encounters of the state above)
+#include "ensemble_observers.h"  // (frames, delta streams, summaries, encounters and the watched run of the state above)

@@ -18,61 +18,12 @@
 #include <stdint.h>
 
 #include "driver.h"
+#include "ensemble_encounter_device.h"
 #include "ensemble_encounters.h"
 
 namespace nbody {
 
 namespace {
-
-template <class T> struct EncounterTypes;
-template <> struct EncounterTypes<float> { using Vec2 = float2; };
-template <> struct EncounterTypes<double> { using Vec2 = double2; };
-
-constexpr uint32_t kEncounterMaxGrid = 1u << 20;
-
-struct EncounterSeg {
-  uint32_t world, tile;  // the work item
-  size_t src0, tgt0;     // the first source row in pos, the first target row in the targets' array and in the per-row outputs
-  uint32_t n_src, n_tgt;
-};
-
-// A world's sources and addressed targets: from the table (ragged) or from its index (uniform).  Both from one load of the
-// record: world_segment (ensemble_rows.h) once per kind would load it twice.
-__device__ __forceinline__ void encounter_rows(const EncounterArgs& a, uint32_t world, EncounterSeg& s) {
-  if (a.table) {
-    const uint4 w = reinterpret_cast<const uint4*>(a.table)[world];
-    s.src0 = w.x;
-    s.n_src = w.y;
-    s.tgt0 = a.tracers ? w.z : w.x;
-    s.n_tgt = a.tracers ? w.w : w.y;
-  } else {
-    s.n_src = a.n_bodies;
-    s.src0 = (size_t)world * a.n_bodies;  // (rows of all worlds <= 2^26)
-    s.n_tgt = a.tracers ? a.n_tracers : a.n_bodies;
-    s.tgt0 = (size_t)world * s.n_tgt;
-  }
-}
-
-// Work item -> (world, tile).  The same in every lane of a block.
-__device__ __forceinline__ EncounterSeg encounter_item(const EncounterArgs& a, uint64_t item) {
-  EncounterSeg s;
-  if (!a.table) {
-    s.world = (uint32_t)(item / a.tiles);
-    s.tile = (uint32_t)(item - (uint64_t)s.world * a.tiles);
-  } else {  // (a world without tiles shares its base with the next: skipped)
-    s.world = world_of_item(a.tile_base, a.n_worlds, item);
-    s.tile = (uint32_t)(item - a.tile_base[s.world]);
-  }
-  encounter_rows(a, s.world, s);
-  return s;
-}
-
-template <class T> __device__ __forceinline__ T encounter_limit(const EncounterArgs& a, uint32_t world) {
-  return (T)(a.limit2 ? a.limit2[world] : a.limit_all);  // (widened on the f64 handles, as a step widens its clamp)
-}
-
-__device__ __forceinline__ float encounter_abs(float v) { return __builtin_fabsf(v); }
-__device__ __forceinline__ double encounter_abs(double v) { return __builtin_fabs(v); }
 
 // One (target, source) pair by the contract: j ascends from call to call.
 template <class T>
@@ -97,7 +48,6 @@ __global__ __launch_bounds__(kEncounterBlock) void ensemble_encounter_pairs(cons
   const uint32_t l = threadIdx.x;
   const T2* const pos = reinterpret_cast<const T2*>(a.pos);
   const T2* const targets = a.tracers ? reinterpret_cast<const T2*>(a.tpos) : pos;
-  const T nan = (T)__builtin_nanf("");
 
   for (uint64_t item = blockIdx.x; item < n_items; item += gridDim.x) {
     const EncounterSeg s = encounter_item(a, item);
@@ -116,14 +66,9 @@ __global__ __launch_bounds__(kEncounterBlock) void ensemble_encounter_pairs(cons
     uint32_t live = 0, near = 0;
     for (uint32_t c0 = 0; c0 < s.n_src; c0 += (uint32_t)kEncounterChunk) {
       __syncthreads();  // (every lane is done with the chunk before, or with the item before)
-#pragma unroll
-      for (int k = 0; k < kEncounterChunk / kEncounterBlock; ++k) {
-        const uint32_t slot = l + (uint32_t)kEncounterBlock * k, j = c0 + slot;
-        staged[slot] = j < s.n_src ? pos[s.src0 + j] : T2{nan, nan};
-      }
+      encounter_stage<T, kEncounterBlock>(staged, pos, s, c0, l);
       __syncthreads();
-      const uint32_t left = s.n_src - c0;
-      const uint32_t count = !valid ? 0u : left < (uint32_t)kEncounterChunk ? (left + 3u) & ~3u : (uint32_t)kEncounterChunk;  // whole groups of four
+      const uint32_t count = valid ? encounter_chunk_count(s, c0) : 0u;  // whole groups of four
       for (uint32_t jj = 0; jj < count; jj += 4) {
         const uint32_t j = c0 + jj;
         if constexpr (sizeof(T) == 4) {

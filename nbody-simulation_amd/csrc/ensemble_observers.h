@@ -5,17 +5,21 @@
 //   ens_summary     nbody_summary_*     one nbody_world_summary per world                  (ensemble_summary.h)
 //   ens_encounters  nbody_encounters_*  nearest neighbours and clamped pairs per world     (ensemble_encounters.h)
 // Each is synchronous on the handle's stream, writes no simulation state, refuses before it allocates or launches anything, and
-// keeps its device scratch in the state.  What differs between the handles is where their rows are: one WorldRows, which the
+// keeps its device scratch in the state.  And the one call that observes while it steps:
+//   ens_watch_with  nbody_watch_*       an update sampled before, between and after its steps    (ensemble_watch.h)  What differs between the handles is where their rows are: one WorldRows, which the
 // ragged, restricted and ragged restricted drivers each make in one function (ragged_rows, rst_rows, rr_rows).  What a call
 // wants of those rows — the bodies or the tracers, the tracers painted or not — is the call's own argument.
 #pragma once
 #include <algorithm>
+#include <limits>
 #include <type_traits>
 
 #include "ensemble_driver.h"
 #include "ensemble_encounters.h"
 #include "ensemble_frames.h"
 #include "ensemble_summary.h"
+#include "ensemble_watch.h"
+#include "env.h"
 
 namespace nbody {
 
@@ -359,6 +363,115 @@ int ens_encounters(EnsembleState<P>* e, uint32_t flags, const float* limit2, nbo
   if (t && nn_d2) ENS_HIPCHK(e, hipMemcpyAsync(nn_d2, e->enc_d2.p, t * sizeof(Real), hipMemcpyDeviceToHost, e->stream));
   if (t && close) ENS_HIPCHK(e, hipMemcpyAsync(close, e->enc_close.p, t * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
   ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
+  return NBODY_OK;
+}
+
+// ---- a watched run: an update whose samples — before, between and after its steps — are folded on the device into six values
+// per target and one nbody_world_watch per world (ensemble_watch.h), into host memory
+// The per-target outputs of the call in the handle's precision: nbody_watch_rows_f32 or nbody_watch_rows_f64.
+template <class Real> struct WatchRowsOf { using type = nbody_watch_rows_f32; };
+template <> struct WatchRowsOf<double> { using type = nbody_watch_rows_f64; };
+
+// out: [n_worlds] records; out_rows: NULL or the six arrays, each NULL or one entry per target of all worlds.  `launch(args)` as
+// in ens_update_with, and the steps are enqueued as it enqueues them: the run is an update's, bit for bit.  One sampling launch
+// per taken sample, one reduce at the end, one synchronise; no loop over worlds but, once per upload, a ragged handle's table.
+template <class P, class Launch>
+int ens_watch_with(EnsembleState<P>* e, uint32_t flags, typename P::Real delta, int n_steps, int stride, const float* limit2, uint32_t height,
+                   nbody_world_watch* out, const typename WatchRowsOf<typename P::Real>::type* out_rows, nbody_counting* counter,
+                   const WorldRows<P>& rows, Launch launch) {
+  using Real = typename P::Real;
+  if (!e) return NBODY_ERR_INVALID;
+  const std::string who = std::string(P::kWho) + " watch: ";
+  if (!e->n_worlds) return ens_fail(e, NBODY_ERR_INVALID, who + "nothing uploaded");
+  if (!out) return ens_fail(e, NBODY_ERR_INVALID, who + "out is NULL");
+  if (flags & ~(NBODY_WATCH_TRACERS | NBODY_WATCH_RESUME)) return ens_fail(e, NBODY_ERR_INVALID, who + "unknown flag bits");
+  const bool tracers = (flags & NBODY_WATCH_TRACERS) != 0;
+  if (tracers && !rows.has_tracer_calls) return ens_fail(e, NBODY_ERR_INVALID, who + "NBODY_WATCH_TRACERS on a handle without tracers");
+  if (n_steps < 0) return ens_fail(e, NBODY_ERR_INVALID, who + "n_steps < 0");
+  if (stride < 1) return ens_fail(e, NBODY_ERR_INVALID, who + "stride must be >= 1");
+  if (height > kWatchMaxHeight) return ens_fail(e, NBODY_ERR_INVALID, who + "height must be <= 2^24");
+
+  ENS_HIPCHK(e, hipSetDevice(e->device));
+  const double t_begin = now_s();
+  const size_t n = (size_t)e->n_worlds;
+  int64_t n_tiles;
+  if (rows.sizes) {
+    if (int rc = ens_world_table(e, rows)) return rc;
+    n_tiles = tracers ? e->table.enc_tracer_tiles : e->table.enc_body_tiles;
+  } else {
+    n_tiles = e->n_worlds * (int64_t)encounter_tiles((uint32_t)(tracers ? rows.n_tracers : e->n_bodies));
+  }
+  const size_t t = (size_t)(tracers ? rows.tracer_rows : e->rows);  // the targets (<= 2^26)
+  if (int rc = e->watch_out.grow(e, n * sizeof(nbody_world_watch))) return rc;
+  if (t) {
+    if (int rc = e->watch_d2.grow(e, t * sizeof(Real))) return rc;
+    if (int rc = e->watch_index.grow(e, t * sizeof(int32_t))) return rc;
+    if (int rc = e->watch_sample.grow(e, t * sizeof(uint32_t))) return rc;
+    if (int rc = e->watch_first_close.grow(e, t * sizeof(uint32_t))) return rc;
+    if (int rc = e->watch_close_samples.grow(e, t * sizeof(uint32_t))) return rc;
+    if (int rc = e->watch_first_out.grow(e, t * sizeof(uint32_t))) return rc;
+  }
+  if (limit2) {
+    if (int rc = e->watch_limit.grow(e, n * sizeof(float))) return rc;
+    ENS_HIPCHK(e, hipMemcpyAsync(e->watch_limit.p, limit2, n * sizeof(float), hipMemcpyHostToDevice, e->stream));
+  }
+  EncounterArgs a;
+  a.tpos = rows.tpos;
+  a.table = rows.sizes ? e->table.worlds : nullptr;
+  a.tile_base = rows.sizes ? e->table.enc_tile_base + (tracers ? n + 1 : 0) : nullptr;
+  a.limit2 = limit2 ? e->watch_limit.p : nullptr;
+  a.limit_all = e->params.clamp;
+  a.n_bodies = (uint32_t)e->n_bodies;
+  a.n_tracers = (uint32_t)rows.n_tracers;
+  a.n_worlds = (uint32_t)e->n_worlds;
+  a.tracers = tracers ? 1u : 0u;
+  WatchRun w;
+  w.min_d2 = e->watch_d2.p;
+  w.min_index = e->watch_index.p;
+  w.min_sample = e->watch_sample.p;
+  w.first_close = e->watch_first_close.p;
+  w.close_samples = e->watch_close_samples.p;
+  w.first_out = e->watch_first_out.p;
+  w.height = height;
+  const int per_lane = lab_int("NBODY_WATCH_PER_LANE", kWatchPerLane);
+  uint32_t samples = 0;
+  for (int s = 0;; ++s) {
+    if (s % stride == 0 && !(s == 0 && (flags & NBODY_WATCH_RESUME))) {
+      a.pos = e->pos[e->cur];  // (the tracers are stepped in place)
+      w.sample = (uint32_t)s;
+      w.first = samples == 0 ? 1u : 0u;
+      ENS_HIPCHK(e, launch_ensemble_watch_sample<Real>(e->stream, a, w, n_tiles, per_lane));
+      ++samples;
+    }
+    if (s == n_steps) break;
+    ENS_HIPCHK(e, ens_enqueue_step(e, delta, launch));
+  }
+  a.pos = e->pos[e->cur];
+  ENS_HIPCHK(e, launch_ensemble_watch_worlds<Real>(e->stream, a, w, samples, e->watch_out.p));
+  ENS_HIPCHK(e, hipMemcpyAsync(out, e->watch_out.p, n * sizeof(nbody_world_watch), hipMemcpyDeviceToHost, e->stream));
+  if (t && out_rows && samples) {
+    const auto copy = [&](void* dst, const void* src, size_t bytes) {
+      return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream) : hipSuccess;
+    };
+    ENS_HIPCHK(e, copy(out_rows->min_d2, e->watch_d2.p, t * sizeof(Real)));
+    ENS_HIPCHK(e, copy(out_rows->min_index, e->watch_index.p, t * sizeof(int32_t)));
+    ENS_HIPCHK(e, copy(out_rows->min_sample, e->watch_sample.p, t * sizeof(uint32_t)));
+    ENS_HIPCHK(e, copy(out_rows->first_close, e->watch_first_close.p, t * sizeof(uint32_t)));
+    ENS_HIPCHK(e, copy(out_rows->close_samples, e->watch_close_samples.p, t * sizeof(uint32_t)));
+    ENS_HIPCHK(e, copy(out_rows->first_out, e->watch_first_out.p, t * sizeof(uint32_t)));
+  }
+  ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (t && out_rows && !samples) {  // no sample was taken: the device rows were never written, every target is as it began
+    if (out_rows->min_d2) std::fill(out_rows->min_d2, out_rows->min_d2 + t, std::numeric_limits<Real>::infinity());
+    if (out_rows->min_index) std::fill(out_rows->min_index, out_rows->min_index + t, -1);
+    if (out_rows->min_sample) std::fill(out_rows->min_sample, out_rows->min_sample + t, NBODY_WATCH_NEVER);
+    if (out_rows->first_close) std::fill(out_rows->first_close, out_rows->first_close + t, NBODY_WATCH_NEVER);
+    if (out_rows->close_samples) std::fill(out_rows->close_samples, out_rows->close_samples + t, 0u);
+    if (out_rows->first_out) std::fill(out_rows->first_out, out_rows->first_out + t, NBODY_WATCH_NEVER);
+  }
+  const double dt = now_s() - t_begin;  // booked as an update's seconds are
+  e->counting.sum_gravity += dt;
+  if (counter) counter->sum_gravity += dt;
   return NBODY_OK;
 }
 

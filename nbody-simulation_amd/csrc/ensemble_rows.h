@@ -3,7 +3,7 @@
 // from its index; a ragged one reads them from a table, one WorldRanges per world, which the driver builds from the sizes and
 // counts it holds (ens_world_table, ensemble_observers.h).  The lookups below are shared where the kernels that use them compile
 // to what they compiled to with a helper of their own; frame_world (ensemble_frames.hip: 32-bit products) and encounter_rows
-// (ensemble_encounters.hip: sources and targets from one load of the record) stay with their units for that reason.
+// (ensemble_encounter_device.h: sources and targets from one load of the record) stay apart for that reason.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -65,3 +65,9 @@ NB_API int nbody_encounters_ragged(nbody_ragged* e, uint32_t flags, const float*
                                    uint32_t* close) {
   return ens_encounters<RagF32>(e, flags, limit2, out, nn_index, nn_d2, close, ragged_rows<RagF32>(e));
 }
+// (an update sampled before, between and after its steps, ensemble_watch.h: likewise a prefix of its own)
+NB_API int nbody_watch_ragged(nbody_ragged* e, uint32_t flags, float delta, int n_steps, int stride, const float* limit2, uint32_t height,
+                              nbody_world_watch* out, const nbody_watch_rows_f32* rows, nbody_counting* counter) {
+  return ens_watch_with<RagF32>(e, flags, delta, n_steps, stride, limit2, height, out, rows, counter, ragged_rows<RagF32>(e),
+                                [e](const RagF32::Args& a) { return ragged_launch_all<RagF32>(e, a); });
+}

@@ -62,3 +62,9 @@ NB_API int nbody_encounters_ragged64(nbody_ragged64* e, uint32_t flags, const fl
                                      uint32_t* close) {
   return ens_encounters<RagF64>(e, flags, limit2, out, nn_index, nn_d2, close, ragged_rows<RagF64>(e));
 }
+// (an update sampled before, between and after its steps, ensemble_watch.h: likewise a prefix of its own)
+NB_API int nbody_watch_ragged64(nbody_ragged64* e, uint32_t flags, double delta, int n_steps, int stride, const float* limit2, uint32_t height,
+                                nbody_world_watch* out, const nbody_watch_rows_f64* rows, nbody_counting* counter) {
+  return ens_watch_with<RagF64>(e, flags, delta, n_steps, stride, limit2, height, out, rows, counter, ragged_rows<RagF64>(e),
+                                [e](const RagF64::Args& a) { return ragged_launch_all<RagF64>(e, a); });
+}

@@ -61,3 +61,9 @@ NB_API int nbody_encounters_restricted(nbody_restricted* e, uint32_t flags, cons
                                        uint32_t* close) {
   return ens_encounters<RstF32>(e, flags, limit2, out, nn_index, nn_d2, close, rst_rows<RstF32>(e));
 }
+// (an update sampled before, between and after its steps, ensemble_watch.h: likewise a prefix of its own)
+NB_API int nbody_watch_restricted(nbody_restricted* e, uint32_t flags, float delta, int n_steps, int stride, const float* limit2, uint32_t height,
+                                  nbody_world_watch* out, const nbody_watch_rows_f32* rows, nbody_counting* counter) {
+  return ens_watch_with<RstF32>(e, flags, delta, n_steps, stride, limit2, height, out, rows, counter, rst_rows<RstF32>(e),
+                                [e](const RstF32::Args& a) { return rst_launch_step<RstF32>(e, a); });
+}

@@ -61,3 +61,9 @@ NB_API int nbody_encounters_restricted64(nbody_restricted64* e, uint32_t flags, 
                                          uint32_t* close) {
   return ens_encounters<Rst64>(e, flags, limit2, out, nn_index, nn_d2, close, rst_rows<Rst64>(e));
 }
+// (an update sampled before, between and after its steps, ensemble_watch.h: likewise a prefix of its own)
+NB_API int nbody_watch_restricted64(nbody_restricted64* e, uint32_t flags, double delta, int n_steps, int stride, const float* limit2, uint32_t height,
+                                    nbody_world_watch* out, const nbody_watch_rows_f64* rows, nbody_counting* counter) {
+  return ens_watch_with<Rst64>(e, flags, delta, n_steps, stride, limit2, height, out, rows, counter, rst_rows<Rst64>(e),
+                               [e](const Rst64::Args& a) { return rst_launch_step<Rst64>(e, a); });
+}

@@ -83,3 +83,9 @@ NB_API int nbody_encounters_rr(nbody_rr* e, uint32_t flags, const float* limit2,
                                uint32_t* close) {
   return ens_encounters<RrF32>(e, flags, limit2, out, nn_index, nn_d2, close, rr_rows<RrF32>(e));
 }
+// (an update sampled before, between and after its steps, ensemble_watch.h: likewise a prefix of its own)
+NB_API int nbody_watch_rr(nbody_rr* e, uint32_t flags, float delta, int n_steps, int stride, const float* limit2, uint32_t height,
+                          nbody_world_watch* out, const nbody_watch_rows_f32* rows, nbody_counting* counter) {
+  return ens_watch_with<RrF32>(e, flags, delta, n_steps, stride, limit2, height, out, rows, counter, rr_rows<RrF32>(e),
+                               [e](const RrF32::Args& a) { return rr_launch_step<RrF32>(e, a); });
+}

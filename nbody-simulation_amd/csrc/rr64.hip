@@ -84,3 +84,9 @@ NB_API int nbody_encounters_rr64(nbody_rr64* e, uint32_t flags, const float* lim
                                  uint32_t* close) {
   return ens_encounters<RrF64>(e, flags, limit2, out, nn_index, nn_d2, close, rr_rows<RrF64>(e));
 }
+// (an update sampled before, between and after its steps, ensemble_watch.h: likewise a prefix of its own)
+NB_API int nbody_watch_rr64(nbody_rr64* e, uint32_t flags, double delta, int n_steps, int stride, const float* limit2, uint32_t height,
+                            nbody_world_watch* out, const nbody_watch_rows_f64* rows, nbody_counting* counter) {
+  return ens_watch_with<RrF64>(e, flags, delta, n_steps, stride, limit2, height, out, rows, counter, rr_rows<RrF64>(e),
+                               [e](const RrF64::Args& a) { return rr_launch_step<RrF64>(e, a); });
+}

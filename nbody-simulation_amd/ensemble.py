@@ -58,6 +58,13 @@ neighbour (`nn_index`, `nn_d2`) and the number of its pairs closer than limit2[k
 the step's own expressions, so with limit2=None `close_pairs` counts the ordered pairs whose force the clamp altered.  Every
 output is order-free, hence bit for bit; the classes with tracers take `tracers=True` for every tracer's nearest
 body.  `encounters_of(targets, sources, limit2)` is the same contract in host code, for one segment.
+
+Every class has `watch(delta, n_steps, limit2=None, height=0, stride=1)` (nbody_watch_*): an update that the device samples
+before, between and after its steps — per body its closest approach over the run and the sample it occurred at, the first sample
+with a pair closer than limit2[k] and how many samples had one, the first sample outside the frame — and per world a record of
+`WATCH_DTYPE`, without a host synchronisation between the steps; the rows afterwards are those of `update`.  The classes with
+tracers take `tracers=True` for every tracer against its world's bodies.  `watch_merge(first, second, steps_before)` joins a call
+and the `resume=True` call that continued it into what one call gives, bit for bit.
 """
 from __future__ import annotations
 
@@ -284,6 +291,138 @@ class _EncountersWithTracers(_Encounters):
         return self._encounters(limit2, tracers, rows)
 
 
+WATCH_DTYPE = _capi.WATCH_DTYPE
+WATCH_NEVER = _capi.WATCH_NEVER
+WATCH_ROWS = _capi.WATCH_ROWS
+
+
+def _checked_watch(who, b, dtype, delta, n_steps, limit2, height, stride, rows, resume, tracers):
+    """The arguments of `watch` for b worlds -> (delta, n_steps, stride, limit2 float32[b] contiguous or None, height, tracers,
+    resume, rows); ValueError naming `who` and the argument for anything else."""
+    if isinstance(delta, (bool, np.bool_)) or not isinstance(delta, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{who}.watch: delta must be a number, got {delta!r}")
+    for name, v, least in (("n_steps", n_steps, 0), ("stride", stride, 1)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not least <= int(v) < 1 << 31:
+            raise ValueError(f"{who}.watch: {name} must be an integer {least} .. 2^31 - 1, got {v!r}")
+    if isinstance(height, (bool, np.bool_)) or not isinstance(height, (int, np.integer)) or not 0 <= int(height) <= MAX_HEIGHT:
+        raise ValueError(f"{who}.watch: height must be an integer 0 .. 2^24, got {height!r}")
+    for name, flag in (("rows", rows), ("resume", resume), ("tracers", tracers)):
+        if not isinstance(flag, (bool, np.bool_)):
+            raise ValueError(f"{who}.watch: {name} must be True or False, got {flag!r}")
+    if limit2 is not None:
+        limit2 = np.asarray(limit2)
+        if limit2.ndim != 1 or limit2.shape[0] != b:
+            raise ValueError(f"{who}.watch: limit2 must hold one squared distance per world ({b} worlds), got shape {limit2.shape}")
+        if limit2.dtype.kind not in "fiu":
+            raise ValueError(f"{who}.watch: limit2 must be real numbers, got {limit2.dtype}")
+        with np.errstate(over="ignore"):
+            limit2 = np.ascontiguousarray(limit2, dtype=np.float32)
+    return float(dtype(delta)), int(n_steps), int(stride), limit2, int(height), bool(tracers), bool(resume), bool(rows)
+
+
+def _min_record(d2, sample):
+    """The row with the smallest (d2, sample, row) among the rows with sample != WATCH_NEVER, or -1."""
+    have = np.flatnonzero(sample != WATCH_NEVER)
+    if not have.size:
+        return -1
+    order = np.lexsort((have, sample[have], d2[have].astype(np.float64)))   # (the last key sorts first)
+    return int(have[order[0]])
+
+
+def watch_merge(first, second, steps_before):
+    """`watch(n1)` and the `watch(n2, resume=True)` that followed it, as one `watch(n1 + n2)`: first and second are what the two
+    calls returned, (records, rows) with rows not None, and steps_before is n1 (a multiple of the stride) -> (records, rows), bit
+    for bit what the one call gives.  The second call's sample numbers are shifted by steps_before; per target its closest
+    approach replaces the first call's on a strict `<` only, first_close and first_out are the first call's unless it has none,
+    close_samples add; the records are made again from the merged rows.  Plain NumPy: no GPU and no library call."""
+    (rec1, rows1), (rec2, rows2) = first, second
+    if rows1 is None or rows2 is None:
+        raise ValueError("watch_merge: both calls must have returned their rows (rows=True): the records alone do not merge")
+    if isinstance(steps_before, (bool, np.bool_)) or not isinstance(steps_before, (int, np.integer)) or not 0 <= int(steps_before) < 1 << 31:
+        raise ValueError(f"watch_merge: steps_before must be an integer 0 .. 2^31 - 1, got {steps_before!r}")
+    rec1, rec2 = np.asarray(rec1), np.asarray(rec2)
+    if rec1.dtype != WATCH_DTYPE or rec2.dtype != WATCH_DTYPE or rec1.shape != rec2.shape or rec1.ndim != 1:
+        raise ValueError("watch_merge: the records must be WATCH_DTYPE arrays of one length")
+    for name in ("rows", "sources"):
+        if not np.array_equal(rec1[name], rec2[name]):
+            raise ValueError(f"watch_merge: the two calls differ in {name}: they are not calls on the same worlds")
+    shift = np.uint32(int(steps_before))
+
+    def later(s):
+        return np.where(s == WATCH_NEVER, np.uint32(WATCH_NEVER), s + shift).astype(np.uint32)
+
+    def world(a, b):
+        take = (b["min_index"] >= 0) & ((a["min_index"] < 0) | (b["min_d2"] < a["min_d2"]))
+        out = {"min_d2": np.where(take, b["min_d2"], a["min_d2"]), "min_index": np.where(take, b["min_index"], a["min_index"]),
+               "min_sample": np.where(take, later(b["min_sample"]), a["min_sample"]),
+               "close_samples": a["close_samples"] + b["close_samples"]}
+        for name in ("first_close", "first_out"):
+            out[name] = np.where(a[name] != WATCH_NEVER, a[name], later(b[name]))
+        return {name: out[name].astype(a[name].dtype) for name in WATCH_ROWS}
+
+    ragged = isinstance(rows1["min_d2"], list)
+    n = rec1.shape[0]
+    per_world = [world({k: rows1[k][i] for k in WATCH_ROWS}, {k: rows2[k][i] for k in WATCH_ROWS}) for i in range(n)]
+    rec = rec1.copy()
+    rec["samples"] = rec1["samples"] + rec2["samples"]
+    for i, r in enumerate(per_world):
+        at = _min_record(r["min_d2"], r["min_sample"])
+        rec["min_row"][i] = at
+        rec["min_source"][i] = r["min_index"][at] if at >= 0 else -1
+        rec["min_sample"][i] = r["min_sample"][at] if at >= 0 else -1
+        rec["min_d2"][i] = r["min_d2"][at] if at >= 0 else np.inf
+        rec["close_rows"][i] = int((r["close_samples"] > 0).sum())
+        rec["close_row_samples"][i] = int(r["close_samples"].astype(np.int64).sum())
+        rec["out_rows"][i] = int((r["first_out"] != WATCH_NEVER).sum())
+        rec["isolated_rows"][i] = int((r["min_index"] < 0).sum())
+        for field, name in (("first_close_sample", "first_close"), ("first_out_sample", "first_out")):
+            seen = r[name][r[name] != WATCH_NEVER]
+            rec[field][i] = int(seen.min()) if seen.size else -1
+    if ragged:
+        return rec, {name: [r[name] for r in per_world] for name in WATCH_ROWS}
+    return rec, {name: np.stack([r[name] for r in per_world]) for name in WATCH_ROWS}
+
+
+class _Watch:
+    """`watch` for the ensemble classes without tracers: the class keeps `_n_worlds` and `_dtype`, its handle has `watch`; a class
+    of worlds of different sizes keeps `_cuts` (and `_tcuts` for its tracers) and gets per-world lists, as from `particles()`."""
+
+    def _watch(self, delta, n_steps, limit2, height, stride, rows, resume, counter, tracers):
+        delta, n_steps, stride, limit2, height, tracers, resume, rows = _checked_watch(
+            type(self).__name__, self._n_worlds, self._dtype, delta, n_steps, limit2, height, stride, rows, resume, tracers)
+        out, flat = self.h.watch(delta, n_steps, stride, limit2, height, tracers, resume, rows, counter)
+        if not rows:
+            return out, None
+        if hasattr(self, "_cuts"):
+            return out, {name: [w.copy() for w in np.split(a, self._tcuts if tracers else self._cuts)] for name, a in flat.items()}
+        return out, {name: a.reshape(self._n_worlds, a.size // self._n_worlds) for name, a in flat.items()}
+
+    def watch(self, delta, n_steps=1, limit2=None, height=0, stride=1, rows=True, resume=False, counter: Counting | None = None):
+        """update(delta, n_steps) with every world sampled on the device before, between and after its steps (nbody_watch_*) ->
+        (records, rows): WATCH_DTYPE[B] and a dict of six arrays per body — min_d2, min_index, min_sample: its closest approach
+        to another body of its world over the samples, the source's world-local index and the sample it occurred at;
+        first_close, close_samples: the first sample at which it had a pair with d2 < limit2[k] and how many samples had one;
+        first_out: the first sample at which it was outside [0, height)^2 — [B, n] arrays, or per-world lists where the worlds
+        have sizes of their own; None with rows=False.  Sample s is the state after s steps of this call, taken when s % stride
+        == 0; resume=True leaves sample 0 out (`watch_merge` joins such a call to the one before it).  A sample number that did
+        not occur is WATCH_NEVER in the rows and -1 in the records.  limit2: None (the clamp of every world) or one number per
+        world.  The rows afterwards are bit for bit those after update(delta, n_steps=n_steps).  The arguments are checked here,
+        with ValueError, before the library is touched."""
+        return self._watch(delta, n_steps, limit2, height, stride, rows, resume, counter, False)
+
+
+class _WatchWithTracers(_Watch):
+    """`watch` for the ensemble classes with tracers."""
+
+    def watch(self, delta, n_steps=1, limit2=None, height=0, stride=1, rows=True, resume=False, counter: Counting | None = None,
+              tracers=False):
+        """-> (records, rows) as the classes without tracers give them; with tracers=True the targets are every world's tracers
+        and the sources its bodies: per tracer its closest approach to a body, its close samples and the sample at which it left
+        the frame ([B, m] arrays or per-world lists; a world without tracers: rows == 0).  Bodies and tracers are stepped
+        either way.  The arguments are checked here, with ValueError, before the library is touched."""
+        return self._watch(delta, n_steps, limit2, height, stride, rows, resume, counter, tracers)
+
+
 class _Sweep:
     """`sweep` for every ensemble class: the class keeps `_n_worlds` and `_dtype`, its handle has `sweep`."""
 
@@ -335,7 +474,7 @@ def _checked(position, velocity, weight, dtype=np.float32, who=None, other=None)
     return b, n, np.ascontiguousarray(position), np.ascontiguousarray(velocity), weight
 
 
-class _EnsembleBase(_Encounters, _Summary, _Sweep):
+class _EnsembleBase(_Watch, _Encounters, _Summary, _Sweep):
     """What Ensemble, Ensemble64 and the restricted ensembles share; each names its dtype and makes its own kind of handle."""
     _dtype = None
 
@@ -454,7 +593,7 @@ def _checked_tracers(tracers, b, who="RestrictedEnsemble", dtype=np.float32):
     return m, np.ascontiguousarray(tp), np.ascontiguousarray(tv)
 
 
-class _RestrictedBase(_EncountersWithTracers, _SummaryWithTracers, _EnsembleBase):
+class _RestrictedBase(_WatchWithTracers, _EncountersWithTracers, _SummaryWithTracers, _EnsembleBase):
     """What RestrictedEnsemble and RestrictedEnsemble64 share: the tracers beside the bodies.  Each names its dtype, makes its own
     kind of handle and says which class takes the other dtype."""
     _other = None
@@ -582,7 +721,7 @@ def _checked_ragged(positions, velocities, weights, dtype=np.float32, who=None, 
     return np.asarray(sizes, np.int64), position, velocity, weight
 
 
-class _RaggedBase(_Encounters, _Summary, _Sweep):
+class _RaggedBase(_Watch, _Encounters, _Summary, _Sweep):
     """What RaggedEnsemble and RaggedEnsemble64 share; each names its dtype, makes its own kind of handle and has its own
     constructor."""
     _dtype = None
@@ -722,7 +861,7 @@ def _checked_rr_tracers(tracers, sizes, who="RaggedRestrictedEnsemble", dtype=np
     return counts, np.ascontiguousarray(np.concatenate(tps)), np.ascontiguousarray(np.concatenate(tvs))
 
 
-class RaggedRestrictedEnsemble(_EncountersWithTracers, _SummaryWithTracers, _RaggedBase):
+class RaggedRestrictedEnsemble(_WatchWithTracers, _EncountersWithTracers, _SummaryWithTracers, _RaggedBase):
     """Worlds of different sizes, each with tracers of its own, stepped together (nbody_rr_*), float32: positions, velocities
     are sequences of [n_k, 2] arrays, weights a sequence of [n_k] integer arrays or None (all 1), tracers None or a list with one
     entry per world, each None or a pair (position[m_k, 2], velocity[m_k, 2]).  1 .. 4096 bodies per world, at most 2^26 bodies
