@@ -850,9 +850,8 @@ int nbody_encounters_of_f64(int64_t n_targets, const double* target_xy, int64_t 
  *     A NULL handle gives NBODY_ERR_INVALID without a message.  NBODY_WATCH_TRACERS on a restricted handle that holds no
  *     tracers, or for a world of an nbody_rr handle without them, gives rows == 0 records: zero counts, -1 indices and sample
  *     numbers, min_d2 = +inf (the steps are taken all the same).
- *   Not offered: a watched sweep with a delta, a clamp or a number of steps per world (the driver takes the step's launch as a
- *     callable, so it can come later); tracer-tracer pairs; the k nearest for k > 1; a per-sample history; a device-pointer
- *     variant; anything for nbody_ctx contexts. */
+ *   Not offered: tracer-tracer pairs; the k nearest for k > 1; a per-sample history; a device-pointer variant; anything for
+ *     nbody_ctx contexts.  (A delta, a clamp, a number of steps and a stride per world: nbody_wsweep_* below.) */
 typedef struct nbody_world_watch { /* 13 fields of 8 bytes, no padding: 104 bytes */
   int64_t rows;               /* targets of the segment: the world's bodies, or its tracers */
   int64_t sources;            /* the world's bodies */
@@ -911,5 +910,105 @@ int nbody_watch_rr64(nbody_rr64* e, uint32_t flags, double delta, int n_steps, i
                      const float* limit2 /*[n_worlds] or NULL: params.clamp*/, uint32_t height,
                      nbody_world_watch* out /*[n_worlds]*/, const nbody_watch_rows_f64* rows /*NULL: records only*/,
                      nbody_counting* counter);
+
+/* ---- a watched sweep of an ensemble: a watched run in which every world has its own time step, clamp, steps and stride ----
+ * The two halves of a parameter study in one call, for all eight handles above.  nbody_sweep_* gives every world a delta, a
+ * clamp and a number of steps; nbody_watch_* asks a run as a whole how close each target got, whether the clamp decided a pair
+ * and when a target left the frame — but steps every world by one delta under one params.clamp.  A watched sweep is the
+ * handle's nbody_sweep_<handle>(delta, clamp, steps, n_steps) with the device sampling world k on world k's own schedule: a
+ * softening sweep learns per world which targets that world's own clamp altered, and a convergence study with steps[k] = T /
+ * delta[k] and stride[k] proportional to steps[k] samples every world at the same physical times.
+ *   The prefix.  nbody_wsweep_<handle>, and nbody_wsweep_plan: the names under nbody_watch_, under nbody_sweep_ and under
+ *     each handle's own prefix are closed sets, so these nine have a prefix of their own.
+ *   Arguments.  delta, clamp, steps and n_steps as nbody_sweep_* takes them; stride and limit2 are host arrays of n_worlds
+ *     elements as well, read during the call only.  stride == NULL: 1 in every world.  The flags are NBODY_WATCH_TRACERS and
+ *     NBODY_WATCH_RESUME; out, rows, nbody_world_watch, nbody_watch_rows_f32 / _f64 and NBODY_WATCH_NEVER are the watch's.
+ *   Run.  After the call the handle's rows — bodies and tracers, under EXACT, FAST and AUTO — are bit for bit those after
+ *     nbody_sweep_<handle>(delta, clamp, steps, n_steps); its step count has advanced by n_steps and its delta-stream sequences
+ *     are as after that sweep.
+ *   Samples.  Sample s, 0 <= s <= n_steps, is the state after s steps of this call.  World k takes it iff s <= steps[k]
+ *     (steps == NULL: n_steps), s % stride[k] == 0, and not (s == 0 with NBODY_WATCH_RESUME).  A world that has taken its
+ *     steps stands still and is not sampled again.  Sample numbers in the outputs are these s, step counts of the call, as in
+ *     a watch.
+ *   Record.  samples is the world's own number of samples: steps[k] / stride[k] + 1, minus 1 with NBODY_WATCH_RESUME.
+ *   Close.  limit2 == NULL: world k's limit is clamp[k]; with clamp == NULL as well, params.clamp.  A softening sweep then
+ *     reports, per world, the targets whose force that world's own clamp altered.
+ *   Per-world contract (all of it).  World k's record and its slice of every rows array are bit for bit what a handle of the
+ *     same kind gives when it holds world k alone with params.clamp = clamp[k] and calls nbody_watch_<handle>(flags, delta[k],
+ *     steps[k], stride[k], limit2 ? &limit2[k] : NULL, height, ...).  So every rule of the watch carries over world by world:
+ *     the arithmetic, live pairs, the tie rules, order-freedom, and tracers against their own world's bodies.
+ *   No samples.  A world takes none under NBODY_WATCH_RESUME with stride[k] > steps[k] (steps[k] == 0 among them), and so
+ *     does every world when n_steps == 0 under NBODY_WATCH_RESUME.  Its record is the watch's no-sample record: samples 0,
+ *     isolated_rows == rows, -1 indices and sample numbers, min_d2 = +inf.  Its rows are +inf, -1, NBODY_WATCH_NEVER,
+ *     NBODY_WATCH_NEVER, 0, NBODY_WATCH_NEVER: written by the reduce, never stale scratch.
+ *   Independence.  As the sweep and the watch state it, and: a world's record and rows do not depend on the other worlds'
+ *     stride, nor on which sampling launches the other worlds caused.
+ *   Split over calls.  wsweep(n1, steps1) followed by wsweep(n2, steps2) with NBODY_WATCH_RESUME, merged as the watch's split
+ *     merges with the second call's sample numbers shifted by n1, is wsweep(n1 + n2, steps) bit for bit, where every world is
+ *     of one of two kinds: it ran through the first call — steps1[k] == n1, n1 % stride[k] == 0, steps[k] = n1 + steps2[k] — or
+ *     it was finished within it — steps2[k] == 0, steps[k] = steps1[k].
+ *   Calls.  Synchronous, on the handle's stream.  The step launches of a sweep (1, 2, at most NBODY_RAGGED_MAX_LAUNCHES or at
+ *     most NBODY_RR_MAX_LAUNCHES per step); one sampling launch for every s at which at least one world takes a sample and
+ *     none for an s nobody samples — the blocks of a world that does not sample at s return before they stage anything; one
+ *     reduce launch at the end.  Nothing is read back and there is no host synchronisation before the end of the call; no
+ *     floating-point atomics.  A world's first taken sample writes its running rows and later ones fold into them, so no pass
+ *     clears them.  The host finds the s that need a launch in time O(n_worlds + n_steps * distinct strides), not O(samples).
+ *     The seconds are booked under sum_gravity (`counter` may be NULL).  The device scratch is the watch's and the sweep's,
+ *     with one 16-byte schedule entry per world beside it, freed with the handle's other arrays.
+ *   nbody_wsweep_plan.  Pure host code, no device, no handle: samples_of_world[k] is the record's samples of world k, and
+ *     n_sampling_launches the number of s in [0, n_steps] at which some world samples; either may be NULL.  It refuses what
+ *     the call refuses of these arguments — n_worlds < 1, n_steps < 0, a steps[k] outside [0, n_steps], a stride[k] < 1,
+ *     unknown flag bits — with NBODY_ERR_INVALID and no message, and then writes nothing.
+ *   Refusals.  NBODY_ERR_INVALID before anything is allocated or enqueued, the message beginning with the handle's word
+ *     ("ensemble", "ragged", "restricted", "ragged restricted") and naming "wsweep": the sweep's and the watch's together —
+ *     nothing uploaded; out NULL; delta NULL; unknown flag bits; n_steps < 0; a steps[k] outside [0, n_steps] (the message
+ *     names the world); NBODY_WATCH_TRACERS on one of the four handles that have no tracer calls; height > 2^24 — and a
+ *     stride[k] < 1 (the message names the world).  n_steps == 0 is allowed: every world takes sample 0 alone, or nothing with
+ *     NBODY_WATCH_RESUME.  A NULL handle gives NBODY_ERR_INVALID without a message.
+ *   Not offered: a per-world height; a per-world arith; a per-sample history; a device-pointer variant; anything for
+ *     nbody_ctx contexts. */
+int nbody_wsweep_ensemble(nbody_ensemble* e, uint32_t flags, const float* delta, const float* clamp,
+                          const int32_t* steps, int n_steps, const int32_t* stride /*[n_worlds] or NULL: 1*/,
+                          const float* limit2 /*[n_worlds] or NULL: world k's own clamp*/, uint32_t height,
+                          nbody_world_watch* out /*[n_worlds]*/, const nbody_watch_rows_f32* rows /*NULL: records only*/,
+                          nbody_counting* counter);
+int nbody_wsweep_ensemble64(nbody_ensemble64* e, uint32_t flags, const double* delta, const float* clamp,
+                            const int32_t* steps, int n_steps, const int32_t* stride /*[n_worlds] or NULL: 1*/,
+                            const float* limit2 /*[n_worlds] or NULL: world k's own clamp*/, uint32_t height,
+                            nbody_world_watch* out /*[n_worlds]*/, const nbody_watch_rows_f64* rows /*NULL: records only*/,
+                            nbody_counting* counter);
+int nbody_wsweep_ragged(nbody_ragged* e, uint32_t flags, const float* delta, const float* clamp,
+                        const int32_t* steps, int n_steps, const int32_t* stride /*[n_worlds] or NULL: 1*/,
+                        const float* limit2 /*[n_worlds] or NULL: world k's own clamp*/, uint32_t height,
+                        nbody_world_watch* out /*[n_worlds]*/, const nbody_watch_rows_f32* rows /*NULL: records only*/,
+                        nbody_counting* counter);
+int nbody_wsweep_ragged64(nbody_ragged64* e, uint32_t flags, const double* delta, const float* clamp,
+                          const int32_t* steps, int n_steps, const int32_t* stride /*[n_worlds] or NULL: 1*/,
+                          const float* limit2 /*[n_worlds] or NULL: world k's own clamp*/, uint32_t height,
+                          nbody_world_watch* out /*[n_worlds]*/, const nbody_watch_rows_f64* rows /*NULL: records only*/,
+                          nbody_counting* counter);
+int nbody_wsweep_restricted(nbody_restricted* e, uint32_t flags, const float* delta, const float* clamp,
+                            const int32_t* steps, int n_steps, const int32_t* stride /*[n_worlds] or NULL: 1*/,
+                            const float* limit2 /*[n_worlds] or NULL: world k's own clamp*/, uint32_t height,
+                            nbody_world_watch* out /*[n_worlds]*/, const nbody_watch_rows_f32* rows /*NULL: records only*/,
+                            nbody_counting* counter);
+int nbody_wsweep_restricted64(nbody_restricted64* e, uint32_t flags, const double* delta, const float* clamp,
+                              const int32_t* steps, int n_steps, const int32_t* stride /*[n_worlds] or NULL: 1*/,
+                              const float* limit2 /*[n_worlds] or NULL: world k's own clamp*/, uint32_t height,
+                              nbody_world_watch* out /*[n_worlds]*/, const nbody_watch_rows_f64* rows /*NULL: records only*/,
+                              nbody_counting* counter);
+int nbody_wsweep_rr(nbody_rr* e, uint32_t flags, const float* delta, const float* clamp,
+                    const int32_t* steps, int n_steps, const int32_t* stride /*[n_worlds] or NULL: 1*/,
+                    const float* limit2 /*[n_worlds] or NULL: world k's own clamp*/, uint32_t height,
+                    nbody_world_watch* out /*[n_worlds]*/, const nbody_watch_rows_f32* rows /*NULL: records only*/,
+                    nbody_counting* counter);
+int nbody_wsweep_rr64(nbody_rr64* e, uint32_t flags, const double* delta, const float* clamp,
+                      const int32_t* steps, int n_steps, const int32_t* stride /*[n_worlds] or NULL: 1*/,
+                      const float* limit2 /*[n_worlds] or NULL: world k's own clamp*/, uint32_t height,
+                      nbody_world_watch* out /*[n_worlds]*/, const nbody_watch_rows_f64* rows /*NULL: records only*/,
+                      nbody_counting* counter);
+int nbody_wsweep_plan(int64_t n_worlds, const int32_t* steps /*[n_worlds] or NULL: n_steps*/, int n_steps,
+                      const int32_t* stride /*[n_worlds] or NULL: 1*/, uint32_t flags,
+                      int64_t* samples_of_world /*[n_worlds] or NULL*/, int64_t* n_sampling_launches /*or NULL*/);
 
 #endif /* NBODY_ENSEMBLE_H */

@@ -255,6 +255,13 @@ _SIGS = {
     **{"nbody_watch_" + h: (C.c_int, [_vp, C.c_uint32, _f64 if h.endswith("64") else _f32, _i32, _i32, C.POINTER(_f32), C.c_uint32, _vp,
                                       C.POINTER(WatchRows), C.POINTER(Counting)])
        for h in ("ensemble", "ensemble64", "ragged", "ragged64", "restricted", "restricted64", "rr", "rr64")},
+    # nbody_wsweep_<handle>: flags, then a sweep's delta, clamp, steps, n_steps, then stride int32[n_worlds] or NULL, limit2
+    # float32[n_worlds] or NULL, and a watch's height, out, rows, counter
+    **{"nbody_wsweep_" + h: (C.c_int, [_vp, C.c_uint32, C.POINTER(_f64 if h.endswith("64") else _f32), C.POINTER(_f32), C.POINTER(C.c_int32),
+                                       _i32, C.POINTER(C.c_int32), C.POINTER(_f32), C.c_uint32, _vp, C.POINTER(WatchRows),
+                                       C.POINTER(Counting)])
+       for h in ("ensemble", "ensemble64", "ragged", "ragged64", "restricted", "restricted64", "rr", "rr64")},
+    "nbody_wsweep_plan": (C.c_int, [_i64, C.POINTER(C.c_int32), _i32, C.POINTER(C.c_int32), C.c_uint32, _vp, _vp]),
     "nbody_accel_tree_f32": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_accel_tree_f64": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_tree_info": (C.c_int, [_vp, C.POINTER(TreeView)]),
@@ -1098,6 +1105,29 @@ class _EnsembleHandleBase:
                                             C.byref(counter) if counter is not None else None))
         return out, arrays
 
+    def watch_sweep(self, delta, clamp, steps, n_steps, stride, limit2, height, tracers=False, resume=False, rows=True,
+                    counter: "Counting | None" = None):
+        """nbody_wsweep_<handle>: sweep(delta, clamp, steps, n_steps) with world k sampled at every s <= steps[k] with s %
+        stride[k] == 0 (resume=True: not s = 0) -> what `watch` returns.  delta [worlds] of the handle's dtype; clamp, limit2
+        float32[worlds] or None; steps, stride int32[worlds] or None; all contiguous (ensemble.py's `watch_sweep` checks and
+        casts them)."""
+        def typed(a, ctype):
+            return None if a is None else a.ctypes.data_as(C.POINTER(ctype))
+        out = np.zeros(self.shape[0], WATCH_DTYPE)
+        arrays, block = None, None
+        if rows:
+            total = int(self._delta_rows(tracers).sum())
+            arrays = {name: np.zeros(total, self._dtype if name == "min_d2" else np.int32 if name == "min_index" else np.uint32)
+                      for name in WATCH_ROWS}
+            block = WatchRows(*[a.ctypes.data for a in arrays.values()])
+        name = "nbody_wsweep_" + self._prefix[len("nbody_"):]
+        real = C.c_double if self._dtype == np.float64 else C.c_float
+        self._check(getattr(self.lib, name)(self.h, (WATCH_TRACERS if tracers else 0) | (WATCH_RESUME if resume else 0), typed(delta, real),
+                                            typed(clamp, C.c_float), typed(steps, C.c_int32), int(n_steps), typed(stride, C.c_int32),
+                                            typed(limit2, C.c_float), int(height), _ptr(out), C.byref(block) if block is not None else None,
+                                            C.byref(counter) if counter is not None else None))
+        return out, arrays
+
     def _delta_rows(self, tracers):
         """The rows of every segment a deltas(), encounters() or watch() call addresses, int64[worlds]."""
         b, n = self.shape
@@ -1277,6 +1307,21 @@ def ragged_plan(sizes, f64=False):
         msg = getattr(lib, prefix + "_last_error")(None)
         raise NBodyError(rc, msg.decode() if msg else "")
     return launch, first, lds[:n.value].copy(), blocks[:n.value].copy()
+
+
+def wsweep_plan(n_worlds, steps, n_steps, stride, resume=False):
+    """nbody_wsweep_plan (pure host code): steps, stride int32[n_worlds], contiguous, or None -> (samples_of_world
+    int64[n_worlds], n_sampling_launches); ValueError where the library refuses."""
+    def typed(a):
+        return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+    lib = load()
+    samples = np.zeros(max(int(n_worlds), 0), np.int64)
+    launches = C.c_int64(0)
+    rc = lib.nbody_wsweep_plan(int(n_worlds), typed(steps), int(n_steps), typed(stride), WATCH_RESUME if resume else 0, _ptr(samples),
+                               C.byref(launches))
+    if rc != 0:
+        raise ValueError(f"wsweep_plan: refused (n_worlds = {n_worlds}, n_steps = {n_steps}): a steps[k] outside 0 .. n_steps or a stride[k] < 1")
+    return samples, int(launches.value)
 
 
 def rr_plan(sizes, tracer_counts, f64=False):

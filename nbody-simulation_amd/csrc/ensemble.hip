@@ -51,3 +51,15 @@ NB_API int nbody_watch_ensemble(nbody_ensemble* e, uint32_t flags, float delta, 
   return ens_watch_with<EnsF32>(e, flags, delta, n_steps, stride, limit2, height, out, rows, counter, WorldRows<EnsF32>(),
                                 [e](const EnsF32::Args& a) { return EnsF32::launch(e->stream, e->n_worlds, a); });
 }
+// (a sweep sampled on every world's own schedule, ensemble_watch.h: likewise a prefix of its own)
+NB_API int nbody_wsweep_ensemble(nbody_ensemble* e, uint32_t flags, const float* delta, const float* clamp, const int32_t* steps, int n_steps,
+        const int32_t* stride, const float* limit2, uint32_t height, nbody_world_watch* out, const nbody_watch_rows_f32* rows,
+        nbody_counting* counter) {
+  return ens_wsweep_with<EnsF32>(e, flags, delta, clamp, steps, n_steps, stride, limit2, height, out, rows, counter, WorldRows<EnsF32>(),
+        [e](const EnsF32::Args& a) { return EnsF32::launch(e->stream, e->n_worlds, a); });
+}
+// (what such a call samples, and in how many launches: pure host code, no handle)
+NB_API int nbody_wsweep_plan(int64_t n_worlds, const int32_t* steps, int n_steps, const int32_t* stride, uint32_t flags, int64_t* samples_of_world,
+                             int64_t* n_sampling_launches) {
+  return wsweep_show_plan(n_worlds, steps, n_steps, stride, flags, samples_of_world, n_sampling_launches);
+}

@@ -51,3 +51,10 @@ NB_API int nbody_watch_ensemble64(nbody_ensemble64* e, uint32_t flags, double de
   return ens_watch_with<EnsF64>(e, flags, delta, n_steps, stride, limit2, height, out, rows, counter, WorldRows<EnsF64>(),
                                 [e](const EnsF64::Args& a) { return EnsF64::launch(e->stream, e->n_worlds, a); });
 }
+// (a sweep sampled on every world's own schedule, ensemble_watch.h: likewise a prefix of its own)
+NB_API int nbody_wsweep_ensemble64(nbody_ensemble64* e, uint32_t flags, const double* delta, const float* clamp, const int32_t* steps, int n_steps,
+        const int32_t* stride, const float* limit2, uint32_t height, nbody_world_watch* out, const nbody_watch_rows_f64* rows,
+        nbody_counting* counter) {
+  return ens_wsweep_with<EnsF64>(e, flags, delta, clamp, steps, n_steps, stride, limit2, height, out, rows, counter, WorldRows<EnsF64>(),
+        [e](const EnsF64::Args& a) { return EnsF64::launch(e->stream, e->n_worlds, a); });
+}

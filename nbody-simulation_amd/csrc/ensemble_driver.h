@@ -20,9 +20,10 @@
 // under its own kWho, with the tracers' launch added to a step through ens_update_with.
 // This file: the state (with the scratch of every call, each a DevBuf grown on demand and freed with the rows), create /
 // destroy, params, upload / download, and the stepping calls: update, sweep (nbody_sweep_*: a time step, a clamp and a number of
-// steps per world) and accel.  The calls that read every world's current rows and return something per world — frames, delta
-// streams, summaries, encounters — and the watched run are ensemble_observers.h, included at the end: one function each for every handle, told where
-// the handle's rows are by one WorldRows.
+// steps per world) and accel; ens_enqueue_step and ens_enqueue_sweep_step are one step of either kind, for the watched runs too.
+// The calls that read every world's current rows and return something per world — frames, delta streams, summaries, encounters
+// — and the watched runs are ensemble_observers.h, included at the end: one function each for every handle, told where the
+// handle's rows are by one WorldRows.
 #pragma once
 #include <cstring>
 #include <new>
@@ -33,6 +34,7 @@
 #include "ensemble_deltas.h"
 #include "ensemble_kernels.h"
 #include "ensemble_rows.h"
+#include "ensemble_watch.h"
 
 namespace nbody {
 
@@ -139,6 +141,9 @@ template <class P> struct EnsembleState {
   DevBuf<int32_t> watch_index;
   DevBuf<uint32_t> watch_sample, watch_first_close, watch_close_samples, watch_first_out;
   DevBuf<float> watch_limit;
+  // a watched sweep (ens_wsweep_with): the watch's scratch above, the sweep's table, and every world's sampling schedule
+  std::vector<WatchWorld> watch_sched_host;
+  DevBuf<WatchWorld> watch_sched;
 };
 
 template <class P> thread_local std::string g_ens_create_error;  // one per precision: what a failed create left for its thread
@@ -173,7 +178,7 @@ template <class P> void ens_free(EnsembleState<P>* e) {
   e->summary_out.release(); e->summary_chunks.release(); e->summary_ref.release();
   e->enc_out.release(); e->enc_index.release(); e->enc_d2.release(); e->enc_close.release(); e->enc_live.release(); e->enc_limit.release();
   e->watch_out.release(); e->watch_d2.release(); e->watch_index.release(); e->watch_sample.release(); e->watch_first_close.release();
-  e->watch_close_samples.release(); e->watch_first_out.release(); e->watch_limit.release();
+  e->watch_close_samples.release(); e->watch_first_out.release(); e->watch_limit.release(); e->watch_sched.release();
   e->dbodies.release();
   e->dtracers.release();
   e->n_worlds = e->n_bodies = e->rows = 0;
@@ -327,6 +332,32 @@ template <class P, class Launch> hipError_t ens_enqueue_step(EnsembleState<P>* e
   return hipSuccess;
 }
 
+// Step `step` of a sweep whose table is in e->sweep_dev, enqueued through `launch(args)`: what a sweep and a watched sweep
+// (ens_wsweep_with, ensemble_observers.h) do per step.  own_clamp: the call brought a clamp per world.
+template <class P, class Launch> hipError_t ens_enqueue_sweep_step(EnsembleState<P>* e, bool own_clamp, int step, Launch& launch) {
+  typename P::Args a = ens_args(e);
+  if (own_clamp) P::sweep_route(a, e->params);
+  a.pos_out = e->pos[1 - e->cur];
+  a.vel = e->vel;
+  a.sweep = e->sweep_dev.p;
+  a.step = step;
+  const hipError_t h = launch(a);
+  if (h != hipSuccess) return h;
+  e->cur = 1 - e->cur;
+  ++e->updates;
+  return hipSuccess;
+}
+
+// The worlds' entries of a sweep's table from the call's arrays, on their way to the device (the copy is enqueued, not waited for).
+template <class P> int ens_sweep_table(EnsembleState<P>* e, const typename P::Real* delta, const float* clamp, const int32_t* steps, int n_steps) {
+  const size_t n = (size_t)e->n_worlds, bytes = n * sizeof(typename P::SweepWorld);
+  e->sweep_host.resize(n);  // (the handle's: the copy below may still read it when an error returns early)
+  for (size_t k = 0; k < n; ++k) e->sweep_host[k] = P::sweep_world(delta[k], clamp ? clamp[k] : e->params.clamp, steps ? steps[k] : n_steps);
+  if (int rc = e->sweep_dev.grow(e, bytes)) return rc;
+  const hipError_t h = hipMemcpyAsync(e->sweep_dev.p, e->sweep_host.data(), bytes, hipMemcpyHostToDevice, e->stream);
+  return h == hipSuccess ? NBODY_OK : ens_fail_hip<P>(e, h, "upload of the sweep's table");
+}
+
 // n_steps steps; `launch(args)` enqueues one step (or one force evaluation) of every world on e->stream and returns a hipError_t.
 template <class P, class Launch>
 int ens_update_with(EnsembleState<P>* e, typename P::Real delta, int n_steps, nbody_counting* counter, Launch launch) {
@@ -370,22 +401,8 @@ int ens_sweep_with(EnsembleState<P>* e, const typename P::Real* delta, const flo
   if (n_steps == 0) return NBODY_OK;
   ENS_HIPCHK(e, hipSetDevice(e->device));
   const double t_begin = now_s();
-  const size_t n = (size_t)e->n_worlds, bytes = n * sizeof(typename P::SweepWorld);
-  e->sweep_host.resize(n);  // (the handle's: the copy below may still read it when an error returns early)
-  for (size_t k = 0; k < n; ++k) e->sweep_host[k] = P::sweep_world(delta[k], clamp ? clamp[k] : e->params.clamp, steps ? steps[k] : n_steps);
-  if (int rc = e->sweep_dev.grow(e, bytes)) return rc;
-  ENS_HIPCHK(e, hipMemcpyAsync(e->sweep_dev.p, e->sweep_host.data(), bytes, hipMemcpyHostToDevice, e->stream));
-  for (int step = 0; step < n_steps; ++step) {
-    typename P::Args a = ens_args(e);
-    if (clamp) P::sweep_route(a, e->params);
-    a.pos_out = e->pos[1 - e->cur];
-    a.vel = e->vel;
-    a.sweep = e->sweep_dev.p;
-    a.step = step;
-    ENS_HIPCHK(e, launch(a));
-    e->cur = 1 - e->cur;
-    ++e->updates;
-  }
+  if (int rc = ens_sweep_table(e, delta, clamp, steps, n_steps)) return rc;
+  for (int step = 0; step < n_steps; ++step) ENS_HIPCHK(e, ens_enqueue_sweep_step(e, clamp != nullptr, step, launch));
   ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
   const double dt = now_s() - t_begin;  // booked as an update's seconds are
   e->counting.sum_gravity += dt;

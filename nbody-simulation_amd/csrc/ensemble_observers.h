@@ -6,7 +6,9 @@
 //   ens_encounters  nbody_encounters_*  nearest neighbours and clamped pairs per world     (ensemble_encounters.h)
 // Each is synchronous on the handle's stream, writes no simulation state, refuses before it allocates or launches anything, and
 // keeps its device scratch in the state.  And the one call that observes while it steps:
-//   ens_watch_with  nbody_watch_*       an update sampled before, between and after its steps    (ensemble_watch.h)  What differs between the handles is where their rows are: one WorldRows, which the
+//   ens_watch_with  nbody_watch_*       an update sampled before, between and after its steps    (ensemble_watch.h)
+//   ens_wsweep_with nbody_wsweep_*      a sweep sampled so, on every world's own schedule        (ensemble_watch.h)
+// What differs between the handles is where their rows are: one WorldRows, which the
 // ragged, restricted and ragged restricted drivers each make in one function (ragged_rows, rst_rows, rr_rows).  What a call
 // wants of those rows — the bodies or the tracers, the tracers painted or not — is the call's own argument.
 #pragma once
@@ -372,6 +374,77 @@ int ens_encounters(EnsembleState<P>* e, uint32_t flags, const float* limit2, nbo
 template <class Real> struct WatchRowsOf { using type = nbody_watch_rows_f32; };
 template <> struct WatchRowsOf<double> { using type = nbody_watch_rows_f64; };
 
+// The scratch of a watched run and the two argument structs over it: the records, the six running rows per target, the call's
+// limit2[] (host, [n_worlds], or NULL: params.clamp) on its way to the device.  a.pos is the caller's to set before every launch.
+struct WatchScratch {
+  EncounterArgs a;
+  WatchRun w;
+  int64_t n_tiles = 0;
+  size_t targets = 0;  // of all worlds (<= 2^26)
+};
+template <class P>
+int ens_watch_scratch(EnsembleState<P>* e, bool tracers, const float* limit2, uint32_t height, const WorldRows<P>& rows, WatchScratch& ws) {
+  using Real = typename P::Real;
+  const size_t n = (size_t)e->n_worlds;
+  int64_t n_tiles;
+  if (rows.sizes) {
+    if (int rc = ens_world_table(e, rows)) return rc;
+    n_tiles = tracers ? e->table.enc_tracer_tiles : e->table.enc_body_tiles;
+  } else {
+    n_tiles = e->n_worlds * (int64_t)encounter_tiles((uint32_t)(tracers ? rows.n_tracers : e->n_bodies));
+  }
+  const size_t t = (size_t)(tracers ? rows.tracer_rows : e->rows);
+  if (int rc = e->watch_out.grow(e, n * sizeof(nbody_world_watch))) return rc;
+  if (t) {
+    if (int rc = e->watch_d2.grow(e, t * sizeof(Real))) return rc;
+    if (int rc = e->watch_index.grow(e, t * sizeof(int32_t))) return rc;
+    if (int rc = e->watch_sample.grow(e, t * sizeof(uint32_t))) return rc;
+    if (int rc = e->watch_first_close.grow(e, t * sizeof(uint32_t))) return rc;
+    if (int rc = e->watch_close_samples.grow(e, t * sizeof(uint32_t))) return rc;
+    if (int rc = e->watch_first_out.grow(e, t * sizeof(uint32_t))) return rc;
+  }
+  if (limit2) {
+    if (int rc = e->watch_limit.grow(e, n * sizeof(float))) return rc;
+    ENS_HIPCHK(e, hipMemcpyAsync(e->watch_limit.p, limit2, n * sizeof(float), hipMemcpyHostToDevice, e->stream));
+  }
+  EncounterArgs& a = ws.a;
+  a.tpos = rows.tpos;
+  a.table = rows.sizes ? e->table.worlds : nullptr;
+  a.tile_base = rows.sizes ? e->table.enc_tile_base + (tracers ? n + 1 : 0) : nullptr;
+  a.limit2 = limit2 ? e->watch_limit.p : nullptr;
+  a.limit_all = e->params.clamp;
+  a.n_bodies = (uint32_t)e->n_bodies;
+  a.n_tracers = (uint32_t)rows.n_tracers;
+  a.n_worlds = (uint32_t)e->n_worlds;
+  a.tracers = tracers ? 1u : 0u;
+  WatchRun& w = ws.w;
+  w.min_d2 = e->watch_d2.p;
+  w.min_index = e->watch_index.p;
+  w.min_sample = e->watch_sample.p;
+  w.first_close = e->watch_first_close.p;
+  w.close_samples = e->watch_close_samples.p;
+  w.first_out = e->watch_first_out.p;
+  w.height = height;
+  ws.n_tiles = n_tiles;
+  ws.targets = t;
+  return NBODY_OK;
+}
+
+// The running rows of all t targets into the caller's arrays, each of which may be NULL (enqueued, not waited for).
+template <class P> int ens_watch_copy_rows(EnsembleState<P>* e, const typename WatchRowsOf<typename P::Real>::type* out_rows, size_t t) {
+  using Real = typename P::Real;
+  const auto copy = [&](void* dst, const void* src, size_t bytes) {
+    return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream) : hipSuccess;
+  };
+  ENS_HIPCHK(e, copy(out_rows->min_d2, e->watch_d2.p, t * sizeof(Real)));
+  ENS_HIPCHK(e, copy(out_rows->min_index, e->watch_index.p, t * sizeof(int32_t)));
+  ENS_HIPCHK(e, copy(out_rows->min_sample, e->watch_sample.p, t * sizeof(uint32_t)));
+  ENS_HIPCHK(e, copy(out_rows->first_close, e->watch_first_close.p, t * sizeof(uint32_t)));
+  ENS_HIPCHK(e, copy(out_rows->close_samples, e->watch_close_samples.p, t * sizeof(uint32_t)));
+  ENS_HIPCHK(e, copy(out_rows->first_out, e->watch_first_out.p, t * sizeof(uint32_t)));
+  return NBODY_OK;
+}
+
 // out: [n_worlds] records; out_rows: NULL or the six arrays, each NULL or one entry per target of all worlds.  `launch(args)` as
 // in ens_update_with, and the steps are enqueued as it enqueues them: the run is an update's, bit for bit.  One sampling launch
 // per taken sample, one reduce at the end, one synchronise; no loop over worlds but, once per upload, a ragged handle's table.
@@ -394,45 +467,12 @@ int ens_watch_with(EnsembleState<P>* e, uint32_t flags, typename P::Real delta, 
   ENS_HIPCHK(e, hipSetDevice(e->device));
   const double t_begin = now_s();
   const size_t n = (size_t)e->n_worlds;
-  int64_t n_tiles;
-  if (rows.sizes) {
-    if (int rc = ens_world_table(e, rows)) return rc;
-    n_tiles = tracers ? e->table.enc_tracer_tiles : e->table.enc_body_tiles;
-  } else {
-    n_tiles = e->n_worlds * (int64_t)encounter_tiles((uint32_t)(tracers ? rows.n_tracers : e->n_bodies));
-  }
-  const size_t t = (size_t)(tracers ? rows.tracer_rows : e->rows);  // the targets (<= 2^26)
-  if (int rc = e->watch_out.grow(e, n * sizeof(nbody_world_watch))) return rc;
-  if (t) {
-    if (int rc = e->watch_d2.grow(e, t * sizeof(Real))) return rc;
-    if (int rc = e->watch_index.grow(e, t * sizeof(int32_t))) return rc;
-    if (int rc = e->watch_sample.grow(e, t * sizeof(uint32_t))) return rc;
-    if (int rc = e->watch_first_close.grow(e, t * sizeof(uint32_t))) return rc;
-    if (int rc = e->watch_close_samples.grow(e, t * sizeof(uint32_t))) return rc;
-    if (int rc = e->watch_first_out.grow(e, t * sizeof(uint32_t))) return rc;
-  }
-  if (limit2) {
-    if (int rc = e->watch_limit.grow(e, n * sizeof(float))) return rc;
-    ENS_HIPCHK(e, hipMemcpyAsync(e->watch_limit.p, limit2, n * sizeof(float), hipMemcpyHostToDevice, e->stream));
-  }
-  EncounterArgs a;
-  a.tpos = rows.tpos;
-  a.table = rows.sizes ? e->table.worlds : nullptr;
-  a.tile_base = rows.sizes ? e->table.enc_tile_base + (tracers ? n + 1 : 0) : nullptr;
-  a.limit2 = limit2 ? e->watch_limit.p : nullptr;
-  a.limit_all = e->params.clamp;
-  a.n_bodies = (uint32_t)e->n_bodies;
-  a.n_tracers = (uint32_t)rows.n_tracers;
-  a.n_worlds = (uint32_t)e->n_worlds;
-  a.tracers = tracers ? 1u : 0u;
-  WatchRun w;
-  w.min_d2 = e->watch_d2.p;
-  w.min_index = e->watch_index.p;
-  w.min_sample = e->watch_sample.p;
-  w.first_close = e->watch_first_close.p;
-  w.close_samples = e->watch_close_samples.p;
-  w.first_out = e->watch_first_out.p;
-  w.height = height;
+  WatchScratch ws;
+  if (int rc = ens_watch_scratch(e, tracers, limit2, height, rows, ws)) return rc;
+  EncounterArgs& a = ws.a;
+  WatchRun& w = ws.w;
+  const int64_t n_tiles = ws.n_tiles;
+  const size_t t = ws.targets;
   const int per_lane = lab_int("NBODY_WATCH_PER_LANE", kWatchPerLane);
   uint32_t samples = 0;
   for (int s = 0;; ++s) {
@@ -449,17 +489,8 @@ int ens_watch_with(EnsembleState<P>* e, uint32_t flags, typename P::Real delta, 
   a.pos = e->pos[e->cur];
   ENS_HIPCHK(e, launch_ensemble_watch_worlds<Real>(e->stream, a, w, samples, e->watch_out.p));
   ENS_HIPCHK(e, hipMemcpyAsync(out, e->watch_out.p, n * sizeof(nbody_world_watch), hipMemcpyDeviceToHost, e->stream));
-  if (t && out_rows && samples) {
-    const auto copy = [&](void* dst, const void* src, size_t bytes) {
-      return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream) : hipSuccess;
-    };
-    ENS_HIPCHK(e, copy(out_rows->min_d2, e->watch_d2.p, t * sizeof(Real)));
-    ENS_HIPCHK(e, copy(out_rows->min_index, e->watch_index.p, t * sizeof(int32_t)));
-    ENS_HIPCHK(e, copy(out_rows->min_sample, e->watch_sample.p, t * sizeof(uint32_t)));
-    ENS_HIPCHK(e, copy(out_rows->first_close, e->watch_first_close.p, t * sizeof(uint32_t)));
-    ENS_HIPCHK(e, copy(out_rows->close_samples, e->watch_close_samples.p, t * sizeof(uint32_t)));
-    ENS_HIPCHK(e, copy(out_rows->first_out, e->watch_first_out.p, t * sizeof(uint32_t)));
-  }
+  if (t && out_rows && samples)
+    if (int rc = ens_watch_copy_rows(e, out_rows, t)) return rc;
   ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
   if (t && out_rows && !samples) {  // no sample was taken: the device rows were never written, every target is as it began
     if (out_rows->min_d2) std::fill(out_rows->min_d2, out_rows->min_d2 + t, std::numeric_limits<Real>::infinity());
@@ -472,6 +503,91 @@ int ens_watch_with(EnsembleState<P>* e, uint32_t flags, typename P::Real delta, 
   const double dt = now_s() - t_begin;  // booked as an update's seconds are
   e->counting.sum_gravity += dt;
   if (counter) counter->sum_gravity += dt;
+  return NBODY_OK;
+}
+
+// ---- a watched sweep: a sweep (ens_sweep_with) watched as ens_watch_with watches an update, every world on a schedule of its
+// own: sample s of world k iff s <= steps[k], s % stride[k] == 0 and not (s == 0 under NBODY_WATCH_RESUME).  The steps are the
+// sweep's (ens_enqueue_sweep_step over its table), the scratch is the watch's, and the schedules are one WatchWorld per world on
+// the device.  One sampling launch at every s that some world takes — the host asks WatchSchedule::any, it does not walk the
+// samples — one reduce, one synchronise.  limit2 NULL: world k's limit is clamp[k]; both NULL: params.clamp.
+template <class P, class Launch>
+int ens_wsweep_with(EnsembleState<P>* e, uint32_t flags, const typename P::Real* delta, const float* clamp, const int32_t* steps, int n_steps,
+                    const int32_t* stride, const float* limit2, uint32_t height, nbody_world_watch* out,
+                    const typename WatchRowsOf<typename P::Real>::type* out_rows, nbody_counting* counter, const WorldRows<P>& rows, Launch launch) {
+  using Real = typename P::Real;
+  if (!e) return NBODY_ERR_INVALID;
+  const std::string who = std::string(P::kWho) + " wsweep: ";
+  if (!e->n_worlds) return ens_fail(e, NBODY_ERR_INVALID, who + "nothing uploaded");
+  if (!out) return ens_fail(e, NBODY_ERR_INVALID, who + "out is NULL");
+  if (!delta) return ens_fail(e, NBODY_ERR_INVALID, who + "delta is NULL");
+  const bool tracers = (flags & NBODY_WATCH_TRACERS) != 0;
+  int64_t k = 0;
+  switch (WatchSchedule::check(e->n_worlds, steps, n_steps, stride, flags, &k)) {
+    case WatchSchedule::kOk: break;
+    case WatchSchedule::kBadFlags: return ens_fail(e, NBODY_ERR_INVALID, who + "unknown flag bits");
+    case WatchSchedule::kStepOutside:
+      return ens_fail(e, NBODY_ERR_INVALID, who + "steps[" + std::to_string(k) + "] = " + std::to_string(steps[k]) + " of world " + std::to_string(k) +
+                                                " is outside 0 .. n_steps = " + std::to_string(n_steps));
+    case WatchSchedule::kBadStride:
+      return ens_fail(e, NBODY_ERR_INVALID, who + "stride[" + std::to_string(k) + "] = " + std::to_string(stride[k]) + " of world " +
+                                                std::to_string(k) + " must be >= 1");
+    default: return ens_fail(e, NBODY_ERR_INVALID, who + "n_steps < 0");
+  }
+  if (tracers && !rows.has_tracer_calls) return ens_fail(e, NBODY_ERR_INVALID, who + "NBODY_WATCH_TRACERS on a handle without tracers");
+  if (height > kWatchMaxHeight) return ens_fail(e, NBODY_ERR_INVALID, who + "height must be <= 2^24");
+
+  ENS_HIPCHK(e, hipSetDevice(e->device));
+  const double t_begin = now_s();
+  const size_t n = (size_t)e->n_worlds;
+  WatchScratch ws;
+  if (int rc = ens_watch_scratch(e, tracers, limit2 ? limit2 : clamp, height, rows, ws)) return rc;
+  e->watch_sched_host.resize(n);  // (the handle's, as the sweep's table is)
+  WatchSchedule schedule;
+  schedule.build(e->n_worlds, steps, n_steps, stride, flags, e->watch_sched_host.data());
+  if (int rc = e->watch_sched.grow(e, n * sizeof(WatchWorld))) return rc;
+  ENS_HIPCHK(e, hipMemcpyAsync(e->watch_sched.p, e->watch_sched_host.data(), n * sizeof(WatchWorld), hipMemcpyHostToDevice, e->stream));
+  if (n_steps > 0)
+    if (int rc = ens_sweep_table(e, delta, clamp, steps, n_steps)) return rc;
+  for (int s = 0;; ++s) {
+    if (schedule.any(s)) {
+      ws.a.pos = e->pos[e->cur];  // (the tracers are stepped in place)
+      ws.w.sample = (uint32_t)s;
+      ENS_HIPCHK(e, launch_ensemble_watch_sample<Real>(e->stream, ws.a, ws.w, ws.n_tiles, kWatchPerLane, e->watch_sched.p));
+    }
+    if (s == n_steps) break;
+    ENS_HIPCHK(e, ens_enqueue_sweep_step(e, clamp != nullptr, s, launch));
+  }
+  ws.a.pos = e->pos[e->cur];
+  ENS_HIPCHK(e, launch_ensemble_watch_worlds<Real>(e->stream, ws.a, ws.w, 0u, e->watch_out.p, e->watch_sched.p));
+  ENS_HIPCHK(e, hipMemcpyAsync(out, e->watch_out.p, n * sizeof(nbody_world_watch), hipMemcpyDeviceToHost, e->stream));
+  if (ws.targets && out_rows)  // (the reduce has written the rows of the worlds that took no sample)
+    if (int rc = ens_watch_copy_rows(e, out_rows, ws.targets)) return rc;
+  ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
+  const double dt = now_s() - t_begin;  // booked as an update's seconds are
+  e->counting.sum_gravity += dt;
+  if (counter) counter->sum_gravity += dt;
+  return NBODY_OK;
+}
+
+// The schedules of a watched sweep as the ABI shows them (nbody_wsweep_plan): pure host code, the call's own refusals, no message.
+inline int wsweep_show_plan(int64_t n_worlds, const int32_t* steps, int n_steps, const int32_t* stride, uint32_t flags, int64_t* samples_of_world,
+                            int64_t* n_sampling_launches) {
+  int64_t k = 0;
+  if (WatchSchedule::check(n_worlds, steps, n_steps, stride, flags, &k) != WatchSchedule::kOk) return NBODY_ERR_INVALID;
+  WatchSchedule schedule;
+  schedule.build(n_worlds, steps, n_steps, stride, flags, nullptr);
+  if (samples_of_world)
+    for (k = 0; k < n_worlds; ++k)
+      samples_of_world[k] = WatchSchedule::world(steps ? steps[k] : n_steps, stride ? stride[k] : 1, schedule.resume).samples;
+  if (n_sampling_launches) {
+    int64_t launches = 0;
+    for (int s = 0;; ++s) {
+      launches += schedule.any(s) ? 1 : 0;
+      if (s == n_steps) break;
+    }
+    *n_sampling_launches = launches;
+  }
   return NBODY_OK;
 }
 

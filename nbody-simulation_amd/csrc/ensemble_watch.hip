@@ -12,8 +12,13 @@
 // targets' running rows and evaluates within_bounds of their positions: rows that no other lane touches, in stream order.
 // ensemble_watch_worlds: one block per world over its targets' running rows; lane to lane by shuffles, wave to wave through LDS.
 // No floating-point atomics; nothing is read back between the launches.
+// Both kernels are instantiated twice: over WatchEvery for the plain watch, and over WatchTable for a watched sweep, whose
+// worlds keep schedules of their own (ensemble_watch.h).  What differs is behind `if constexpr`: the plain instantiation reads
+// no table and is the code it was.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "driver.h"
 #include "ensemble_encounter_device.h"
@@ -36,12 +41,13 @@ template <class T> __device__ __forceinline__ void watch_pair(T xi, T yi, T sx, 
 }
 
 // A target's sample folded into its running row.  (best, idx): the sample's nearest live source, idx < 0: none.
+// first: this is the first taken sample of the target's world in the call.
 template <class T>
-__device__ __forceinline__ void watch_fold(const WatchRun& w, size_t row, T best, int32_t idx, T limit, bool out) {
+__device__ __forceinline__ void watch_fold(const WatchRun& w, uint32_t first, size_t row, T best, int32_t idx, T limit, bool out) {
   T* const min_d2 = reinterpret_cast<T*>(w.min_d2);
   const bool has = idx >= 0;
   const bool close = has & (best < limit);  // (a NaN or zero limit is never close; a live d2 is never NaN)
-  if (w.first) {
+  if (first) {
     min_d2[row] = best;  // (+inf, -1 without a live pair)
     w.min_index[row] = idx;
     w.min_sample[row] = has ? w.sample : NBODY_WATCH_NEVER;
@@ -62,8 +68,17 @@ __device__ __forceinline__ void watch_fold(const WatchRun& w, size_t row, T best
   if (out && w.first_out[row] == NBODY_WATCH_NEVER) w.first_out[row] = w.sample;
 }
 
-template <class T, int kPerLane>
-__global__ __launch_bounds__(kEncounterBlock / kPerLane) void ensemble_watch_sample(const EncounterArgs a, const WatchRun w, uint64_t n_items) {
+// Does the world of a work item take the launch's sample w.sample, and is it the world's first?  The world is the same in every
+// lane of the block, so its entry arrives by one scalar load and the answer is the block's.
+__device__ __forceinline__ bool watch_takes(const WatchTable& t, const WatchRun& w, uint32_t world, bool& first) {
+  const uint4 e = reinterpret_cast<const uint4*>(t.worlds)[__builtin_amdgcn_readfirstlane(world)];  // (says "uniform" to the compiler)
+  first = w.sample == e.z;
+  return w.sample >= e.z && w.sample <= e.y && w.sample % e.x == 0u;  // (first = NEVER: never; steps < 2^31 as unsigned)
+}
+
+template <class T, int kPerLane, class Sched>
+__global__ __launch_bounds__(kEncounterBlock / kPerLane) void ensemble_watch_sample(const EncounterArgs a, const WatchRun w, uint64_t n_items,
+                                                                                    const Sched sched) {
   using T2 = typename EncounterTypes<T>::Vec2;
   constexpr int kThreads = kEncounterBlock / kPerLane;
   __shared__ __attribute__((aligned(16))) T2 staged[kEncounterChunk];
@@ -74,6 +89,12 @@ __global__ __launch_bounds__(kEncounterBlock / kPerLane) void ensemble_watch_sam
 
   for (uint64_t item = blockIdx.x; item < n_items; item += gridDim.x) {
     const EncounterSeg s = encounter_item(a, item);
+    uint32_t first = w.first;
+    if constexpr (!std::is_same_v<Sched, WatchEvery>) {
+      bool own_first;
+      if (!watch_takes(sched, w, s.world, own_first)) continue;  // (the whole block: before any staging or barrier)
+      first = own_first ? 1u : 0u;
+    }
     const T limit = encounter_limit<T>(a, s.world);
     uint32_t t[kPerLane];
     T xi[kPerLane], yi[kPerLane], best[kPerLane];
@@ -123,7 +144,7 @@ __global__ __launch_bounds__(kEncounterBlock / kPerLane) void ensemble_watch_sam
     for (int r = 0; r < kPerLane; ++r) {
       if (t[r] >= s.n_tgt) continue;
       const bool inside = yi[r] < h && xi[r] < h && yi[r] >= (T)0 && xi[r] >= (T)0;  // within_bounds; NaN fails
-      watch_fold<T>(w, s.tgt0 + t[r], best[r], idx[r], limit, !inside);
+      watch_fold<T>(w, first, s.tgt0 + t[r], best[r], idx[r], limit, !inside);
     }
   }
 }
@@ -172,22 +193,32 @@ __device__ __forceinline__ WatchPart watch_from_lane(const WatchPart& p, int d) 
 
 __device__ __forceinline__ int64_t watch_sample_or_none(uint32_t s) { return s == NBODY_WATCH_NEVER ? -1 : (int64_t)s; }
 
-template <class T>
-__global__ __launch_bounds__(kEncounterBlock) void ensemble_watch_worlds(const EncounterArgs a, const WatchRun w, uint32_t samples,
-                                                                         nbody_world_watch* __restrict__ out) {
+template <class T, class Sched>
+__global__ __launch_bounds__(kEncounterBlock) void ensemble_watch_worlds(const EncounterArgs a, const WatchRun w, uint32_t samples_all,
+                                                                         nbody_world_watch* __restrict__ out, const Sched sched) {
   __shared__ WatchPart waves[kEncounterBlock / 64];
   const uint32_t l = threadIdx.x;
-  const T* const min_d2 = reinterpret_cast<const T*>(w.min_d2);
+  T* const min_d2 = reinterpret_cast<T*>(w.min_d2);
   for (uint32_t world = blockIdx.x; world < a.n_worlds; world += gridDim.x) {
     EncounterSeg s;
     encounter_rows(a, world, s);
+    uint32_t samples = samples_all;
+    if constexpr (!std::is_same_v<Sched, WatchEvery>) samples = sched.worlds[world].samples;
     WatchPart p = watch_nothing();
     for (uint32_t t = l; t < s.n_tgt; t += (uint32_t)kEncounterBlock) {
+      const size_t row = s.tgt0 + t;
       if (!samples) {  // (no sample was taken: the rows were never written)
         ++p.isolated;
+        if constexpr (!std::is_same_v<Sched, WatchEvery>) {  // a world among others that took some: its rows are the empty ones
+          min_d2[row] = (T)__builtin_huge_val();
+          w.min_index[row] = -1;
+          w.min_sample[row] = NBODY_WATCH_NEVER;
+          w.first_close[row] = NBODY_WATCH_NEVER;
+          w.close_samples[row] = 0u;
+          w.first_out[row] = NBODY_WATCH_NEVER;
+        }
         continue;
       }
-      const size_t row = s.tgt0 + t;
       const uint32_t near = w.close_samples[row], fc = w.first_close[row], fo = w.first_out[row];
       p.close_rows += near ? 1u : 0u;
       p.close_row_samples += near;
@@ -255,36 +286,46 @@ bool watch_rows_missing(const WatchRun& w) {
 
 }  // namespace
 
-template <class T> hipError_t launch_ensemble_watch_sample(hipStream_t s, EncounterArgs a, const WatchRun& w, int64_t n_tiles, int per_lane) {
+template <class T>
+hipError_t launch_ensemble_watch_sample(hipStream_t s, EncounterArgs a, const WatchRun& w, int64_t n_tiles, int per_lane, const WatchWorld* sched) {
   if (hipError_t h = watch_args(a, n_tiles)) return h;
   if (n_tiles == 0) return hipSuccess;
   if (watch_rows_missing(w) || (a.tracers && !a.tpos) || w.height > kWatchMaxHeight) return hipErrorInvalidValue;
   const unsigned grid = (unsigned)(n_tiles < (int64_t)kEncounterMaxGrid ? n_tiles : (int64_t)kEncounterMaxGrid);
-  if (per_lane == kWatchPerLane) {
-    hipLaunchKernelGGL((ensemble_watch_sample<T, kWatchPerLane>), dim3(grid), dim3(kEncounterBlock / kWatchPerLane), 0, s, a, w, (uint64_t)n_tiles);
+  if (sched) {  // a watched sweep: the product's targets per lane in both builds
+    hipLaunchKernelGGL((ensemble_watch_sample<T, kWatchPerLane, WatchTable>), dim3(grid), dim3(kEncounterBlock / kWatchPerLane), 0, s, a, w,
+                       (uint64_t)n_tiles, WatchTable{sched});
+  } else if (per_lane == kWatchPerLane) {
+    hipLaunchKernelGGL((ensemble_watch_sample<T, kWatchPerLane, WatchEvery>), dim3(grid), dim3(kEncounterBlock / kWatchPerLane), 0, s, a, w,
+                       (uint64_t)n_tiles, WatchEvery{});
   } else if (kLabBuild && (per_lane == 1 || per_lane == 2)) {
     if constexpr (kLabBuild)
-      hipLaunchKernelGGL((ensemble_watch_sample<T, 3 - kWatchPerLane>), dim3(grid), dim3(kEncounterBlock / (3 - kWatchPerLane)), 0, s, a, w,
-                         (uint64_t)n_tiles);
+      hipLaunchKernelGGL((ensemble_watch_sample<T, 3 - kWatchPerLane, WatchEvery>), dim3(grid), dim3(kEncounterBlock / (3 - kWatchPerLane)), 0, s, a,
+                         w, (uint64_t)n_tiles, WatchEvery{});
   } else {
     return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
 
-template <class T> hipError_t launch_ensemble_watch_worlds(hipStream_t s, EncounterArgs a, const WatchRun& w, uint32_t samples, nbody_world_watch* out) {
+template <class T>
+hipError_t launch_ensemble_watch_worlds(hipStream_t s, EncounterArgs a, const WatchRun& w, uint32_t samples, nbody_world_watch* out,
+                                        const WatchWorld* sched) {
   if (!out || a.n_worlds < 1 || (int64_t)a.n_worlds > (1ll << 26)) return hipErrorInvalidValue;
   if (a.table ? !a.tile_base : a.n_bodies < 1) return hipErrorInvalidValue;
   const uint64_t rows = a.table ? 0 : (uint64_t)(a.tracers ? a.n_tracers : a.n_bodies) * a.n_worlds;  // (a table's rows: its builder knows them)
-  if (samples && rows && watch_rows_missing(w)) return hipErrorInvalidValue;
+  if ((samples || sched) && rows && watch_rows_missing(w)) return hipErrorInvalidValue;
   const unsigned grid = a.n_worlds < kEncounterMaxGrid ? a.n_worlds : kEncounterMaxGrid;
-  hipLaunchKernelGGL(ensemble_watch_worlds<T>, dim3(grid), dim3(kEncounterBlock), 0, s, a, w, samples, out);
+  if (sched)
+    hipLaunchKernelGGL((ensemble_watch_worlds<T, WatchTable>), dim3(grid), dim3(kEncounterBlock), 0, s, a, w, 0u, out, WatchTable{sched});
+  else
+    hipLaunchKernelGGL((ensemble_watch_worlds<T, WatchEvery>), dim3(grid), dim3(kEncounterBlock), 0, s, a, w, samples, out, WatchEvery{});
   return hipGetLastError();
 }
 
-template hipError_t launch_ensemble_watch_sample<float>(hipStream_t, EncounterArgs, const WatchRun&, int64_t, int);
-template hipError_t launch_ensemble_watch_sample<double>(hipStream_t, EncounterArgs, const WatchRun&, int64_t, int);
-template hipError_t launch_ensemble_watch_worlds<float>(hipStream_t, EncounterArgs, const WatchRun&, uint32_t, nbody_world_watch*);
-template hipError_t launch_ensemble_watch_worlds<double>(hipStream_t, EncounterArgs, const WatchRun&, uint32_t, nbody_world_watch*);
+template hipError_t launch_ensemble_watch_sample<float>(hipStream_t, EncounterArgs, const WatchRun&, int64_t, int, const WatchWorld*);
+template hipError_t launch_ensemble_watch_sample<double>(hipStream_t, EncounterArgs, const WatchRun&, int64_t, int, const WatchWorld*);
+template hipError_t launch_ensemble_watch_worlds<float>(hipStream_t, EncounterArgs, const WatchRun&, uint32_t, nbody_world_watch*, const WatchWorld*);
+template hipError_t launch_ensemble_watch_worlds<double>(hipStream_t, EncounterArgs, const WatchRun&, uint32_t, nbody_world_watch*, const WatchWorld*);
 
 }  // namespace nbody

@@ -68,3 +68,10 @@ NB_API int nbody_watch_ragged64(nbody_ragged64* e, uint32_t flags, double delta,
   return ens_watch_with<RagF64>(e, flags, delta, n_steps, stride, limit2, height, out, rows, counter, ragged_rows<RagF64>(e),
                                 [e](const RagF64::Args& a) { return ragged_launch_all<RagF64>(e, a); });
 }
+// (a sweep sampled on every world's own schedule, ensemble_watch.h: likewise a prefix of its own)
+NB_API int nbody_wsweep_ragged64(nbody_ragged64* e, uint32_t flags, const double* delta, const float* clamp, const int32_t* steps, int n_steps,
+        const int32_t* stride, const float* limit2, uint32_t height, nbody_world_watch* out, const nbody_watch_rows_f64* rows,
+        nbody_counting* counter) {
+  return ens_wsweep_with<RagF64>(e, flags, delta, clamp, steps, n_steps, stride, limit2, height, out, rows, counter, ragged_rows<RagF64>(e),
+        [e](const RagF64::Args& a) { return ragged_launch_all<RagF64>(e, a); });
+}

@@ -67,3 +67,10 @@ NB_API int nbody_watch_restricted(nbody_restricted* e, uint32_t flags, float del
   return ens_watch_with<RstF32>(e, flags, delta, n_steps, stride, limit2, height, out, rows, counter, rst_rows<RstF32>(e),
                                 [e](const RstF32::Args& a) { return rst_launch_step<RstF32>(e, a); });
 }
+// (a sweep sampled on every world's own schedule, ensemble_watch.h: likewise a prefix of its own)
+NB_API int nbody_wsweep_restricted(nbody_restricted* e, uint32_t flags, const float* delta, const float* clamp, const int32_t* steps, int n_steps,
+        const int32_t* stride, const float* limit2, uint32_t height, nbody_world_watch* out, const nbody_watch_rows_f32* rows,
+        nbody_counting* counter) {
+  return ens_wsweep_with<RstF32>(e, flags, delta, clamp, steps, n_steps, stride, limit2, height, out, rows, counter, rst_rows<RstF32>(e),
+        [e](const RstF32::Args& a) { return rst_launch_step<RstF32>(e, a); });
+}

@@ -67,3 +67,10 @@ NB_API int nbody_watch_restricted64(nbody_restricted64* e, uint32_t flags, doubl
   return ens_watch_with<Rst64>(e, flags, delta, n_steps, stride, limit2, height, out, rows, counter, rst_rows<Rst64>(e),
                                [e](const Rst64::Args& a) { return rst_launch_step<Rst64>(e, a); });
 }
+// (a sweep sampled on every world's own schedule, ensemble_watch.h: likewise a prefix of its own)
+NB_API int nbody_wsweep_restricted64(nbody_restricted64* e, uint32_t flags, const double* delta, const float* clamp, const int32_t* steps, int n_steps,
+        const int32_t* stride, const float* limit2, uint32_t height, nbody_world_watch* out, const nbody_watch_rows_f64* rows,
+        nbody_counting* counter) {
+  return ens_wsweep_with<Rst64>(e, flags, delta, clamp, steps, n_steps, stride, limit2, height, out, rows, counter, rst_rows<Rst64>(e),
+        [e](const Rst64::Args& a) { return rst_launch_step<Rst64>(e, a); });
+}

@@ -89,3 +89,10 @@ NB_API int nbody_watch_rr(nbody_rr* e, uint32_t flags, float delta, int n_steps,
   return ens_watch_with<RrF32>(e, flags, delta, n_steps, stride, limit2, height, out, rows, counter, rr_rows<RrF32>(e),
                                [e](const RrF32::Args& a) { return rr_launch_step<RrF32>(e, a); });
 }
+// (a sweep sampled on every world's own schedule, ensemble_watch.h: likewise a prefix of its own)
+NB_API int nbody_wsweep_rr(nbody_rr* e, uint32_t flags, const float* delta, const float* clamp, const int32_t* steps, int n_steps,
+        const int32_t* stride, const float* limit2, uint32_t height, nbody_world_watch* out, const nbody_watch_rows_f32* rows,
+        nbody_counting* counter) {
+  return ens_wsweep_with<RrF32>(e, flags, delta, clamp, steps, n_steps, stride, limit2, height, out, rows, counter, rr_rows<RrF32>(e),
+        [e](const RrF32::Args& a) { return rr_launch_step<RrF32>(e, a); });
+}

@@ -90,3 +90,10 @@ NB_API int nbody_watch_rr64(nbody_rr64* e, uint32_t flags, double delta, int n_s
   return ens_watch_with<RrF64>(e, flags, delta, n_steps, stride, limit2, height, out, rows, counter, rr_rows<RrF64>(e),
                                [e](const RrF64::Args& a) { return rr_launch_step<RrF64>(e, a); });
 }
+// (a sweep sampled on every world's own schedule, ensemble_watch.h: likewise a prefix of its own)
+NB_API int nbody_wsweep_rr64(nbody_rr64* e, uint32_t flags, const double* delta, const float* clamp, const int32_t* steps, int n_steps,
+        const int32_t* stride, const float* limit2, uint32_t height, nbody_world_watch* out, const nbody_watch_rows_f64* rows,
+        nbody_counting* counter) {
+  return ens_wsweep_with<RrF64>(e, flags, delta, clamp, steps, n_steps, stride, limit2, height, out, rows, counter, rr_rows<RrF64>(e),
+        [e](const RrF64::Args& a) { return rr_launch_step<RrF64>(e, a); });
+}

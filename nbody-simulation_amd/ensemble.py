@@ -65,6 +65,12 @@ with a pair closer than limit2[k] and how many samples had one, the first sample
 `WATCH_DTYPE`, without a host synchronisation between the steps; the rows afterwards are those of `update`.  The classes with
 tracers take `tracers=True` for every tracer against its world's bodies.  `watch_merge(first, second, steps_before)` joins a call
 and the `resume=True` call that continued it into what one call gives, bit for bit.
+
+Every class has `watch_sweep(delta, clamp=None, steps=None, n_steps=None, stride=1, limit2=None, height=0)` (nbody_wsweep_*): the
+two together, a `sweep` watched on every world's own schedule — world k is sampled at the s <= steps[k] with s % stride[k] == 0,
+against its own clamp[k] where limit2 is None — with world k's record and rows bit for bit those of `watch` on the same class
+holding world k alone, and the rows afterwards those of `sweep`.  `watch_sweep_plan(steps, n_steps, stride, resume)` gives the
+samples per world and the number of sampling launches of a schedule in host code.
 """
 from __future__ import annotations
 
@@ -85,37 +91,37 @@ def _streams(handle, tracers, key):
     return [buf[int(off[k]):int(off[k + 1])].tobytes() for k in range(off.shape[0] - 1)], step
 
 
-def _checked_sweep(who, b, dtype, delta, clamp, steps, n_steps):
+def _checked_sweep(who, b, dtype, delta, clamp, steps, n_steps, what="sweep"):
     """The arguments of `sweep` for b worlds -> (delta dtype[b], clamp float32[b] or None, steps int32[b] or None, n_steps),
     contiguous; ValueError naming `who` and the argument for anything else.  n_steps defaults to max(steps), or 1 without steps."""
     def per_world(name, a, to):
         a = np.asarray(a)
         if a.ndim != 1 or a.shape[0] != b:
-            raise ValueError(f"{who}.sweep: {name} must hold one value per world ({b} worlds), got shape {a.shape}")
+            raise ValueError(f"{who}.{what}: {name} must hold one value per world ({b} worlds), got shape {a.shape}")
         if a.dtype.kind not in "fiu":
-            raise ValueError(f"{who}.sweep: {name} must be numbers, got {a.dtype}")
+            raise ValueError(f"{who}.{what}: {name} must be numbers, got {a.dtype}")
         return a if to is None else np.ascontiguousarray(a, dtype=to)
     if delta is None:
-        raise ValueError(f"{who}.sweep: delta is required, one time step per world")
+        raise ValueError(f"{who}.{what}: delta is required, one time step per world")
     delta = per_world("delta", delta, dtype)
     if clamp is not None:
         clamp = per_world("clamp", clamp, np.float32)
     if n_steps is not None:
         if isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer)) or not 0 <= int(n_steps) < 1 << 31:
-            raise ValueError(f"{who}.sweep: n_steps must be an integer 0 .. 2^31 - 1, got {n_steps!r}")
+            raise ValueError(f"{who}.{what}: n_steps must be an integer 0 .. 2^31 - 1, got {n_steps!r}")
         n_steps = int(n_steps)
     if steps is not None:
         steps = per_world("steps", steps, None)
         if steps.dtype.kind == "f":
             if not (np.isfinite(steps).all() and (steps == np.floor(steps)).all()):
-                raise ValueError(f"{who}.sweep: steps must be whole numbers")
+                raise ValueError(f"{who}.{what}: steps must be whole numbers")
         top = int(steps.max()) if n_steps is None else n_steps
         if top >= 1 << 31:
-            raise ValueError(f"{who}.sweep: steps must be below 2^31")
+            raise ValueError(f"{who}.{what}: steps must be below 2^31")
         bad = np.flatnonzero((steps < 0) | (steps > top))
         if bad.size:
             k = int(bad[0])
-            raise ValueError(f"{who}.sweep: steps[{k}] = {steps[k]} of world {k} is outside 0 .. n_steps = {top}")
+            raise ValueError(f"{who}.{what}: steps[{k}] = {steps[k]} of world {k} is outside 0 .. n_steps = {top}")
         steps, n_steps = np.ascontiguousarray(steps, dtype=np.int32), top
     return delta, clamp, steps, 1 if n_steps is None else n_steps
 
@@ -296,25 +302,25 @@ WATCH_NEVER = _capi.WATCH_NEVER
 WATCH_ROWS = _capi.WATCH_ROWS
 
 
-def _checked_watch(who, b, dtype, delta, n_steps, limit2, height, stride, rows, resume, tracers):
+def _checked_watch(who, b, dtype, delta, n_steps, limit2, height, stride, rows, resume, tracers, what="watch"):
     """The arguments of `watch` for b worlds -> (delta, n_steps, stride, limit2 float32[b] contiguous or None, height, tracers,
     resume, rows); ValueError naming `who` and the argument for anything else."""
     if isinstance(delta, (bool, np.bool_)) or not isinstance(delta, (int, float, np.integer, np.floating)):
-        raise ValueError(f"{who}.watch: delta must be a number, got {delta!r}")
+        raise ValueError(f"{who}.{what}: delta must be a number, got {delta!r}")
     for name, v, least in (("n_steps", n_steps, 0), ("stride", stride, 1)):
         if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not least <= int(v) < 1 << 31:
-            raise ValueError(f"{who}.watch: {name} must be an integer {least} .. 2^31 - 1, got {v!r}")
+            raise ValueError(f"{who}.{what}: {name} must be an integer {least} .. 2^31 - 1, got {v!r}")
     if isinstance(height, (bool, np.bool_)) or not isinstance(height, (int, np.integer)) or not 0 <= int(height) <= MAX_HEIGHT:
-        raise ValueError(f"{who}.watch: height must be an integer 0 .. 2^24, got {height!r}")
+        raise ValueError(f"{who}.{what}: height must be an integer 0 .. 2^24, got {height!r}")
     for name, flag in (("rows", rows), ("resume", resume), ("tracers", tracers)):
         if not isinstance(flag, (bool, np.bool_)):
-            raise ValueError(f"{who}.watch: {name} must be True or False, got {flag!r}")
+            raise ValueError(f"{who}.{what}: {name} must be True or False, got {flag!r}")
     if limit2 is not None:
         limit2 = np.asarray(limit2)
         if limit2.ndim != 1 or limit2.shape[0] != b:
-            raise ValueError(f"{who}.watch: limit2 must hold one squared distance per world ({b} worlds), got shape {limit2.shape}")
+            raise ValueError(f"{who}.{what}: limit2 must hold one squared distance per world ({b} worlds), got shape {limit2.shape}")
         if limit2.dtype.kind not in "fiu":
-            raise ValueError(f"{who}.watch: limit2 must be real numbers, got {limit2.dtype}")
+            raise ValueError(f"{who}.{what}: limit2 must be real numbers, got {limit2.dtype}")
         with np.errstate(over="ignore"):
             limit2 = np.ascontiguousarray(limit2, dtype=np.float32)
     return float(dtype(delta)), int(n_steps), int(stride), limit2, int(height), bool(tracers), bool(resume), bool(rows)
@@ -423,6 +429,82 @@ class _WatchWithTracers(_Watch):
         return self._watch(delta, n_steps, limit2, height, stride, rows, resume, counter, tracers)
 
 
+def _checked_watch_sweep(who, b, dtype, delta, clamp, steps, n_steps, stride, limit2, height, rows, resume, tracers):
+    """The arguments of `watch_sweep` for b worlds -> (delta dtype[b], clamp float32[b] or None, steps int32[b] or None, n_steps,
+    stride int32[b], limit2 float32[b] or None, height, tracers, resume, rows): the sweep's arguments as `sweep` checks them, the
+    watch's as `watch` does, and stride a whole number >= 1 or one per world; ValueError naming `who` and the argument."""
+    what = "watch_sweep"
+    delta, clamp, steps, n_steps = _checked_sweep(who, b, dtype, delta, clamp, steps, n_steps, what)
+    _, _, _, limit2, height, tracers, resume, rows = _checked_watch(who, b, dtype, 0.0, n_steps, limit2, height, 1, rows, resume, tracers, what)
+    stride = np.asarray(stride)
+    if stride.ndim == 0:
+        stride = np.full(b, stride)
+    if stride.ndim != 1 or stride.shape[0] != b:
+        raise ValueError(f"{who}.{what}: stride must be one number or hold one per world ({b} worlds), got shape {stride.shape}")
+    if stride.dtype.kind not in "iu":
+        raise ValueError(f"{who}.{what}: stride must be integers, got {stride.dtype}")
+    bad = np.flatnonzero((stride < 1) | (stride >= 1 << 31))
+    if bad.size:
+        k = int(bad[0])
+        raise ValueError(f"{who}.{what}: stride[{k}] = {stride[k]} of world {k} must be 1 .. 2^31 - 1")
+    return delta, clamp, steps, n_steps, np.ascontiguousarray(stride, dtype=np.int32), limit2, height, tracers, resume, rows
+
+
+def watch_sweep_plan(steps, n_steps, stride=1, resume=False):
+    """What `watch_sweep(..., steps=steps, n_steps=n_steps, stride=stride, resume=resume)` samples (nbody_wsweep_plan, pure host
+    code, no GPU) -> (samples int64[B], launches): world k's number of samples — steps[k] // stride[k] + 1, one fewer with
+    resume — and the number of s in 0 .. n_steps at which at least one world takes a sample, each of which costs one sampling
+    launch.  steps: [B] integers; stride: one number or [B]."""
+    steps = np.asarray(steps)
+    if steps.ndim != 1 or steps.shape[0] < 1:
+        raise ValueError(f"watch_sweep_plan: steps must hold one number per world, got shape {steps.shape}")
+    b = steps.shape[0]
+    _, _, steps, n_steps, stride, _, _, _, resume, _ = _checked_watch_sweep(
+        "ensemble", b, np.float32, np.zeros(b, np.float32), None, steps, n_steps, stride, None, 0, True, resume, False)
+    return _capi.wsweep_plan(b, steps, n_steps, stride, resume)
+
+
+class _WatchSweep:
+    """`watch_sweep` for the ensemble classes without tracers: what `_Watch` asks of the class, and a handle with `watch_sweep`."""
+
+    def _watch_sweep(self, delta, clamp, steps, n_steps, stride, limit2, height, rows, resume, counter, tracers):
+        delta, clamp, steps, n_steps, stride, limit2, height, tracers, resume, rows = _checked_watch_sweep(
+            type(self).__name__, self._n_worlds, self._dtype, delta, clamp, steps, n_steps, stride, limit2, height, rows, resume, tracers)
+        out, flat = self.h.watch_sweep(delta, clamp, steps, n_steps, stride, limit2, height, tracers, resume, rows, counter)
+        if not rows:
+            return out, None
+        if hasattr(self, "_cuts"):
+            return out, {name: [w.copy() for w in np.split(a, self._tcuts if tracers else self._cuts)] for name, a in flat.items()}
+        return out, {name: a.reshape(self._n_worlds, a.size // self._n_worlds) for name, a in flat.items()}
+
+    def watch_sweep(self, delta, clamp=None, steps=None, n_steps=None, stride=1, limit2=None, height=0, rows=True, resume=False,
+                    counter: Counting | None = None):
+        """sweep(delta, clamp, steps, n_steps=n_steps) with every world sampled on the device on its own schedule
+        (nbody_wsweep_*) -> (records, rows) in the shapes `watch` returns.  World k takes sample s — the state after s steps of
+        this call — iff s <= steps[k], s % stride[k] == 0 and not (s == 0 with resume=True); once it has taken its steps it
+        stands still and is not sampled again, and its record's `samples` is its own steps[k] // stride[k] + 1 (one fewer with
+        resume).  stride: one number or [B].  limit2: None (world k's own clamp[k]; without clamp the constructor's) or one
+        number per world.  n_steps defaults as `sweep`'s does.  World k's record and rows are bit for bit those of this class
+        holding world k alone with clamp[k], from watch(delta[k], steps[k], stride=stride[k], limit2 = limit2[k:k+1] or None);
+        a world that takes no sample has samples == 0 and the empty rows (+inf, -1, WATCH_NEVER, WATCH_NEVER, 0, WATCH_NEVER).
+        The rows afterwards are bit for bit those after sweep(delta, clamp, steps, n_steps=n_steps).  `watch_merge` joins a call
+        and the resume=True call that continued it where every world either ran through the first call on a stride dividing
+        its length or was finished within it; `watch_sweep_plan` says how many samples and sampling launches a schedule costs.
+        The arguments are checked here, with ValueError, before the library is touched."""
+        return self._watch_sweep(delta, clamp, steps, n_steps, stride, limit2, height, rows, resume, counter, False)
+
+
+class _WatchSweepWithTracers(_WatchSweep):
+    """`watch_sweep` for the ensemble classes with tracers."""
+
+    def watch_sweep(self, delta, clamp=None, steps=None, n_steps=None, stride=1, limit2=None, height=0, rows=True, resume=False,
+                    counter: Counting | None = None, tracers=False):
+        """-> (records, rows) as the classes without tracers give them; with tracers=True the targets are every world's tracers
+        and the sources its bodies, on the world's own schedule.  Bodies and tracers are stepped either way.  The arguments are
+        checked here, with ValueError, before the library is touched."""
+        return self._watch_sweep(delta, clamp, steps, n_steps, stride, limit2, height, rows, resume, counter, tracers)
+
+
 class _Sweep:
     """`sweep` for every ensemble class: the class keeps `_n_worlds` and `_dtype`, its handle has `sweep`."""
 
@@ -474,7 +556,7 @@ def _checked(position, velocity, weight, dtype=np.float32, who=None, other=None)
     return b, n, np.ascontiguousarray(position), np.ascontiguousarray(velocity), weight
 
 
-class _EnsembleBase(_Watch, _Encounters, _Summary, _Sweep):
+class _EnsembleBase(_WatchSweep, _Watch, _Encounters, _Summary, _Sweep):
     """What Ensemble, Ensemble64 and the restricted ensembles share; each names its dtype and makes its own kind of handle."""
     _dtype = None
 
@@ -593,7 +675,7 @@ def _checked_tracers(tracers, b, who="RestrictedEnsemble", dtype=np.float32):
     return m, np.ascontiguousarray(tp), np.ascontiguousarray(tv)
 
 
-class _RestrictedBase(_WatchWithTracers, _EncountersWithTracers, _SummaryWithTracers, _EnsembleBase):
+class _RestrictedBase(_WatchSweepWithTracers, _WatchWithTracers, _EncountersWithTracers, _SummaryWithTracers, _EnsembleBase):
     """What RestrictedEnsemble and RestrictedEnsemble64 share: the tracers beside the bodies.  Each names its dtype, makes its own
     kind of handle and says which class takes the other dtype."""
     _other = None
@@ -721,7 +803,7 @@ def _checked_ragged(positions, velocities, weights, dtype=np.float32, who=None, 
     return np.asarray(sizes, np.int64), position, velocity, weight
 
 
-class _RaggedBase(_Watch, _Encounters, _Summary, _Sweep):
+class _RaggedBase(_WatchSweep, _Watch, _Encounters, _Summary, _Sweep):
     """What RaggedEnsemble and RaggedEnsemble64 share; each names its dtype, makes its own kind of handle and has its own
     constructor."""
     _dtype = None
@@ -861,7 +943,7 @@ def _checked_rr_tracers(tracers, sizes, who="RaggedRestrictedEnsemble", dtype=np
     return counts, np.ascontiguousarray(np.concatenate(tps)), np.ascontiguousarray(np.concatenate(tvs))
 
 
-class RaggedRestrictedEnsemble(_WatchWithTracers, _EncountersWithTracers, _SummaryWithTracers, _RaggedBase):
+class RaggedRestrictedEnsemble(_WatchSweepWithTracers, _WatchWithTracers, _EncountersWithTracers, _SummaryWithTracers, _RaggedBase):
     """Worlds of different sizes, each with tracers of its own, stepped together (nbody_rr_*), float32: positions, velocities
     are sequences of [n_k, 2] arrays, weights a sequence of [n_k] integer arrays or None (all 1), tracers None or a list with one
     entry per world, each None or a pair (position[m_k, 2], velocity[m_k, 2]).  1 .. 4096 bodies per world, at most 2^26 bodies
