@@ -1011,4 +1011,59 @@ int nbody_wsweep_plan(int64_t n_worlds, const int32_t* steps /*[n_worlds] or NUL
                       const int32_t* stride /*[n_worlds] or NULL: 1*/, uint32_t flags,
                       int64_t* samples_of_world /*[n_worlds] or NULL*/, int64_t* n_sampling_launches /*or NULL*/);
 
+/* ---- resident runs: small worlds take a call's steps in one launch ----
+ * Every stepping call above pays one launch per step.  A world of at most NBODY_RESIDENT_MAX_BODIES bodies is one block of
+ * that launch in both precisions, the block stages the world whole in LDS and reads nothing another block writes — and yet
+ * every step ends with a write to global memory and a launch boundary, and the next one stages the same rows again.  For a
+ * seed ensemble of three-body scatterings or a time-step convergence study of a few dozen bodies run for 10^4 .. 10^6 steps
+ * that round trip costs more than the step.  A resident run is nbody_sweep_<handle> through another route: one block per world
+ * stages its world once, takes the world's steps of the call in a loop with positions and velocities in LDS, and writes the
+ * rows back once.  The arithmetic of a step is the text the stepping kernels run.
+ *   The prefix.  nbody_resident_<handle> for the four handles without tracers, and nbody_resident_plan: a closed set of five,
+ *     under a prefix of its own.
+ *   Arguments.  nbody_sweep_<handle>'s, word for word: delta [n_worlds] in the handle's precision, required; clamp [n_worlds]
+ *     or NULL (params.clamp in every world); steps [n_worlds] with 0 <= steps[k] <= n_steps, or NULL (every world takes
+ *     n_steps).  The call is stateless: nothing of it stays in the handle.
+ *   Contract.  After the call every bit of the handle's positions and velocities is what it would be after
+ *     nbody_sweep_<handle> with the same arguments, under EXACT, FAST and AUTO; the handle's step count has advanced by n_steps
+ *     and its delta-stream sequences are as after that sweep.  So the sweep's promises hold world by world: EXACT is
+ *     bit-identical to the oracle's update_direct of that world with its own delta, clamp and number of steps; FAST and AUTO are
+ *     bit-identical to that world alone; the route is taken per world from its clamp; the AUTO decision per world and per step
+ *     from the positions at the start of that step; a world that has taken its steps keeps its bits, whatever they are (-0.0,
+ *     NaN payloads, infinities); a world's bits depend on no other world, and not on where the call is cut into launches.
+ *   Launches.  One block of 256 threads per world.  A launch takes at most NBODY_RESIDENT_STEPS_PER_LAUNCH steps of the call,
+ *     so that no single kernel runs long on a shared device: a call whose largest steps[k] is S enqueues
+ *     ceil(S / NBODY_RESIDENT_STEPS_PER_LAUNCH) launches, none with S == 0.  Between launches the rows are in global memory at
+ *     full precision, so the cut is invisible.  The kernels write the rows in place (a block owns its world's rows for the
+ *     whole launch).  No host synchronisation before the end of the call, nothing read back, no device scratch beyond the
+ *     sweep's table and, on a ragged handle, 8 bytes per world (its first row and size), freed with the rows.  The seconds are
+ *     booked under sum_gravity (`counter` may be NULL).
+ *   nbody_resident_plan.  Pure host code, no device, no handle: n_launches as above and lds_bytes, the dynamic LDS of a
+ *     launch, which is that of the largest world — the stepping kernels' layout plus the velocities: 24 bytes per couple of
+ *     bodies + 8 n in f32, 20 bytes per body of the size padded to 8 + 16 n in f64.  Either output may be NULL.
+ *   Refusals.  NBODY_ERR_INVALID before anything is allocated or enqueued, the message beginning with the handle's word
+ *     ("ensemble", "ragged") and naming "resident": nothing uploaded; delta NULL; n_steps < 0; a steps[k] outside [0, n_steps]
+ *     (the message names the world); a world of more than NBODY_RESIDENT_MAX_BODIES bodies (on a ragged handle the message
+ *     names the first such world; the whole call is refused and nothing moves).  n_steps == 0 after the checks is a no-op.  A
+ *     NULL handle gives NBODY_ERR_INVALID without a message.  nbody_resident_plan refuses the same arguments, and n_worlds < 1
+ *     or n_bodies NULL, with NBODY_ERR_INVALID and no message, and then writes nothing.
+ *   Measured (profiles/ensemble_resident.txt: end-to-end call times on an MI355X, 1024 steps, against *_update of the same
+ *     handle).  4096 worlds x 3 bodies: 1.9 ms against 6.0 ms in f32 EXACT, 3.7 against 7.0 ms in f64 FAST; 4096 x 64: 20.5
+ *     against 22.5 ms in f32 EXACT, 5.9 against 8.9 ms in f32 FAST; 1024 x 256: 59.8 against 63.4 ms in f32 EXACT, 90.3 against
+ *     93.1 ms in f64 EXACT, which is the longest full launch recorded.  The gain is the launches and the round trip through
+ *     global memory, so it shrinks as the pairs per step grow: 3.2 x at 3 bodies, 1.03 .. 1.15 x at 256.  A resident run was
+ *     slower than *_update at no recorded shape (the four above and a ragged handle of 1024 worlds of 3 .. 256 bodies, in f32
+ *     and f64, under EXACT and FAST).
+ *   Not offered: worlds above 256 bodies (several blocks of a world would have to meet once per step: nbody_sweep_* is the
+ *     call); the four handles with tracers (a tracer block would have to carry its world's bodies forward itself); several tiny
+ *     worlds packed into one block; a resident watch; anything for nbody_ctx contexts. */
+#define NBODY_RESIDENT_MAX_BODIES 256          /* a world that is one block: tiles == 1 in both precisions */
+#define NBODY_RESIDENT_STEPS_PER_LAUNCH 1024   /* a launch takes at most this many steps of the call */
+int nbody_resident_ensemble  (nbody_ensemble*   e, const float*  delta, const float* clamp, const int32_t* steps, int n_steps, nbody_counting* counter);
+int nbody_resident_ensemble64(nbody_ensemble64* e, const double* delta, const float* clamp, const int32_t* steps, int n_steps, nbody_counting* counter);
+int nbody_resident_ragged    (nbody_ragged*     e, const float*  delta, const float* clamp, const int32_t* steps, int n_steps, nbody_counting* counter);
+int nbody_resident_ragged64  (nbody_ragged64*   e, const double* delta, const float* clamp, const int32_t* steps, int n_steps, nbody_counting* counter);
+int nbody_resident_plan(int64_t n_worlds, const int64_t* n_bodies /*[n_worlds]*/, const int32_t* steps /*[n_worlds] or NULL: n_steps*/,
+                        int n_steps, int is_f64, int32_t* n_launches, int32_t* lds_bytes);
+
 #endif /* NBODY_ENSEMBLE_H */

@@ -11,8 +11,8 @@ There is no CPU fallback: every compute entry point raises if the HIP library or
 """
 from . import _capi  # noqa: F401
 from .world import Counting, World  # noqa: F401
-from .ensemble import Ensemble, Ensemble64, RaggedEnsemble, RaggedEnsemble64, RestrictedEnsemble, RestrictedEnsemble64, RaggedRestrictedEnsemble, RaggedRestrictedEnsemble64, DeltasDecoder, contact_sheet, ragged_plan, rr_plan, summary_of, SUMMARY_DTYPE, encounters_of, ENCOUNTERS_DTYPE, watch_merge, watch_sweep_plan, WATCH_DTYPE, WATCH_NEVER  # noqa: F401
+from .ensemble import Ensemble, Ensemble64, RaggedEnsemble, RaggedEnsemble64, RestrictedEnsemble, RestrictedEnsemble64, RaggedRestrictedEnsemble, RaggedRestrictedEnsemble64, DeltasDecoder, contact_sheet, ragged_plan, rr_plan, resident_plan, summary_of, SUMMARY_DTYPE, encounters_of, ENCOUNTERS_DTYPE, watch_merge, watch_sweep_plan, WATCH_DTYPE, WATCH_NEVER  # noqa: F401
 from ._capi import DeltaDecoder  # noqa: F401
 from . import scenes  # noqa: F401
 
-__all__ = ["World", "Counting", "Ensemble", "Ensemble64", "RaggedEnsemble", "RaggedEnsemble64", "RestrictedEnsemble", "RestrictedEnsemble64", "RaggedRestrictedEnsemble", "RaggedRestrictedEnsemble64", "ragged_plan", "rr_plan", "contact_sheet", "DeltaDecoder", "DeltasDecoder", "summary_of", "SUMMARY_DTYPE", "encounters_of", "ENCOUNTERS_DTYPE", "watch_merge", "watch_sweep_plan", "WATCH_DTYPE", "WATCH_NEVER", "scenes", "_capi"]
+__all__ = ["World", "Counting", "Ensemble", "Ensemble64", "RaggedEnsemble", "RaggedEnsemble64", "RestrictedEnsemble", "RestrictedEnsemble64", "RaggedRestrictedEnsemble", "RaggedRestrictedEnsemble64", "ragged_plan", "rr_plan", "resident_plan", "contact_sheet", "DeltaDecoder", "DeltasDecoder", "summary_of", "SUMMARY_DTYPE", "encounters_of", "ENCOUNTERS_DTYPE", "watch_merge", "watch_sweep_plan", "WATCH_DTYPE", "WATCH_NEVER", "scenes", "_capi"]

@@ -262,6 +262,11 @@ _SIGS = {
                                        C.POINTER(Counting)])
        for h in ("ensemble", "ensemble64", "ragged", "ragged64", "restricted", "restricted64", "rr", "rr64")},
     "nbody_wsweep_plan": (C.c_int, [_i64, C.POINTER(C.c_int32), _i32, C.POINTER(C.c_int32), C.c_uint32, _vp, _vp]),
+    # nbody_resident_<handle>: a sweep's arguments, on the four handles without tracers
+    **{"nbody_resident_" + h: (C.c_int, [_vp, C.POINTER(_f64 if h.endswith("64") else _f32), C.POINTER(_f32), C.POINTER(C.c_int32), _i32,
+                                         C.POINTER(Counting)])
+       for h in ("ensemble", "ensemble64", "ragged", "ragged64")},
+    "nbody_resident_plan": (C.c_int, [_i64, C.POINTER(_i64), C.POINTER(C.c_int32), _i32, _i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "nbody_accel_tree_f32": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_accel_tree_f64": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "nbody_tree_info": (C.c_int, [_vp, C.POINTER(TreeView)]),
@@ -1049,6 +1054,17 @@ class _EnsembleHandleBase:
         self._check(getattr(self.lib, name)(self.h, typed(delta, real), typed(clamp, C.c_float), typed(steps, C.c_int32), int(n_steps),
                                             C.byref(counter) if counter is not None else None))
 
+    def resident(self, delta, clamp, steps, n_steps, counter: "Counting | None" = None):
+        """nbody_resident_<handle> (the four handles without tracers): `sweep`'s arguments, `sweep`'s rows afterwards."""
+        def typed(a, ctype):
+            return None if a is None else a.ctypes.data_as(C.POINTER(ctype))
+        name = "nbody_resident_" + self._prefix[len("nbody_"):]
+        if name not in _SIGS:   # the handles with tracers inherit this method, and the library has no such call for them
+            raise NBodyError(ERR_INVALID, f"{name}: resident runs are not offered on a handle with tracers (sweep is the call)")
+        real = C.c_double if self._dtype == np.float64 else C.c_float
+        self._check(getattr(self.lib, name)(self.h, typed(delta, real), typed(clamp, C.c_float), typed(steps, C.c_int32), int(n_steps),
+                                            C.byref(counter) if counter is not None else None))
+
     _frames_tracers = False   # the handle's nbody_frames_* call takes with_tracers
 
     def frames(self, height, render_px, tracers=False):
@@ -1307,6 +1323,23 @@ def ragged_plan(sizes, f64=False):
         msg = getattr(lib, prefix + "_last_error")(None)
         raise NBodyError(rc, msg.decode() if msg else "")
     return launch, first, lds[:n.value].copy(), blocks[:n.value].copy()
+
+
+RESIDENT_MAX_BODIES, RESIDENT_STEPS_PER_LAUNCH = 256, 1024   # NBODY_RESIDENT_* of include/nbody_ensemble.h
+
+
+def resident_plan(sizes, steps, n_steps, is_f64):
+    """nbody_resident_plan (pure host code): sizes int64[n_worlds], steps int32[n_worlds] or None, contiguous -> (n_launches,
+    lds_bytes) of nbody_resident_<handle> with these arguments; ValueError where the library refuses them."""
+    lib = load()
+    launches, lds = C.c_int32(-1), C.c_int32(-1)
+    rc = lib.nbody_resident_plan(int(sizes.shape[0]), sizes.ctypes.data_as(C.POINTER(_i64)),
+                                 None if steps is None else steps.ctypes.data_as(C.POINTER(C.c_int32)), int(n_steps), 1 if is_f64 else 0,
+                                 C.byref(launches), C.byref(lds))
+    if rc != OK:
+        raise ValueError(f"resident_plan: refused ({sizes.shape[0]} worlds, n_steps = {n_steps}): a world of more than "
+                         f"{RESIDENT_MAX_BODIES} bodies (or none), or a steps[k] outside 0 .. n_steps")
+    return int(launches.value), int(lds.value)
 
 
 def wsweep_plan(n_worlds, steps, n_steps, stride, resume=False):

@@ -63,3 +63,15 @@ NB_API int nbody_wsweep_plan(int64_t n_worlds, const int32_t* steps, int n_steps
                              int64_t* n_sampling_launches) {
   return wsweep_show_plan(n_worlds, steps, n_steps, stride, flags, samples_of_world, n_sampling_launches);
 }
+// (a resident run — that sweep with every world kept in LDS, include/nbody_ensemble.h: likewise a prefix of its own)
+NB_API int nbody_resident_ensemble(nbody_ensemble* e, const float* delta, const float* clamp, const int32_t* steps, int n_steps,
+                                   nbody_counting* counter) {
+  return ens_resident_with<EnsF32>(e, delta, clamp, steps, n_steps, counter);
+}
+// (its launches and their dynamic LDS: pure host code, no handle)
+static_assert(NBODY_RESIDENT_MAX_BODIES == kResidentMaxBodies && NBODY_RESIDENT_STEPS_PER_LAUNCH == kResidentStepsPerLaunch,
+              "the header's constants are the kernels'");
+NB_API int nbody_resident_plan(int64_t n_worlds, const int64_t* n_bodies, const int32_t* steps, int n_steps, int is_f64, int32_t* n_launches,
+                               int32_t* lds_bytes) {
+  return resident_plan(n_worlds, n_bodies, steps, n_steps, is_f64, n_launches, lds_bytes) ? NBODY_ERR_INVALID : NBODY_OK;
+}

@@ -58,3 +58,8 @@ NB_API int nbody_wsweep_ensemble64(nbody_ensemble64* e, uint32_t flags, const do
   return ens_wsweep_with<EnsF64>(e, flags, delta, clamp, steps, n_steps, stride, limit2, height, out, rows, counter, WorldRows<EnsF64>(),
         [e](const EnsF64::Args& a) { return EnsF64::launch(e->stream, e->n_worlds, a); });
 }
+// (a resident run — that sweep with every world kept in LDS, include/nbody_ensemble.h: likewise a prefix of its own)
+NB_API int nbody_resident_ensemble64(nbody_ensemble64* e, const double* delta, const float* clamp, const int32_t* steps, int n_steps,
+                                     nbody_counting* counter) {
+  return ens_resident_with<EnsF64>(e, delta, clamp, steps, n_steps, counter);
+}

@@ -11,7 +11,9 @@
 //   SweepWorld, sweep_world(delta, clamp, steps), sweep_route(args, params)
 //                                  sweeps (ens_sweep_with): a world's entry of the kernels' table, and the call-wide arithmetic
 //                                  where every world brings a clamp of its own (params.arith alone: the clamp's test is the kernels');
-//   launch(stream, n_worlds, args) one step, or one force evaluation, of all worlds.
+//   launch(stream, n_worlds, args) one step, or one force evaluation, of all worlds;
+//   launch_resident(stream, n_worlds, worlds, lds_bytes, args), resident_lds_bytes(n_bodies)
+//                                  resident runs (ens_resident_with): one launch of ensemble_resident.h and a world's dynamic LDS in it.
 // A handle is a struct of its own derived from EnsembleState<P>: the C header declares distinct opaque types.
 // The ragged handle (ragged_driver.h: worlds of different sizes, several launches per step) is built from the same parts: the
 // state, create / destroy, params and errors as they are, and upload, download, update and accel through the *_rows / *_with
@@ -20,11 +22,13 @@
 // under its own kWho, with the tracers' launch added to a step through ens_update_with.
 // This file: the state (with the scratch of every call, each a DevBuf grown on demand and freed with the rows), create /
 // destroy, params, upload / download, and the stepping calls: update, sweep (nbody_sweep_*: a time step, a clamp and a number of
-// steps per world) and accel; ens_enqueue_step and ens_enqueue_sweep_step are one step of either kind, for the watched runs too.
+// steps per world), resident (nbody_resident_*: that sweep with every world kept in LDS for up to 1024 steps of a launch) and
+// accel; ens_enqueue_step and ens_enqueue_sweep_step are one step of either kind, for the watched runs too.
 // The calls that read every world's current rows and return something per world — frames, delta streams, summaries, encounters
 // — and the watched runs are ensemble_observers.h, included at the end: one function each for every handle, told where the
 // handle's rows are by one WorldRows.
 #pragma once
+#include <algorithm>
 #include <cstring>
 #include <new>
 #include <string>
@@ -33,6 +37,7 @@
 #include "driver.h"
 #include "ensemble_deltas.h"
 #include "ensemble_kernels.h"
+#include "ensemble_resident.h"
 #include "ensemble_rows.h"
 #include "ensemble_watch.h"
 
@@ -126,6 +131,9 @@ template <class P> struct EnsembleState {
   // every call, nothing of a sweep outlives it
   std::vector<typename P::SweepWorld> sweep_host;
   DevBuf<typename P::SweepWorld> sweep_dev;
+  // resident runs (ens_resident_with) of a ragged handle: every world's {row0, n}, made by the first such call after an upload
+  std::vector<uint2> resident_host;
+  DevBuf<uint2> resident_worlds;
   // summaries (ens_summary): the records, the chunk records of segments of several chunks and the call's ref[]
   DevBuf<nbody_world_summary> summary_out, summary_chunks;
   DevBuf<int32_t> summary_ref;
@@ -175,6 +183,7 @@ template <class P> void ens_free(EnsembleState<P>* e) {
   e->table.release();
   e->frame_rgba.release(); e->frame_work.release();
   e->sweep_dev.release();
+  e->resident_worlds.release();
   e->summary_out.release(); e->summary_chunks.release(); e->summary_ref.release();
   e->enc_out.release(); e->enc_index.release(); e->enc_d2.release(); e->enc_close.release(); e->enc_live.release(); e->enc_limit.release();
   e->watch_out.release(); e->watch_d2.release(); e->watch_index.release(); e->watch_sample.release(); e->watch_first_close.release();
@@ -380,6 +389,21 @@ template <class P> int ens_update(EnsembleState<P>* e, typename P::Real delta, i
   return ens_update_with(e, delta, n_steps, counter, [e](const typename P::Args& a) { return P::launch(e->stream, e->n_worlds, a); });
 }
 
+// What a sweep refuses of its arguments, for `who` ("<handle's word> sweep: ", or the resident run's): nothing uploaded, no
+// delta, n_steps < 0, a steps[k] outside 0 .. n_steps.
+template <class P>
+int ens_sweep_check(EnsembleState<P>* e, const std::string& who, const typename P::Real* delta, const int32_t* steps, int n_steps) {
+  if (!e->n_worlds) return ens_fail(e, NBODY_ERR_INVALID, who + "nothing uploaded");
+  if (!delta) return ens_fail(e, NBODY_ERR_INVALID, who + "delta is NULL");
+  if (n_steps < 0) return ens_fail(e, NBODY_ERR_INVALID, who + "n_steps < 0");
+  if (steps)
+    for (int64_t k = 0; k < e->n_worlds; ++k)
+      if (steps[k] < 0 || steps[k] > n_steps)
+        return ens_fail(e, NBODY_ERR_INVALID, who + "steps[" + std::to_string(k) + "] = " + std::to_string(steps[k]) + " of world " +
+                                                  std::to_string(k) + " is outside 0 .. n_steps = " + std::to_string(n_steps));
+  return NBODY_OK;
+}
+
 // A sweep: n_steps steps in which world k steps by delta[k] under clamp[k] (NULL: params.clamp in every world) and takes the
 // first steps[k] of them (NULL: all), then stands still; `launch(args)` as in ens_update_with.  Every refusal comes before
 // anything is allocated or enqueued.  The three arrays are read here, into the table the kernels read: the call keeps nothing.
@@ -389,15 +413,7 @@ template <class P, class Launch>
 int ens_sweep_with(EnsembleState<P>* e, const typename P::Real* delta, const float* clamp, const int32_t* steps, int n_steps,
                    nbody_counting* counter, Launch launch) {
   if (!e) return NBODY_ERR_INVALID;
-  const std::string who = std::string(P::kWho) + " sweep: ";
-  if (!e->n_worlds) return ens_fail(e, NBODY_ERR_INVALID, who + "nothing uploaded");
-  if (!delta) return ens_fail(e, NBODY_ERR_INVALID, who + "delta is NULL");
-  if (n_steps < 0) return ens_fail(e, NBODY_ERR_INVALID, who + "n_steps < 0");
-  if (steps)
-    for (int64_t k = 0; k < e->n_worlds; ++k)
-      if (steps[k] < 0 || steps[k] > n_steps)
-        return ens_fail(e, NBODY_ERR_INVALID, who + "steps[" + std::to_string(k) + "] = " + std::to_string(steps[k]) + " of world " +
-                                                  std::to_string(k) + " is outside 0 .. n_steps = " + std::to_string(n_steps));
+  if (int rc = ens_sweep_check(e, std::string(P::kWho) + " sweep: ", delta, steps, n_steps)) return rc;
   if (n_steps == 0) return NBODY_OK;
   ENS_HIPCHK(e, hipSetDevice(e->device));
   const double t_begin = now_s();
@@ -414,6 +430,69 @@ template <class P>
 int ens_sweep(EnsembleState<P>* e, const typename P::Real* delta, const float* clamp, const int32_t* steps, int n_steps, nbody_counting* counter) {
   return ens_sweep_with(e, delta, clamp, steps, n_steps, counter,
                         [e](const typename P::Args& a) { return P::launch(e->stream, e->n_worlds, a); });
+}
+
+// A resident run (nbody_resident_*): the sweep above through another route — one block per world keeps its world in LDS and
+// takes up to kResidentStepsPerLaunch of its steps per launch (ensemble_resident.h), so a call whose largest steps[k] is S
+// enqueues ceil(S / kResidentStepsPerLaunch) launches instead of n_steps.  The arguments and their checks are the sweep's, the
+// table is the sweep's (ens_sweep_table), and so are the arithmetic of a launch and the bookkeeping: the handle's step count
+// advances by n_steps, the seconds go to sum_gravity.  The kernels write the rows in place, so the position buffers do not flip.
+// sizes: the bodies per world of a ragged handle, or NULL (e->n_bodies in every world).  Every refusal comes before anything is
+// allocated or enqueued.
+template <class P>
+int ens_resident_with(EnsembleState<P>* e, const typename P::Real* delta, const float* clamp, const int32_t* steps, int n_steps,
+                      nbody_counting* counter, const int64_t* sizes = nullptr) {
+  if (!e) return NBODY_ERR_INVALID;
+  const std::string who = std::string(P::kWho) + " resident: ";
+  if (int rc = ens_sweep_check(e, who, delta, steps, n_steps)) return rc;
+  int32_t most = steps ? 0 : n_steps;
+  if (steps)
+    for (int64_t k = 0; k < e->n_worlds; ++k) most = std::max(most, steps[k]);
+  int64_t largest = e->n_bodies;
+  for (int64_t k = 0; k < e->n_worlds; ++k) {
+    const int64_t n = sizes ? sizes[k] : e->n_bodies;
+    if (n > kResidentMaxBodies)
+      return ens_fail(e, NBODY_ERR_INVALID, who + "world " + std::to_string(k) + " has " + std::to_string(n) + " bodies; a resident run takes worlds of at most " +
+                                                std::to_string(kResidentMaxBodies) + " (one block per world): sweep is the call for this handle");
+    if (n > largest) largest = n;
+    if (!sizes) break;  // (worlds of one size)
+  }
+  if (n_steps == 0) return NBODY_OK;
+  ENS_HIPCHK(e, hipSetDevice(e->device));
+  const double t_begin = now_s();
+  if (most > 0) {
+    if (int rc = ens_sweep_table(e, delta, clamp, steps, n_steps)) return rc;
+    if (sizes && !e->resident_worlds.p) {
+      const size_t n = (size_t)e->n_worlds;
+      e->resident_host.resize(n);  // (the handle's: the copy below may still read it when an error returns early)
+      uint32_t row0 = 0;
+      for (size_t k = 0; k < n; ++k) {
+        e->resident_host[k] = uint2{row0, (uint32_t)sizes[k]};
+        row0 += (uint32_t)sizes[k];  // (rows of all worlds <= 2^26)
+      }
+      if (int rc = e->resident_worlds.grow(e, n * sizeof(uint2))) return rc;
+      const hipError_t h = hipMemcpyAsync(e->resident_worlds.p, e->resident_host.data(), n * sizeof(uint2), hipMemcpyHostToDevice, e->stream);
+      if (h != hipSuccess) {
+        e->resident_worlds.release();  // (not filled: the next call makes it again)
+        return ens_fail_hip<P>(e, h, "upload of the resident run's table");
+      }
+    }
+    typename P::Args a = ens_args(e);
+    if (clamp) P::sweep_route(a, e->params);
+    a.vel = e->vel;
+    a.sweep = e->sweep_dev.p;
+    const size_t lds = P::resident_lds_bytes((int)largest);
+    for (int64_t base = 0; base < most; base += kResidentStepsPerLaunch) {
+      a.step = (int)base;
+      ENS_HIPCHK(e, P::launch_resident(e->stream, e->n_worlds, sizes ? e->resident_worlds.p : nullptr, lds, a));
+    }
+  }
+  e->updates += (uint64_t)n_steps;  // the handle's steps, as after the sweep: not any world's own
+  ENS_HIPCHK(e, hipStreamSynchronize(e->stream));
+  const double dt = now_s() - t_begin;  // booked as an update's seconds are
+  e->counting.sum_gravity += dt;
+  if (counter) counter->sum_gravity += dt;
+  return NBODY_OK;
 }
 
 template <class P, class Launch> int ens_accel_with(EnsembleState<P>* e, typename P::Real* acc_xy, Launch launch) {

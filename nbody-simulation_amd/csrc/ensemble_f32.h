@@ -28,6 +28,10 @@ struct EnsF32 {
   static EnsSweepWorld sweep_world(float delta, float clamp, int32_t steps) { return EnsSweepWorld{delta, clamp, steps, 0}; }
   static void sweep_route(EnsembleArgs& a, const nbody_params& p) { a.arith = p.arith; }  // (direct_arith_f32's clamp test: per world, in the kernel)
   static hipError_t launch(hipStream_t s, int64_t n_worlds, const EnsembleArgs& a) { return launch_ensemble_step(s, n_worlds, a); }
+  static hipError_t launch_resident(hipStream_t s, int64_t n_worlds, const uint2* worlds, size_t lds_bytes, const EnsembleArgs& a) {
+    return launch_ensemble_resident(s, n_worlds, worlds, lds_bytes, a);
+  }
+  static size_t resident_lds_bytes(int n_bodies) { return ensemble_resident_lds_bytes(n_bodies); }
 };
 
 }  // namespace nbody

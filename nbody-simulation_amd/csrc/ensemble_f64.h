@@ -30,6 +30,10 @@ struct EnsF64 {
   static Ens64SweepWorld sweep_world(double delta, float clamp, int32_t steps) { return Ens64SweepWorld{delta, (double)clamp, steps, 0}; }
   static void sweep_route(Ensemble64Args& a, const nbody_params& p) { a.fast = p.arith == NBODY_ARITH_FAST ? 1 : 0; }  // (direct_fast_f64's clamp test: per world, in the kernel)
   static hipError_t launch(hipStream_t s, int64_t n_worlds, const Ensemble64Args& a) { return launch_ensemble64_step(s, n_worlds, a); }
+  static hipError_t launch_resident(hipStream_t s, int64_t n_worlds, const uint2* worlds, size_t lds_bytes, const Ensemble64Args& a) {
+    return launch_ensemble64_resident(s, n_worlds, worlds, lds_bytes, a);
+  }
+  static size_t resident_lds_bytes(int n_bodies) { return ensemble64_resident_lds_bytes(n_bodies); }
 };
 
 }  // namespace nbody

@@ -78,3 +78,8 @@ NB_API int nbody_wsweep_ragged(nbody_ragged* e, uint32_t flags, const float* del
   return ens_wsweep_with<RagF32>(e, flags, delta, clamp, steps, n_steps, stride, limit2, height, out, rows, counter, ragged_rows<RagF32>(e),
         [e](const RagF32::Args& a) { return ragged_launch_all<RagF32>(e, a); });
 }
+// (a resident run — that sweep with every world kept in LDS, include/nbody_ensemble.h: likewise a prefix of its own)
+NB_API int nbody_resident_ragged(nbody_ragged* e, const float* delta, const float* clamp, const int32_t* steps, int n_steps,
+                                 nbody_counting* counter) {
+  return ragged_resident<RagF32>(e, delta, clamp, steps, n_steps, counter);
+}

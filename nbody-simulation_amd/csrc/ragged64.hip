@@ -75,3 +75,8 @@ NB_API int nbody_wsweep_ragged64(nbody_ragged64* e, uint32_t flags, const double
   return ens_wsweep_with<RagF64>(e, flags, delta, clamp, steps, n_steps, stride, limit2, height, out, rows, counter, ragged_rows<RagF64>(e),
         [e](const RagF64::Args& a) { return ragged_launch_all<RagF64>(e, a); });
 }
+// (a resident run — that sweep with every world kept in LDS, include/nbody_ensemble.h: likewise a prefix of its own)
+NB_API int nbody_resident_ragged64(nbody_ragged64* e, const double* delta, const float* clamp, const int32_t* steps, int n_steps,
+                                   nbody_counting* counter) {
+  return ragged_resident<RagF64>(e, delta, clamp, steps, n_steps, counter);
+}

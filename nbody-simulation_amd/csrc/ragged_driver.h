@@ -81,6 +81,10 @@ template <class P>
 int ragged_sweep(RaggedState<P>* e, const typename P::Real* delta, const float* clamp, const int32_t* steps, int n_steps, nbody_counting* counter) {
   return ens_sweep_with<P>(e, delta, clamp, steps, n_steps, counter, [e](const typename P::Args& a) { return ragged_launch_all<P>(e, a); });
 }
+template <class P>
+int ragged_resident(RaggedState<P>* e, const typename P::Real* delta, const float* clamp, const int32_t* steps, int n_steps, nbody_counting* counter) {
+  return ens_resident_with<P>(e, delta, clamp, steps, n_steps, counter, e && e->n_worlds ? e->sizes.data() : nullptr);
+}
 template <class P> int ragged_accel(RaggedState<P>* e, typename P::Real* acc_xy) {
   return ens_accel_with<P>(e, acc_xy, [e](const typename P::Args& a) { return ragged_launch_all<P>(e, a); });
 }

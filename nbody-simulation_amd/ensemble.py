@@ -71,6 +71,11 @@ two together, a `sweep` watched on every world's own schedule — world k is sam
 against its own clamp[k] where limit2 is None — with world k's record and rows bit for bit those of `watch` on the same class
 holding world k alone, and the rows afterwards those of `sweep`.  `watch_sweep_plan(steps, n_steps, stride, resume)` gives the
 samples per world and the number of sampling launches of a schedule in host code.
+
+The four classes without tracers — `Ensemble`, `Ensemble64`, `RaggedEnsemble`, `RaggedEnsemble64` — have `run(delta, n_steps=None,
+clamp=None, steps=None)` (nbody_resident_*): `sweep` as a resident run, for worlds of at most 256 bodies.  One block per world
+keeps the world in LDS and takes up to 1024 of its steps per launch; the rows afterwards are bit for bit those of `sweep`.
+`resident_plan(sizes, steps, n_steps, dtype)` gives the launches of such a call and their LDS in host code.
 """
 from __future__ import annotations
 
@@ -518,6 +523,22 @@ class _Sweep:
         self.h.sweep(*args, counter)
 
 
+class _Resident:
+    """`run` for the ensemble classes without tracers: the class keeps `_n_worlds` and `_dtype`, its handle has `resident`."""
+
+    def run(self, delta, n_steps=None, clamp=None, steps=None, counter: Counting | None = None):
+        """`sweep(delta, clamp, steps, n_steps=n_steps)` as a resident run (nbody_resident_*): every world is one block that
+        keeps its positions and velocities in LDS and takes up to 1024 of its steps per launch, instead of one launch per step.
+        delta is one time step for every world or one per world [B]; clamp, steps and n_steps are `sweep`'s.  The rows, the step
+        count and the delta-stream sequence afterwards are bit for bit those after that `sweep`.  Worlds of at most 256 bodies
+        only: the library refuses the call otherwise, and nothing moves.  The arguments are checked here, with ValueError, before
+        the library is touched."""
+        if delta is not None and np.ndim(delta) == 0:
+            delta = np.full(self._n_worlds, delta)
+        args = _checked_sweep(type(self).__name__, self._n_worlds, self._dtype, delta, clamp, steps, n_steps, "run")
+        self.h.resident(*args, counter)
+
+
 def _checked(position, velocity, weight, dtype=np.float32, who=None, other=None):
     """-> (B, n, position[B,n,2], velocity[B,n,2], weight[B,n] or None), contiguous; ValueError for anything else.  The
     messages name `who`, or the class of that dtype: Ensemble (float32) or Ensemble64 (float64); a wrong dtype adds `other`, or
@@ -627,7 +648,7 @@ class _EnsembleBase(_WatchSweep, _Watch, _Encounters, _Summary, _Sweep):
         self.close()
 
 
-class Ensemble(_EnsembleBase):
+class Ensemble(_Resident, _EnsembleBase):
     """The ensemble in single precision: position, velocity [B, n, 2] float32."""
     _dtype = np.float32
 
@@ -636,7 +657,7 @@ class Ensemble(_EnsembleBase):
         return _capi.EnsembleHandle(device)
 
 
-class Ensemble64(_EnsembleBase):
+class Ensemble64(_Resident, _EnsembleBase):
     """The ensemble in double precision: position, velocity [B, n, 2] float64.  arith "auto" and "exact" are the exact chain;
     "fast" is opt-in and gated per world and per step on the device; clamp is a float, widened to double by the library."""
     _dtype = np.float64
@@ -878,7 +899,7 @@ class _RaggedBase(_WatchSweep, _Watch, _Encounters, _Summary, _Sweep):
         self.close()
 
 
-class RaggedEnsemble(_RaggedBase):
+class RaggedEnsemble(_Resident, _RaggedBase):
     """Worlds of different sizes, stepped together: positions, velocities are sequences of [n_k, 2] float32 arrays, weights a
     sequence of [n_k] integer arrays or None (all 1).  1 .. 4096 bodies per world, at most 2^26 bodies in all."""
     _dtype = np.float32
@@ -891,7 +912,7 @@ class RaggedEnsemble(_RaggedBase):
         self._create(positions, velocities, weights, device, clamp, arith)
 
 
-class RaggedEnsemble64(_RaggedBase):
+class RaggedEnsemble64(_Resident, _RaggedBase):
     """The ragged ensemble in double precision: positions, velocities are sequences of [n_k, 2] float64 arrays.  arith "exact"
     and "auto" are the exact chain; "fast" is opt-in and gated per world and per step on the device; clamp is a float, widened
     to double by the library."""
@@ -1127,6 +1148,29 @@ def rr_plan(sizes, tracer_counts, dtype=np.float32):
         raise ValueError("rr_plan: one tracer count >= 0 per world, at most 2^26 tracers in all")
     launch, first, lds, blocks = _capi.rr_plan(sizes, counts, f64=dtype == np.float64)
     return dict(launch_of_world=launch, first_block_of_world=first, lds_bytes=lds, blocks=blocks)
+
+
+RESIDENT_MAX_BODIES = _capi.RESIDENT_MAX_BODIES                # per world of a resident run: one block
+RESIDENT_STEPS_PER_LAUNCH = _capi.RESIDENT_STEPS_PER_LAUNCH    # of a resident run
+
+
+def resident_plan(sizes, steps=None, n_steps=1, dtype=np.float32):
+    """What `run(..., steps=steps, n_steps=n_steps)` on worlds of these sizes enqueues (nbody_resident_plan; host code, no GPU
+    needed) -> dict: n_launches — ceil(max(steps) / 1024), 0 where no world takes a step — and lds_bytes, the dynamic LDS of a
+    launch, which is that of the largest world.  steps is one count per world or None (every world takes n_steps)."""
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError(f"resident_plan: dtype must be float32 or float64, got {dtype}")
+    sizes = np.ascontiguousarray([int(n) for n in sizes], dtype=np.int64)
+    if isinstance(n_steps, bool) or not isinstance(n_steps, (int, np.integer)) or not -(1 << 31) <= int(n_steps) < 1 << 31:
+        raise ValueError(f"resident_plan: n_steps must be an integer, got {n_steps!r}")
+    if steps is not None:
+        steps = np.asarray(steps)
+        if steps.shape != sizes.shape or steps.dtype.kind not in "iu" or (steps.size and (steps.min() < -(1 << 31) or steps.max() >= 1 << 31)):
+            raise ValueError(f"resident_plan: steps must hold one integer per world, got shape {steps.shape} of {steps.dtype}")
+        steps = np.ascontiguousarray(steps, dtype=np.int32)
+    launches, lds = _capi.resident_plan(sizes, steps, int(n_steps), dtype == np.float64)
+    return dict(n_launches=launches, lds_bytes=lds)
 
 
 def ragged_plan(sizes, dtype=np.float32):
